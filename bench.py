@@ -12,7 +12,11 @@ as N grows -> "scaling": "strong".
 Synthetic data (no network): means ~ U(-0.6,0.6)^3, opacity sigmoid(-2.2), colours sigmoid(0.1 U),
 density-matched scale 0.1061*(1200/N)^(1/3); targets are seeded random images.
 
-Also reported on rank 0:
+A plain run (no --full) does only what the headline needs: set up, warm up, time the steps, write the
+outputs when --dump-outputs is given, print the result line (metric, value, unit, ms_per_step, ... and the
+workload's config).  --dump-outputs DIR writes what the last timed step handed its caller (dump_outputs).
+
+With --full, also reported on rank 0 (each from runs of its own after the timed region):
   roofline      the dominant kernel (the backward splat; both splats under "splats"): at 32-pixel tiles its
                 executed 16-bit MFMA FLOP/s against the dense bf16 peak (48 v_mfma_f32_32x32x16 per 32 pairs),
                 with SURVEY.md 8(d)'s byte model beside it under "hbm" (48 B per pair forward, 84 B per pair
@@ -48,7 +52,8 @@ Also reported on rank 0:
                 profiles/pmc_traffic.json (tools/pmc_profile.sh), used only when its source stamp equals
                 the sha256 of this tree's gr_hip.hip (else flagged stale and not used).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline] [--device cpu]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full [--no-cpu-baseline ...]]
+       [--device cpu]
 N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
      --master-port P bench.py --gpus N --steps K --warmup W
      (or plain `python bench.py --gpus N`: it starts that launcher itself as a child process)
@@ -121,6 +126,12 @@ def parse():
     ap.add_argument("--gaussians", type=int, default=1_000_000)
     ap.add_argument("--views", type=int, default=50)
     ap.add_argument("--res", type=int, default=800)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything else the line can carry: roofline and "
+                         "per-kernel figures, the other precision modes, the drop-in op, PSNR against the dense "
+                         "reference, the shader clock, the CPU baseline (the --no-* options below trim that)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, parameters, gradients) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra-modes", action="store_true",
                     help="skip the extra timed steps of the default (depth-loss) precision mode")
@@ -435,6 +446,37 @@ def splat_replay(fitter, device) -> dict:
     return out
 
 
+DUMP_BUDGET_BYTES = 60_000_000  # of --dump-outputs, all files together (under 64 MB)
+
+
+def dump_outputs(path: str, fitter, loss) -> dict:
+    """What the last timed step handed its caller, as float32 ``path/<name>.npy``: the loss step() returned, the
+    parameters it updated (``means``, ``scales_raw``, ...) and the gradients it left in their ``.grad``
+    (``grad_<name>``), rows in the caller's own (canonical) Gaussian order, not the trainer's Morton order.  Above
+    DUMP_BUDGET_BYTES in all, the same seeded sample of Gaussians (sorted row indices, seed 0) of every array."""
+    os.makedirs(path, exist_ok=True)
+    canon = fitter.canonical_params()  # (settles a replayed step first: the loss below is final)
+    arrays = {"loss": loss.detach().reshape(1)}
+    for k, p in fitter.params.items():
+        arrays[k] = canon[k].detach()
+        if p.grad is not None:
+            g = p.grad.detach()
+            if fitter.perm is not None:
+                c = torch.empty_like(g)
+                c[fitter.perm] = g
+                g = c
+            arrays["grad_" + k] = g
+    n = int(fitter.params["means"].shape[0])
+    row_bytes = sum(4 * a.numel() // max(n, 1) for k, a in arrays.items() if k != "loss")
+    rows = None
+    if n * row_bytes > DUMP_BUDGET_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n, DUMP_BUDGET_BYTES // row_bytes, replace=False))
+    for k, a in arrays.items():
+        a = a.to(torch.float32).cpu().numpy()
+        np.save(os.path.join(path, k + ".npy"), a if (rows is None or k == "loss") else a[rows])
+    return {"dir": path, "arrays": sorted(arrays), "gaussians": n, "rows": n if rows is None else int(rows.size)}
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -455,7 +497,7 @@ def main():
             dist.init_process_group("gloo")
     sync = torch.cuda.synchronize if on_gpu else (lambda: None)
     n, V, R = args.gaussians, args.views, args.res
-    clk0 = sclk_mhz() if (on_gpu and rank == 0) else None
+    clk0 = sclk_mhz() if (args.full and on_gpu and rank == 0) else None
 
     params = synthetic_params(n, device)
     cams = fm.orbit_cameras(V, R, R, device)
@@ -491,6 +533,7 @@ def main():
     elapsed, loss = timed(args.steps)
     pixels = V * R * R * args.steps
     value = pixels / elapsed / 1e6
+    dumped = dump_outputs(args.dump_outputs, fitter, loss) if (args.dump_outputs and rank == 0) else None
 
     if not on_gpu:  # dry run of the launcher / sharding: no measurement keys
         if rank == 0:
@@ -498,6 +541,48 @@ def main():
                               "value": round(value, 4), "unit": "Mpixels/sec", "n_gpus": world, "steps": args.steps,
                               "warmup": args.warmup, "device": "cpu", "views_per_rank": views_per_rank,
                               "loss": float(loss)}), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    def headline(tile, pairs=None):
+        """The result line's head: the metric, its value and the workload (pairs: per view, when they were counted)."""
+        counted = {} if pairs is None else {"pairs_per_view": int(pairs), "core_pairs_per_view": int(pairs)}
+        return {
+            "metric": "Mpixels/sec fwd+bwd @1M Gaussians 800\u00d7800; PSNR vs torch ref",
+            "value": round(value, 2),
+            "unit": "Mpixels/sec",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(1e3 * elapsed / args.steps, 3),
+            "higher_is_better": True,
+            "scaling": "strong",
+            "vs_baseline": None,
+            "dtype": "f32 (splat contractions on v_mfma_f32_32x32x16_f16 with f32 accumulation; every operand in two "
+                     "round-to-nearest f16 pieces, pre-scaled into f16's normal range, three piece products: "
+                     "<= 3*2^-22 per product, forward and backward; no-depth-gradient mode)",
+            "data": "synthetic (seeded Gaussians per SURVEY.md 8(d), random targets)",
+            "config": {"workload": f"C4: {n} Gaussians, {V} orbit views {R}x{R}, fwd+bwd+grad all-reduce+Adam per step",
+                       "gaussians": n, "views": V, "width": R, "height": R, "cutoff_sigma": tr.FIT_CUTOFF, "core_cutoff_sigma": tr.FIT_CUTOFF,
+                       "tile": tile,
+                       "render_path": "fused fit path: per view gr_fwd_render_l1 (forward, loss and upstream gradients) "
+                                      "+ gr_bwd_splat + gr_gather_view (per-Gaussian sums), then gr_reduce_sums (chain rule) "
+                                      "per batch of a stream's views (fit_multiview._views_direct, 4 HIP streams)",
+                       "scale": round(0.1061 * (1200.0 / n) ** (1.0 / 3.0), 5), "seed": 0,
+                       "parallelism": f"view-sharded dp{world}", "views_per_rank": views_per_rank, **counted,
+                       "gaussian_order": "random" if args.no_reorder else
+                       f"morton (trainer layout, re-established every {fm.RESORT_EVERY} steps)"},
+        }
+
+    if not args.full:  # the plain run: the headline alone, nothing measured beyond the timed steps
+        if rank == 0:
+            out = headline(fitter.views_tile())
+            out["loss"] = float(loss)
+            if dumped:
+                out["dumped_outputs"] = dumped
+            print(json.dumps(out), flush=True)
         if world > 1:
             dist.barrier()
             dist.destroy_process_group()
@@ -632,32 +717,8 @@ def main():
             return {"pairs_per_view": int(k), "bytes_per_view": int(b), "roofline_mpx_per_s": round(roof_mpx, 1),
                     "frac": round(value / (roof_mpx * world), 4)}
 
-        out = {
-            "metric": "Mpixels/sec fwd+bwd @1M Gaussians 800\u00d7800; PSNR vs torch ref",
-            "value": round(value, 2),
-            "unit": "Mpixels/sec",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(1e3 * elapsed / args.steps, 3),
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "f32 (splat contractions on v_mfma_f32_32x32x16_f16 with f32 accumulation; every operand in two "
-                     "round-to-nearest f16 pieces, pre-scaled into f16's normal range, three piece products: "
-                     "<= 3*2^-22 per product, forward and backward; no-depth-gradient mode)",
-            "data": "synthetic (seeded Gaussians per SURVEY.md 8(d), random targets)",
-            "config": {"workload": f"C4: {n} Gaussians, {V} orbit views {R}x{R}, fwd+bwd+grad all-reduce+Adam per step",
-                       "gaussians": n, "views": V, "width": R, "height": R, "cutoff_sigma": tr.FIT_CUTOFF, "core_cutoff_sigma": tr.FIT_CUTOFF,
-                       "tile": replay["tile"],
-                       "render_path": "fused fit path: per view gr_fwd_render_l1 (forward, loss and upstream gradients) "
-                                      "+ gr_bwd_splat + gr_gather_view (per-Gaussian sums), then gr_reduce_sums (chain rule) "
-                                      "per batch of a stream's views (fit_multiview._views_direct, 4 HIP streams)",
-                       "scale": round(0.1061 * (1200.0 / n) ** (1.0 / 3.0), 5), "seed": 0,
-                       "parallelism": f"view-sharded dp{world}", "views_per_rank": views_per_rank,
-                       "pairs_per_view": int(avg_pairs), "core_pairs_per_view": int(avg_core),
-                       "gaussian_order": "random" if args.no_reorder else
-                       f"morton (trainer layout, re-established every {fm.RESORT_EVERY} steps)"},
+        out = headline(replay["tile"], avg_pairs)
+        out.update({
             # the dominant splat kernel against the HBM roofline (SURVEY.md 8(d) bytes per pair); both
             # splats in "splats", with their MFMA rates beside
             "roofline": roof(dominant),
@@ -679,7 +740,9 @@ def main():
             "pmc": {k: v for k, v in pmc.items() if k != "kernels"},
             "sclk_mhz": {"before": clk0, "after": clk1},
             "loss": float(loss),
-        }
+        })
+        if dumped:
+            out["dumped_outputs"] = dumped
         if not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(n, R, V)
         print(json.dumps(out), flush=True)

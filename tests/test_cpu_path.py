@@ -149,3 +149,44 @@ def test_bench_cpu_baseline_small():
     assert out["value"] > 0 and out["kind"] == "port" and out["oracle"]["value"] > 0 and out["c1"]["value"] > 0
     assert out["usable_cores"] == cores and out["torch_threads"] == cores and out["cores"] == cores
     assert "sched_getaffinity" in how and "unscaled" in out["sample"]
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs): after a step of a small fit on host tensors it writes the loss, every
+    parameter and every gradient as float32 .npy in the canonical Gaussian order; over the byte budget, the same seeded
+    rows of every array, the same from call to call."""
+    import importlib
+    import os
+
+    bench = importlib.import_module("bench")
+    fm = importlib.import_module("3dgaussian_amd.fit_multiview")
+    dev = torch.device("cpu")
+    n, V, R = 300, 2, 24
+    params = bench.synthetic_params(n, dev)
+    g = torch.Generator().manual_seed(1)
+    targets = [torch.rand((R, R, 3), generator=g) for _ in range(V)]
+    fitter = fm.ViewShardedFitter(params, fm.orbit_cameras(V, R, R, dev), targets, R, R, lr=0.02)
+    assert fitter.perm is not None  # the trainer's Morton order: the dump must undo it
+    loss = fitter.step()
+    info = bench.dump_outputs(str(tmp_path / "all"), fitter, loss)
+    names = ["loss"] + list(params) + ["grad_" + k for k in params]
+    assert info["rows"] == n and info["arrays"] == sorted(names)
+    assert sorted(os.listdir(tmp_path / "all")) == sorted(k + ".npy" for k in names)
+    got = {k: np.load(tmp_path / "all" / (k + ".npy")) for k in names}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert got["loss"].shape == (1,) and got["loss"][0] == np.float32(float(loss))
+    canon = fitter.canonical_params()
+    for k, p in fitter.params.items():
+        assert np.array_equal(got[k], canon[k].detach().numpy())
+        assert np.array_equal(got["grad_" + k][fitter.perm.numpy()], p.grad.numpy()) and np.abs(got["grad_" + k]).max() > 0
+    # over the budget: 100 of the 300 Gaussians (80 bytes a row), the same sorted rows in every array and every call
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 100 * 80)
+    for d in ("s1", "s2"):
+        assert bench.dump_outputs(str(tmp_path / d), fitter, loss)["rows"] == 100
+    rows = np.sort(np.random.default_rng(0).choice(n, 100, replace=False))
+    for k in names:
+        a = np.load(tmp_path / "s1" / (k + ".npy"))
+        assert np.array_equal(a, np.load(tmp_path / "s2" / (k + ".npy")))
+        assert np.array_equal(a, got[k] if k == "loss" else got[k][rows])
+    total = sum(os.path.getsize(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1"))
+    assert total <= 100 * 80 + 128 * len(names) + 4  # the budget plus the .npy headers and the loss

@@ -12,7 +12,7 @@ mkdir -p $O
 for r in $(seq 1 $ROUNDS); do
   for d in "$@"; do
     name=$(basename $(cd $R/$d && pwd))
-    (cd $R/$d && timeout -k 10 240 python bench.py --steps 20 --warmup 2 --no-cpu-baseline --no-psnr --no-dropin \
+    (cd $R/$d && timeout -k 10 240 python bench.py --full --steps 20 --warmup 2 --no-cpu-baseline --no-psnr --no-dropin \
       --no-extra-modes > $O/ab_${name}_$r.log 2>&1)
     echo "$name round $r: $(python3 -c "
 import json,sys

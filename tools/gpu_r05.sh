@@ -15,9 +15,9 @@ for step in "$@"; do
   echo "== $step $(date +%T)"
   case $step in
     bench)
-      (cd $R && timeout -k 10 500 python bench.py > $O/bench.log 2>&1) ;;
+      (cd $R && timeout -k 10 500 python bench.py --full > $O/bench.log 2>&1) ;;
     benchq)
-      (cd $R && timeout -k 10 300 python bench.py --no-cpu-baseline --no-psnr > $O/benchq.log 2>&1) ;;
+      (cd $R && timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-psnr >$O/benchq.log 2>&1) ;;
     stats1)
       (cd /tmp && GR_STREAMS=1 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/stats1 -o run --output-format csv -- \
         python3 $R/bench.py --steps 20 --warmup 2 --no-cpu-baseline --no-extra-modes --no-dropin --no-psnr > $O/bench_prof1.log 2>&1)
