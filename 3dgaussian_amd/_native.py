@@ -20,6 +20,7 @@ _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GR_HIP_LIB", os.path.join(_PKG_DIR, "libgr_hip.so"))
 
 TILE = 16
+SSIM_TILE = 16  # GR_SSIM_TILE: tile edge of the D-SSIM kernels
 
 GR_OK = 0
 GR_ERR_INVALID_ARGUMENT = 1
@@ -212,6 +213,10 @@ _SIG = {
     "gr_l1_loss_fwd": (ctypes.c_int, [_P, _P, ctypes.c_int64, _P, _P, ctypes.c_int64, ctypes.c_float, _P, _P,
                                       ctypes.c_size_t, _P]),
     "gr_l1_loss_bwd": (ctypes.c_int, [_P, _P, ctypes.c_int64, _P, _P, ctypes.c_int64, ctypes.c_float, _P, _P, _P, _P]),
+    "gr_ssim_ws_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "gr_ssim_fwd": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P,
+                                   ctypes.c_size_t, _P]),
+    "gr_ssim_bwd": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, ctypes.c_size_t, _P, _P]),
     "gr_last_error": (ctypes.c_char_p, []),
     "gr_version": (ctypes.c_char_p, []),
 }

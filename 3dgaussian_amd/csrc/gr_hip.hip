@@ -4467,6 +4467,186 @@ __global__ __launch_bounds__(256) void k_l1_grad(const float* __restrict__ a, co
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// D-SSIM loss (the caller's side of the render op): dssim = 1 - mean(m) over the H*W*C values of two
+// channel-last images, m the SSIM index under the 11x11 Gaussian window (sigma 1.5, zero padding):
+//   mx = conv(x), my = conv(y), sx = conv(x^2) - mx^2, sy = conv(y^2) - my^2, sxy = conv(xy) - mx my
+//   m = A1 A2 / (B1 B2), A1 = 2 mx my + C1, A2 = 2 sxy + C2, B1 = mx^2 + my^2 + C1, B2 = sx + sy + C2.
+// One workgroup per GR_SSIM_TILE x GR_SSIM_TILE pixel tile.  A row of the image is W*C floats and the
+// window acts on floats C apart, so the tile is handled as 16 rows of TC = 16 C consecutive floats
+// ("values"), any C alike.  The tile and its 5-pixel halo of both images are staged in LDS (out-of-image
+// values as the zero padding), the five windowed sums are taken separably (horizontal pass over the 26
+// staged rows into LDS, then the vertical pass), 22 taps instead of 121 per sum.
+// LDS addressing: every pass gives consecutive lanes consecutive values of a row, and the horizontal
+// sums are stored at pitch TC without padding, so in the vertical pass (which walks down a column) a
+// wave's 64 lanes read 64 consecutive dwords at every tap, rows wrapping included: one address per
+// bank in each 32-lane group of ds_read_b32, no conflicts.  In the horizontal pass a wave that spans
+// two staged rows skips the 10 C halo values between them: at most 2 addresses on a few banks.
+// LDS per workgroup: (2 * 26 * 26 C + 5 * 26 * 16 C) * 4 B + 1 KiB = 14.4 / 27.8 / 41.2 / 54.6 KiB for
+// C = 1..4 (three workgroups per CU at C = 3).
+// Deterministic: a fixed grid, a tree sum per workgroup, the final sum in double in a fixed order.
+// ------------------------------------------------------------------------------------------------
+constexpr int ST = GR_SSIM_TILE;  // tile edge in pixels
+constexpr int SR = 5;             // window radius
+constexpr int SE = ST + 2 * SR;   // staged rows (and staged pixels per row)
+constexpr float SSIM_C1 = 1e-4f, SSIM_C2 = 9e-4f;
+__constant__ float SSIM_G[2 * SR + 1] = {0.001028380123898387f, 0.0075987582094967365f, 0.036000773310661316f,
+                                         0.10936068743467331f,  0.21300554275512695f,   0.26601171493530273f,
+                                         0.21300554275512695f,  0.10936068743467331f,   0.036000773310661316f,
+                                         0.0075987582094967365f, 0.001028380123898387f};
+
+// Stages one image's tile + halo: dst[r * SE * C + c] = value c of row r of the staged window (0 outside the image).
+template <int C>
+__device__ __forceinline__ void ssim_stage(const float* __restrict__ src, int H, int WC, int y0, int v0, float* dst) {
+  constexpr int SP = SE * C;
+  for (int e = threadIdx.x; e < SE * SP; e += 256) {
+    const int r = e / SP, c = e - r * SP;
+    const int gy = y0 - SR + r, gv = v0 - SR * C + c;
+    dst[e] = (gy >= 0 && gy < H && gv >= 0 && gv < WC) ? src[(int64_t)gy * WC + gv] : 0.0f;
+  }
+}
+
+// GRAD: also writes, per value, the three maps the backward convolves (planes of H*W*C floats):
+//   maps[0] = dm/dmx with sx and sxy expressed through mx: 2 (my (A2 - A1) - mx m (B2 - B1)) / (B1 B2)
+//   maps[1] = dm/dsx = -m / B2            maps[2] = dm/dsxy = 2 A1 / (B1 B2)
+template <int C, bool GRAD>
+__global__ __launch_bounds__(256) void k_ssim_fwd(const float* __restrict__ x, const float* __restrict__ y, int H, int W,
+                                                  float* __restrict__ partial, float* __restrict__ maps) {
+  constexpr int TC = ST * C, SP = SE * C;
+  __shared__ float tx[SE * SP], ty[SE * SP];
+  __shared__ float hs[5][SE * TC];
+  __shared__ float red[256];
+  const int t = threadIdx.x;
+  const int WC = W * C;
+  const int y0 = blockIdx.y * ST, v0 = blockIdx.x * TC;
+  ssim_stage<C>(x, H, WC, y0, v0, tx);
+  ssim_stage<C>(y, H, WC, y0, v0, ty);
+  __syncthreads();
+  for (int o = t; o < SE * TC; o += 256) {
+    const int r = o / TC, c = o - r * TC;
+    const float* px = tx + r * SP + c;
+    const float* py = ty + r * SP + c;
+    float a = 0.0f, b = 0.0f, aa = 0.0f, bb = 0.0f, ab = 0.0f;
+#pragma unroll
+    for (int k = 0; k <= 2 * SR; ++k) {
+      const float g = SSIM_G[k], u = px[k * C], v = py[k * C];
+      a = fmaf(g, u, a);
+      b = fmaf(g, v, b);
+      aa = fmaf(g, u * u, aa);
+      bb = fmaf(g, v * v, bb);
+      ab = fmaf(g, u * v, ab);
+    }
+    hs[0][o] = a;
+    hs[1][o] = b;
+    hs[2][o] = aa;
+    hs[3][o] = bb;
+    hs[4][o] = ab;
+  }
+  __syncthreads();
+  const int64_t N = (int64_t)H * WC;
+  float acc = 0.0f;
+  for (int o = t; o < ST * TC; o += 256) {
+    const int r = o / TC, c = o - r * TC;
+    float mx = 0.0f, my = 0.0f, exx = 0.0f, eyy = 0.0f, exy = 0.0f;
+#pragma unroll
+    for (int k = 0; k <= 2 * SR; ++k) {
+      const float g = SSIM_G[k];
+      mx = fmaf(g, hs[0][o + k * TC], mx);
+      my = fmaf(g, hs[1][o + k * TC], my);
+      exx = fmaf(g, hs[2][o + k * TC], exx);
+      eyy = fmaf(g, hs[3][o + k * TC], eyy);
+      exy = fmaf(g, hs[4][o + k * TC], exy);
+    }
+    const int gy = y0 + r, gv = v0 + c;
+    if (gy < H && gv < WC) {
+      const float sx = fmaf(-mx, mx, exx), sy = fmaf(-my, my, eyy), sxy = fmaf(-mx, my, exy);
+      const float A1 = fmaf(2.0f * mx, my, SSIM_C1), A2 = fmaf(2.0f, sxy, SSIM_C2);
+      const float B1 = fmaf(mx, mx, fmaf(my, my, SSIM_C1)), B2 = sx + sy + SSIM_C2;
+      const float rr = 1.0f / (B1 * B2);
+      const float m = (A1 * A2) * rr;
+      acc += m;
+      if (GRAD) {
+        const int64_t off = (int64_t)gy * WC + gv;
+        maps[off] = 2.0f * rr * (my * (A2 - A1) - mx * m * (B2 - B1));
+        maps[N + off] = -m / B2;
+        maps[2 * N + off] = 2.0f * A1 * rr;
+      }
+    }
+  }
+  red[t] = acc;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (t < w) red[t] += red[t + w];
+    __syncthreads();
+  }
+  if (t == 0) partial[blockIdx.y * gridDim.x + blockIdx.x] = red[0];
+}
+
+__global__ __launch_bounds__(256) void k_ssim_final(const float* __restrict__ partial, int blocks, int64_t n,
+                                                    float* __restrict__ dssim) {
+  __shared__ double r[256];
+  const int t = threadIdx.x;
+  double s = 0.0;
+  for (int i = t; i < blocks; i += 256) s += (double)partial[i];
+  r[t] = s;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (t < w) r[t] += r[t + w];
+    __syncthreads();
+  }
+  if (t == 0) *dssim = (float)(1.0 - r[0] / (double)n);
+}
+
+// d dssim / d x, the same tiling: the three maps are convolved with the window (symmetric, zero padding: the
+// transposed convolution is the convolution itself) and
+//   g_x = -(g / (H W C)) (conv(maps[0]) + 2 x conv(maps[1]) + y conv(maps[2])),  g = *g_loss.
+template <int C>
+__global__ __launch_bounds__(256) void k_ssim_bwd(const float* __restrict__ x, const float* __restrict__ y, int H, int W,
+                                                  const float* __restrict__ maps, const float* __restrict__ g_loss,
+                                                  float* __restrict__ gx) {
+  constexpr int TC = ST * C, SP = SE * C;
+  __shared__ float tm[3][SE * SP];
+  __shared__ float hs[3][SE * TC];
+  const int t = threadIdx.x;
+  const int WC = W * C;
+  const int64_t N = (int64_t)H * WC;
+  const int y0 = blockIdx.y * ST, v0 = blockIdx.x * TC;
+  for (int q = 0; q < 3; ++q) ssim_stage<C>(maps + q * N, H, WC, y0, v0, tm[q]);
+  __syncthreads();
+  for (int o = t; o < SE * TC; o += 256) {
+    const int r = o / TC, c = o - r * TC;
+    const int s = r * SP + c;
+    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f;
+#pragma unroll
+    for (int k = 0; k <= 2 * SR; ++k) {
+      const float g = SSIM_G[k];
+      a0 = fmaf(g, tm[0][s + k * C], a0);
+      a1 = fmaf(g, tm[1][s + k * C], a1);
+      a2 = fmaf(g, tm[2][s + k * C], a2);
+    }
+    hs[0][o] = a0;
+    hs[1][o] = a1;
+    hs[2][o] = a2;
+  }
+  __syncthreads();
+  const float scale = -(*g_loss / (float)N);
+  for (int o = t; o < ST * TC; o += 256) {
+    const int r = o / TC, c = o - r * TC;
+    const int gy = y0 + r, gv = v0 + c;
+    if (gy >= H || gv >= WC) continue;
+    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f;
+#pragma unroll
+    for (int k = 0; k <= 2 * SR; ++k) {
+      const float g = SSIM_G[k];
+      a0 = fmaf(g, hs[0][o + k * TC], a0);
+      a1 = fmaf(g, hs[1][o + k * TC], a1);
+      a2 = fmaf(g, hs[2][o + k * TC], a2);
+    }
+    const int64_t off = (int64_t)gy * WC + gv;
+    gx[off] = scale * fmaf(y[off], a2, fmaf(2.0f * x[off], a1, a0));
+  }
+}
+
 // The fit loop's parameter update (fit_multiview_stub.py:268-275 activations, :307-308 regulariser,
 // :311 Adam) for one parameter tensor, fused into one pass over its elements (gr_fit_param_step):
 //   g_raw = act'(raw) * (((acc0 + acc1) + ...) + reg)     d loss / d raw parameter (torch's backward of
@@ -6226,6 +6406,70 @@ gr_status gr_l1_loss_bwd(const float* a, const float* b, int64_t n1, const float
   const int64_t nm = n1 > n2 ? n1 : n2;
   hipLaunchKernelGGL(k_l1_grad, dim3(blocks_for(nm)), dim3(256), 0, (hipStream_t)stream, a, b, n1, c, d, n2, w2, g_loss,
                      g_a, g_c);
+  GR_HIP_TRY(hipGetLastError());
+  return GR_OK;
+}
+
+// D-SSIM workspace: the per-workgroup partial sums of m, then (want_grad) the three maps of the backward.
+static bool ssim_shape_ok(int height, int width, int channels) {
+  return height > 0 && width > 0 && channels >= 1 && channels <= 4 && (int64_t)height * width * channels <= (1ll << 30) &&
+         tiles_y_of(height, ST) <= 65535;  // (grid.y)
+}
+static size_t ssim_partial_bytes(int height, int width) {
+  return align_up((size_t)tiles_x_of(width, ST) * tiles_y_of(height, ST) * sizeof(float));
+}
+
+size_t gr_ssim_ws_bytes(int height, int width, int channels, int want_grad) {
+  if (!ssim_shape_ok(height, width, channels)) return 0;
+  return ssim_partial_bytes(height, width) + (want_grad ? (size_t)3 * height * width * channels * sizeof(float) : 0);
+}
+
+gr_status gr_ssim_fwd(const float* x, const float* y, int height, int width, int channels, int want_grad, float* dssim,
+                      void* ws, size_t ws_bytes, void* stream) {
+  if (!ssim_shape_ok(height, width, channels))
+    return set_error(GR_ERR_INVALID_ARGUMENT, "gr_ssim_fwd: height, width must be positive (at most 2^30 values), channels in 1..4");
+  if (!x || !y || !dssim || !ws) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_ssim_fwd: null pointer");
+  if (ws_bytes < gr_ssim_ws_bytes(height, width, channels, want_grad))
+    return set_error(GR_ERR_WORKSPACE, "gr_ssim_fwd: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid(tiles_x_of(width, ST), tiles_y_of(height, ST));
+  float* partial = (float*)ws;
+  float* maps = (float*)((char*)ws + ssim_partial_bytes(height, width));
+#define GR_SSIM_FWD(C_)                                                                                              \
+  if (want_grad)                                                                                                     \
+    hipLaunchKernelGGL((k_ssim_fwd<C_, true>), grid, dim3(256), 0, s, x, y, height, width, partial, maps);           \
+  else                                                                                                               \
+    hipLaunchKernelGGL((k_ssim_fwd<C_, false>), grid, dim3(256), 0, s, x, y, height, width, partial, (float*)nullptr)
+  switch (channels) {
+    case 1: GR_SSIM_FWD(1); break;
+    case 2: GR_SSIM_FWD(2); break;
+    case 3: GR_SSIM_FWD(3); break;
+    default: GR_SSIM_FWD(4); break;
+  }
+#undef GR_SSIM_FWD
+  GR_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_ssim_final, dim3(1), dim3(256), 0, s, (const float*)partial, (int)(grid.x * grid.y),
+                     (int64_t)height * width * channels, dssim);
+  GR_HIP_TRY(hipGetLastError());
+  return GR_OK;
+}
+
+gr_status gr_ssim_bwd(const float* x, const float* y, int height, int width, int channels, const float* g_loss,
+                      const void* ws, size_t ws_bytes, float* g_x, void* stream) {
+  if (!ssim_shape_ok(height, width, channels))
+    return set_error(GR_ERR_INVALID_ARGUMENT, "gr_ssim_bwd: height, width must be positive (at most 2^30 values), channels in 1..4");
+  if (!x || !y || !g_loss || !ws || !g_x) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_ssim_bwd: null pointer");
+  if (ws_bytes < gr_ssim_ws_bytes(height, width, channels, 1))
+    return set_error(GR_ERR_WORKSPACE, "gr_ssim_bwd: workspace too small (the forward must have run with want_grad)");
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid(tiles_x_of(width, ST), tiles_y_of(height, ST));
+  const float* maps = (const float*)((const char*)ws + ssim_partial_bytes(height, width));
+  switch (channels) {
+    case 1: hipLaunchKernelGGL(k_ssim_bwd<1>, grid, dim3(256), 0, s, x, y, height, width, maps, g_loss, g_x); break;
+    case 2: hipLaunchKernelGGL(k_ssim_bwd<2>, grid, dim3(256), 0, s, x, y, height, width, maps, g_loss, g_x); break;
+    case 3: hipLaunchKernelGGL(k_ssim_bwd<3>, grid, dim3(256), 0, s, x, y, height, width, maps, g_loss, g_x); break;
+    default: hipLaunchKernelGGL(k_ssim_bwd<4>, grid, dim3(256), 0, s, x, y, height, width, maps, g_loss, g_x); break;
+  }
   GR_HIP_TRY(hipGetLastError());
   return GR_OK;
 }

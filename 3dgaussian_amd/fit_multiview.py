@@ -389,7 +389,9 @@ class ViewShardedFitter:
     def __init__(self, params: dict, cams: list, targets: list, width: int, height: int, lr: float = 0.02,
                  masks: Optional[list] = None, depths: Optional[list] = None, silhouette_weight: float = 0.2,
                  depth_weight: float = 0.05, reg_opacity: float = 1e-3, reg_scale: float = 1e-3,
-                 render_fn: RenderFn = hip_render, group=None, reorder: bool = True):
+                 render_fn: RenderFn = hip_render, group=None, reorder: bool = True, dssim_weight: float = 0.0):
+        # dssim_weight l > 0: a view's photometric term is (1 - l) mean|pred - tgt| + l dssim(pred, tgt)
+        # (losses.dssim_loss) on the per-view autograd path; 0 (default): the L1 fit, every path as it was
         # reorder: keep the Gaussians in spatial (Morton) order, re-established after every
         # densify/prune (spatial_order); off only to compare with an unpermuted run
         # perm: self.params[k][i] = canonical[k][perm[i]], the canonical order being the stub's (the
@@ -415,6 +417,9 @@ class ViewShardedFitter:
         self.cams, self.targets, self.masks, self.depths = cams, targets, masks, depths
         self.width, self.height, self.lr = width, height, lr
         self.w_sil, self.w_depth = silhouette_weight, depth_weight
+        if not 0.0 <= dssim_weight <= 1.0:
+            raise ValueError(f"dssim_weight must be in [0, 1], got {dssim_weight}")
+        self.w_dssim = float(dssim_weight)
         self.reg_opacity, self.reg_scale = reg_opacity, reg_scale
         self.render_fn = render_fn
         self.group = group
@@ -667,7 +672,18 @@ class ViewShardedFitter:
         pred, alpha, depth = self.render_fn(means, scales, colors, opacities, self.cams[i], self.width, self.height,
                                             self._background(device), **kw)
         use_sil = self.masks is not None and self.w_sil > 0.0
-        if self.render_fn is hip_render and pred.device.type == "cuda" and FUSED_LOSS:
+        if self.w_dssim > 0.0:
+            # (1 - l) L1 + l D-SSIM for the photometric term; the silhouette term as below
+            lam = self.w_dssim
+            if self.render_fn is hip_render and pred.device.type == "cuda" and FUSED_LOSS:
+                loss = (1.0 - lam) * losses.l1_loss(pred, self.targets[i]) + lam * losses.dssim_loss(pred, self.targets[i])
+                if use_sil:
+                    loss = loss + self.w_sil * losses.l1_loss(alpha, self.masks[i])
+            else:
+                loss = (1.0 - lam) * torch.mean(torch.abs(pred - self.targets[i])) + lam * losses.dssim_loss(pred, self.targets[i])
+                if use_sil:
+                    loss = loss + self.w_sil * torch.mean(torch.abs(alpha - self.masks[i]))
+        elif self.render_fn is hip_render and pred.device.type == "cuda" and FUSED_LOSS:
             # photometric + silhouette L1 fused on the device (losses.l1_loss); same value and gradient
             loss = losses.l1_loss(pred, self.targets[i], alpha if use_sil else None,
                                   self.masks[i] if use_sil else None, self.w_sil if use_sil else 0.0)
@@ -683,7 +699,10 @@ class ViewShardedFitter:
     def _direct(self, device) -> bool:
         """The fused path (_views_direct, or _views_direct_depth with a depth term): HIP render op, the
         view loss and its gradients in the C ABI, no autograd per view.  Needs float32 parameters and
-        targets / masks / depths of exactly the image's shape (checked at construction)."""
+        targets / masks / depths of exactly the image's shape (checked at construction).  A D-SSIM term
+        (dssim_weight > 0) is not fused into the splat epilogues: such a fit takes the per-view autograd path."""
+        if self.w_dssim > 0.0:
+            return False
         return (self.render_fn is hip_render and device.type == "cuda" and FUSED_LOSS and DIRECT_BACKWARD
                 and self._images_ok and all(p.dtype == torch.float32 for p in self.params.values()))
 
@@ -1662,6 +1681,8 @@ def main(argv=None) -> None:
     ap.add_argument("--silhouette_weight", type=float, default=0.2)
     ap.add_argument("--mask_thresh", type=float, default=0.06)
     ap.add_argument("--depth_weight", type=float, default=0.05)
+    ap.add_argument("--dssim_weight", type=float, default=0.0,
+                    help="l in (1 - l) L1 + l (1 - SSIM) for the photometric term (0: the reference's L1 fit)")
     ap.add_argument("--reg_opacity", type=float, default=0.001)
     ap.add_argument("--reg_scale", type=float, default=0.001)
     ap.add_argument("--seed", type=int, default=None, help="torch.manual_seed before initialisation")
@@ -1714,7 +1735,7 @@ def main(argv=None) -> None:
     params = build_params(args.num_gaussians, device, args.use_sh, args.sh_degree)
     fitter = ViewShardedFitter(params, cams, targets, args.width, args.height, lr=args.lr, masks=masks, depths=depths,
                                silhouette_weight=args.silhouette_weight, depth_weight=args.depth_weight,
-                               reg_opacity=args.reg_opacity, reg_scale=args.reg_scale)
+                               reg_opacity=args.reg_opacity, reg_scale=args.reg_scale, dssim_weight=args.dssim_weight)
     loss_log = []
     pending = []  # the step tensors not yet read: a replayed step found to have overflowed is redone and its loss
     #               rewritten in place one step later (graph_sync), so the host reads them after that
@@ -1752,6 +1773,9 @@ def save_outputs(fitter: ViewShardedFitter, cams, args, out_dir: Path, loss_log)
     arrays = dict(means=means, scales=scales, colors=colors, opacities=opacities)
     if sh is not None:
         arrays["sh_coeffs"] = sh
+    if getattr(args, "dssim_weight", 0.0) > 0.0:
+        # the loss the Gaussians were fitted with (absent: the reference's L1 fit, whose file is unchanged)
+        arrays["dssim_weight"] = torch.tensor(float(args.dssim_weight))
     np.savez(out_dir / "gaussians_fitted.npz", **{k: v.detach().cpu().numpy().astype(np.float32) for k, v in arrays.items()})
     (out_dir / "loss.txt").write_text("\n".join(f"{v:.8f}" for v in loss_log), encoding="utf-8")
     with torch.no_grad():

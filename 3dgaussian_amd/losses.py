@@ -5,6 +5,14 @@ plus the weighted silhouette L1 of python/fit_multiview_stub.py:292-299, as one 
 (k_l1_partial + k_l1_final) and one backward kernel (k_l1_grad) in libgr_hip.so instead of torch's
 chain of sub / abs / mean / mul / add launches and their backward.  Same value and gradient as the
 torch expression up to float32 summation order (tests/test_losses_gpu.py); deterministic.
+
+``dssim_loss(pred, target)`` = ``1 - mean SSIM`` of two channel-last ``(H, W, C)`` images (11x11 Gaussian
+window, sigma 1.5, zero padding, C1 = 1e-4, C2 = 9e-4; include/gr_hip.h), the structural term of
+``(1 - l) * L1 + l * (1 - SSIM)``: one tiled forward kernel (k_ssim_fwd, separable windowed sums in LDS)
+plus the final sum, and one backward kernel (k_ssim_bwd) over three maps the forward keeps, instead of
+about ten conv2d and fifteen elementwise launches with their autograd graph.  ``ssim(a, b)`` is the
+mean SSIM as a metric (no gradient, no maps).  On CPU tensors both evaluate the same definition with
+torch ops, so that a ``--device cpu`` fit works (tests/test_ssim_gpu.py, tests/test_ssim_cpu.py).
 """
 from __future__ import annotations
 
@@ -63,4 +71,85 @@ def l1_loss(a: torch.Tensor, b: torch.Tensor, c: Optional[torch.Tensor] = None, 
     return _L1Loss.apply(f(a), f(b).detach(), f(c), None if d is None else f(d).detach(), float(w2))
 
 
-__all__ = ["l1_loss"]
+SSIM_WINDOW, SSIM_SIGMA, SSIM_C1, SSIM_C2 = 11, 1.5, 1e-4, 9e-4
+
+
+def _ssim_mean_torch(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """mean SSIM of two (H, W, C) images with torch ops (the CPU path): the definition of include/gr_hip.h."""
+    C = x.shape[2]
+    r = SSIM_WINDOW // 2
+    g = torch.exp(-(torch.arange(SSIM_WINDOW, dtype=torch.float64) - r) ** 2 / (2.0 * SSIM_SIGMA ** 2))
+    g = g / g.sum()
+    w = torch.outer(g, g).to(dtype=x.dtype, device=x.device).expand(C, 1, SSIM_WINDOW, SSIM_WINDOW).contiguous()
+
+    def conv(t):
+        return torch.nn.functional.conv2d(t, w, padding=r, groups=C)
+
+    X, Y = x.permute(2, 0, 1).unsqueeze(0), y.permute(2, 0, 1).unsqueeze(0)
+    mx, my = conv(X), conv(Y)
+    sx, sy, sxy = conv(X * X) - mx * mx, conv(Y * Y) - my * my, conv(X * Y) - mx * my
+    m = ((2.0 * mx * my + SSIM_C1) * (2.0 * sxy + SSIM_C2)) / ((mx * mx + my * my + SSIM_C1) * (sx + sy + SSIM_C2))
+    return m.mean()
+
+
+class _DSSIMLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y):
+        L = _native.lib()
+        H, W, C = x.shape
+        want = 1 if ctx.needs_input_grad[0] else 0
+        loss = torch.empty((), dtype=torch.float32, device=x.device)
+        ws = torch.empty((int(L.gr_ssim_ws_bytes(H, W, C, want)),), dtype=torch.uint8, device=x.device)
+        _native.check(L.gr_ssim_fwd(_native.ptr(x), _native.ptr(y), H, W, C, want, _native.ptr(loss), _native.ptr(ws),
+                                    ws.numel(), _stream(x)), "gr_ssim_fwd")
+        if want:
+            ctx.save_for_backward(x, y, ws)  # ws: the three maps of the backward
+            ctx.stream = torch.cuda.current_stream(x.device)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        x, y, ws = ctx.saved_tensors
+        L = _native.lib()
+        H, W, C = x.shape
+        cur = torch.cuda.current_stream(x.device)
+        if cur != ctx.stream:
+            # a backward driven from another stream than the forward's: ordered after it, and the forward
+            # stream's allocator must not reuse the tensors while this stream reads them
+            cur.wait_stream(ctx.stream)
+            for t in (x, y, ws):
+                t.record_stream(cur)
+        g = g.contiguous().float()
+        gx = torch.empty_like(x)
+        _native.check(L.gr_ssim_bwd(_native.ptr(x), _native.ptr(y), H, W, C, _native.ptr(g), _native.ptr(ws), ws.numel(),
+                                    _native.ptr(gx), _stream(x)), "gr_ssim_bwd")
+        return gx, None
+
+
+def _ssim_args(name: str, a: torch.Tensor, b: torch.Tensor):
+    if a.shape != b.shape:
+        raise ValueError(f"{name}: shape mismatch {tuple(a.shape)} vs {tuple(b.shape)}")
+    if a.dim() != 3 or not 1 <= a.shape[2] <= 4 or a.numel() == 0:
+        raise ValueError(f"{name}: images are (H, W, C) with 1 <= C <= 4, got {tuple(a.shape)}")
+    return a.contiguous().float(), b.detach().contiguous().float()
+
+
+def dssim_loss(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    """1 - mean SSIM(pred, target) of two (H, W, C) images, C <= 4; the gradient flows to pred only.
+    HIP kernels on the device; the same definition with torch ops on CPU tensors."""
+    x, y = _ssim_args("dssim_loss", pred, target)
+    if x.device.type != "cuda":
+        return 1.0 - _ssim_mean_torch(x, y)
+    return _DSSIMLoss.apply(x, y)
+
+
+def ssim(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """The mean SSIM of two (H, W, C) images as a metric: no gradient, no backward maps written."""
+    with torch.no_grad():
+        x, y = _ssim_args("ssim", a.detach(), b)
+        if x.device.type != "cuda":
+            return _ssim_mean_torch(x, y)
+        return 1.0 - _DSSIMLoss.apply(x, y)
+
+
+__all__ = ["l1_loss", "dssim_loss", "ssim"]

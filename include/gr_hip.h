@@ -411,6 +411,28 @@ gr_status gr_l1_loss_bwd(const float* a, const float* b, int64_t n1, const float
                          void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* D-SSIM loss, the structural term of (1 - l) L1 + l (1 - SSIM) that Gaussian-splatting       */
+/* trainers minimise (an extension: the reference fit loop has L1 terms only).                 */
+/*   x, y: (height, width, channels) float32 device images, contiguous, 1 <= channels <= 4     */
+/*   per channel, g the 11-tap Gaussian (sigma 1.5, sum 1), window g x g, zero padding of 5:    */
+/*   mx = conv(x), my = conv(y), sx = conv(x^2) - mx^2, sy = conv(y^2) - my^2,                  */
+/*   sxy = conv(xy) - mx my, m = (2 mx my + C1)(2 sxy + C2) / ((mx^2 + my^2 + C1)(sx + sy + C2)) */
+/*   with C1 = 1e-4, C2 = 9e-4;  *dssim = 1 - mean(m) over all height*width*channels values.   */
+/* gr_ssim_fwd: one launch for the map (one workgroup per GR_SSIM_TILE^2 pixels, separable sums */
+/* in LDS) and one for the final sum.  want_grad != 0: the same launch keeps three per-value    */
+/* maps in ws for gr_ssim_bwd (ws of gr_ssim_ws_bytes(.., 1)); 0: none are written.            */
+/* gr_ssim_bwd: g_x = (*g_loss) d dssim / d x, one launch; no gradient to y.  ws is the         */
+/* forward's, untouched since.  Stream-ordered, deterministic, no allocation.                  */
+/* At most 2^30 values and 16 * 65535 rows.                                                    */
+/* ------------------------------------------------------------------------------------------ */
+#define GR_SSIM_TILE 16 /* tile edge in pixels of the D-SSIM kernels */
+size_t gr_ssim_ws_bytes(int height, int width, int channels, int want_grad);
+gr_status gr_ssim_fwd(const float* x, const float* y, int height, int width, int channels, int want_grad,
+                      float* dssim, void* ws, size_t ws_bytes, void* stream);
+gr_status gr_ssim_bwd(const float* x, const float* y, int height, int width, int channels,
+                      const float* g_loss, const void* ws, size_t ws_bytes, float* g_x, void* stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Fit-loop parameter update, the caller's side of the render op (fit_multiview_stub.py:268-275   */
 /* activations, :307-308 regulariser, :311 torch.optim.Adam), one pass per parameter tensor:    */
 /*   grad = act'(param) * (((accs[0] + accs[1]) + ...) + reg)  (up to GR_FIT_MAX_ACC device arrays  */
