@@ -197,6 +197,16 @@ _SIG = {
     "gr_gather_view": (ctypes.c_int, [_VP, ctypes.c_int, _PP, _P, _P, _P, _P, _P]),
     "gr_bwd_fit_gather": (ctypes.c_int, [_VP, ctypes.c_int, _PP, _P, _P, _P, _P, _P, ctypes.c_float, _P, ctypes.c_float,
                                          ctypes.c_float, _P, _P, ctypes.c_size_t, _P, _P, _P]),
+    "gr_bwd_ssim_bytes": (ctypes.c_size_t, [_VP, ctypes.c_int, _PP]),
+    "gr_bwd_fit_ssim": (ctypes.c_int, [_VP, ctypes.c_int, _PP, _P, _P, _P, ctypes.c_int, _P, _P, _P, _P, _P, _P,
+                                       ctypes.c_float, _P, ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, _P, _P, _P,
+                                       _P, ctypes.c_int, _P, ctypes.c_size_t, _P]),
+    "gr_bwd_fit_ssim_gather": (ctypes.c_int, [_VP, ctypes.c_int, _PP, _P, _P, _P, _P, _P, ctypes.c_float, _P,
+                                              ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, _P, ctypes.c_size_t, _P,
+                                              _P, _P]),
+    "gr_fit_views_ssim": (ctypes.c_int, [_P, ctypes.POINTER(GrFitConfig), ctypes.c_int, ctypes.POINTER(GrFitTarget),
+                                         ctypes.c_int, _P, _P, _P, ctypes.c_int, _P, ctypes.c_float, ctypes.c_float,
+                                         ctypes.c_float, ctypes.c_float, _P, ctypes.POINTER(ctypes.c_void_p), _P]),
     "gr_reduce_sums": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(GrSumsView), ctypes.c_int, _P, _P, _P, ctypes.c_int,
                                       _P, _P, _P, _P, _P, ctypes.c_int, _P]),
     "gr_executor_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),

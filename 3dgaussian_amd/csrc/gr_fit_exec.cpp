@@ -7,8 +7,8 @@
 // (the small-view configs and the per-rank share of a multi-GPU step are host-bound in Python).
 //
 // Only the public C ABI (gr_fwd_prepare_views_async, gr_fwd_render_l1, gr_bwd_splat, gr_gather_view,
-// gr_reduce_sums, gr_fwd_render, gr_bwd_fit) and the HIP runtime are used.  Workspaces are the executor's
-// own, kept across steps and reused only in stream order: each render stream owns its view workspace
+// gr_reduce_sums, gr_fwd_render, gr_bwd_fit_gather, gr_bwd_fit_ssim_gather) and the HIP runtime are used.
+// Workspaces are the executor's own, kept across steps and reused only in stream order: each render stream owns its view workspace
 // (bins, forward scratch, backward workspace, saved sums) and a ring of per-view sums for its reduction
 // batch; the geoms are a ring of slots written on the preparation stream, a slot being rewritten only
 // after the preparation stream has waited for the event recorded behind its last reader.  A buffer that
@@ -116,11 +116,11 @@ struct gr_executor {
 
 static gr_status fit_views_on_device(gr_executor* ex, const gr_fit_config* cfg, int num_views, const gr_fit_target* views,
                                      int n, const float* means, const float* scales, const float* colors, int color_dim,
-                                     const float* opacities, float w_sil, float w_depth, float g_scale, float* losses,
-                                     float* const* acc, void* stream);
+                                     const float* opacities, float w_sil, float w_depth, float g_scale, float w_dssim,
+                                     float* losses, float* const* acc, void* stream);
 static gr_status enqueue_views(gr_executor* ex, const gr_fit_config* cfg, int num_views, const gr_fit_target* views, int n,
                                const float* means, const float* scales, const float* colors, int color_dim,
-                               const float* opacities, float w_sil, float w_depth, float g_scale, float* losses,
+                               const float* opacities, float w_sil, float w_depth, float g_scale, float w_dssim, float* losses,
                                float* const* acc, const Sched& sc, const std::vector<hipStream_t>& st, hipStream_t prep,
                                bool depth, int nslots, int& ngroups);
 
@@ -174,10 +174,10 @@ void gr_executor_destroy(gr_executor* ex) {
   delete ex;
 }
 
-gr_status gr_fit_views(gr_executor* ex, const gr_fit_config* cfg, int num_views, const gr_fit_target* views, int n,
-                       const float* means, const float* scales, const float* colors, int color_dim,
-                       const float* opacities, float w_sil, float w_depth, float g_scale, float* losses,
-                       float* const* acc, void* stream) {
+static gr_status fit_views_checked(gr_executor* ex, const gr_fit_config* cfg, int num_views, const gr_fit_target* views,
+                                   int n, const float* means, const float* scales, const float* colors, int color_dim,
+                                   const float* opacities, float w_sil, float w_depth, float g_scale, float w_dssim,
+                                   float* losses, float* const* acc, void* stream) {
   if (!ex || !cfg || (num_views > 0 && (!views || !losses || !acc)))
     return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, "gr_fit_views: null argument");
   // every batch of a stream (its last one holds reduce_tail views) and every preparation group must fit the
@@ -199,17 +199,35 @@ gr_status gr_fit_views(gr_executor* ex, const gr_fit_config* cfg, int num_views,
   GR_EXEC_TRY(hipGetDevice(&prev_dev));
   GR_EXEC_TRY(hipSetDevice(ex->device));
   const gr_status st = fit_views_on_device(ex, cfg, num_views, views, n, means, scales, colors, color_dim, opacities, w_sil,
-                                           w_depth, g_scale, losses, acc, stream);
+                                           w_depth, g_scale, w_dssim, losses, acc, stream);
   (void)hipSetDevice(prev_dev);
   return st;
+}
+
+gr_status gr_fit_views(gr_executor* ex, const gr_fit_config* cfg, int num_views, const gr_fit_target* views, int n,
+                       const float* means, const float* scales, const float* colors, int color_dim,
+                       const float* opacities, float w_sil, float w_depth, float g_scale, float* losses,
+                       float* const* acc, void* stream) {
+  return fit_views_checked(ex, cfg, num_views, views, n, means, scales, colors, color_dim, opacities, w_sil, w_depth,
+                           g_scale, 0.0f, losses, acc, stream);
+}
+
+gr_status gr_fit_views_ssim(gr_executor* ex, const gr_fit_config* cfg, int num_views, const gr_fit_target* views, int n,
+                            const float* means, const float* scales, const float* colors, int color_dim,
+                            const float* opacities, float w_sil, float w_depth, float g_scale, float w_dssim,
+                            float* losses, float* const* acc, void* stream) {
+  if (!(w_dssim >= 0.0f && w_dssim <= 1.0f))
+    return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, "gr_fit_views_ssim: w_dssim must be in [0, 1]");
+  return fit_views_checked(ex, cfg, num_views, views, n, means, scales, colors, color_dim, opacities, w_sil, w_depth,
+                           g_scale, w_dssim, losses, acc, stream);
 }
 
 }  // extern "C"
 
 static gr_status fit_views_on_device(gr_executor* ex, const gr_fit_config* cfg, int num_views, const gr_fit_target* views,
                                      int n, const float* means, const float* scales, const float* colors, int color_dim,
-                                     const float* opacities, float w_sil, float w_depth, float g_scale, float* losses,
-                                     float* const* acc, void* stream) {
+                                     const float* opacities, float w_sil, float w_depth, float g_scale, float w_dssim,
+                                     float* losses, float* const* acc, void* stream) {
   const bool depth = views[0].target_depth != nullptr;
   const Sched sc = schedule(num_views, *cfg);
   const int ns = sc.ns;
@@ -284,14 +302,14 @@ static gr_status fit_views_on_device(gr_executor* ex, const gr_fit_config* cfg, 
       (void)hipStreamSynchronize(prep);
   };
   const gr_status status = enqueue_views(ex, cfg, num_views, views, n, means, scales, colors, color_dim, opacities, w_sil,
-                                         w_depth, g_scale, losses, acc, sc, st, prep, depth, nslots, ngroups);
+                                         w_depth, g_scale, w_dssim, losses, acc, sc, st, prep, depth, nslots, ngroups);
   join();
   return status;
 }
 
 static gr_status enqueue_views(gr_executor* ex, const gr_fit_config* cfg, int num_views, const gr_fit_target* views, int n,
                                const float* means, const float* scales, const float* colors, int color_dim,
-                               const float* opacities, float w_sil, float w_depth, float g_scale, float* losses,
+                               const float* opacities, float w_sil, float w_depth, float g_scale, float w_dssim, float* losses,
                                float* const* acc, const Sched& sc, const std::vector<hipStream_t>& st, hipStream_t prep,
                                bool depth, int nslots, int& ngroups) {
   const int ns = sc.ns;
@@ -377,13 +395,28 @@ static gr_status enqueue_views(gr_executor* ex, const gr_fit_config* cfg, int nu
     if (plan.num_pairs < 0 || plan.num_slots < 0) return gr_exec_set_error(GR_ERR_OVERFLOW, "pair count overflows int32");
     const gr_view& v = views[j].view;
     const size_t bins_bytes = gr_bins_bytes(&v, n, &plan), scratch_bytes = gr_fwd_scratch_bytes(&v, n, &plan);
-    const size_t ws_bytes = gr_bwd_bytes(&v, n, &plan);
+    const bool ssim = w_dssim > 0.0f;  // the D-SSIM form (gr_fit_views_ssim)
+    const size_t ws_bytes = ssim ? gr_bwd_ssim_bytes(&v, n, &plan) : gr_bwd_bytes(&v, n, &plan);
     StreamWs& W = ex->ws[k];
     GR_EXEC_TRY(W.bins.fit(bins_bytes, s));
     GR_EXEC_TRY(W.scratch.fit(scratch_bytes, s));
     GR_EXEC_TRY(W.ws.fit(ws_bytes, s));
     void *bins = W.bins.p, *scratch = W.scratch.p, *ws = W.ws.p;
-    if (!depth) {
+    if (ssim) {
+      // the saved sums only (no image: the D-SSIM forward stages the colours from them); sums3 with a depth target
+      GR_EXEC_TRY(W.saved.fit(gr_saved_floats(&v) * sizeof(float), s));
+      GR_EXEC_CALL(gr_fwd_render(&v, n, &plan, geom[j], bins, W.bins.cap, scratch, W.scratch.cap, nullptr, nullptr,
+                                 nullptr, (float*)W.saved.p, s));
+      Buf& sb = W.sums[pending[k].size()];
+      Buf& s3 = W.sums3[pending[k].size()];
+      GR_EXEC_TRY(sb.fit(sums_bytes, s));
+      if (depth) GR_EXEC_TRY(s3.fit((size_t)n * sizeof(float), s));
+      float* p3 = depth ? (float*)s3.p : nullptr;
+      GR_EXEC_CALL(gr_bwd_fit_ssim_gather(&v, n, &plan, geom[j], bins, (const float*)W.saved.p, views[j].target_rgb,
+                                          views[j].target_mask, w_sil, views[j].target_depth, w_depth, g_scale, w_dssim,
+                                          losses + j, ws, W.ws.cap, (float*)sb.p, p3, s));
+      pending[k].push_back({v, (float*)sb.p, p3});
+    } else if (!depth) {
       GR_EXEC_CALL(gr_fwd_render_l1(&v, n, &plan, geom[j], bins, W.bins.cap, scratch, W.scratch.cap, views[j].target_rgb,
                                     views[j].target_mask, w_sil, g_scale, losses + j, nullptr, nullptr, ws, W.ws.cap, s));
       GR_EXEC_CALL(gr_bwd_splat(&v, n, &plan, geom[j], bins, ws, W.ws.cap, s));

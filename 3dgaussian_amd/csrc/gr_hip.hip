@@ -18,6 +18,8 @@
 //                    a tile split over several items is finished by its last item (arrival ticket);
 //                    out/alpha/depth + saved, with the fit loss its upstream fragments and the view loss.
 //   k_pixel_grads    per pixel upstream vector U = (dC, dW, dD), pre-split into MFMA fragments.
+//   k_ssim_pixel_grads  k_pixel_grads of a fit with a D-SSIM term: the D-SSIM backward's convolutions in the same
+//                    tile, its gradient added to the L1 term's per pixel (gr_bwd_fit_ssim; no gradient image).
 //   k_raster_bwd_bf16   per work item: the two K = 16 contractions (over x, over y) of U with the
 //                    Gaussians' exponentials; 8- or 9-float partial rows at the pairs' sorted positions.
 //   k_reduce_bwd     per Gaussian: its rows (through pos_of) summed in a fixed order (deterministic, no
@@ -2113,6 +2115,7 @@ struct L1Args {
   float w_depth = 0.0f;
   const float* dscal = nullptr;    // device scalars: [0] max(depth), [1] the max's gradient per arg-max pixel
   int pieces = 2;                  // bf16 pieces of the upstream fragments (gr_fwd_render_l1: 3 at f32 grade)
+  float w_dssim = 0.0f;            // D-SSIM weight l of the photometric term (1 - l) L1 + l D-SSIM (k_ssim_pixel_grads only)
   // gr_fwd_render_l1: the view loss, written by the forward's last finished tile (photometric / silhouette element
   // counts n1 / n2, tile_loss_total)
   float* loss_out = nullptr;
@@ -2156,9 +2159,13 @@ __device__ __forceinline__ void tile_loss_total(const float* __restrict__ tile_l
 __device__ __forceinline__ float sign0(float t) { return t > 0.0f ? 1.0f : (t < 0.0f ? -1.0f : 0.0f); }
 
 // U of pixel p from its sums s = (W, C_r, C_g, C_b) and D; l_rgb / l_sil get the pixel's L1 terms.
+// SSIM (k_ssim_pixel_grads): the photometric gradient is sign(out - t) (1 - l) g / (3 HW) + g_ssim[k], l = l1.w_dssim,
+// g_ssim the pixel's three D-SSIM gradients (already scaled by l g).
+template <bool SSIM = false>
 __device__ __forceinline__ void pixel_upstream(const ViewK& v, int p, float4 s, float Dp, const float* __restrict__ g_rgb,
                                                const float* __restrict__ g_alpha, const float* __restrict__ g_depth,
-                                               const L1Args& l1, float (&u)[5], float& l_rgb, float& l_sil) {
+                                               const L1Args& l1, float (&u)[5], float& l_rgb, float& l_sil,
+                                               const float* g_ssim = nullptr) {
   const float den = 1.0f + s.x, dden = s.x + 1e-6f;
   // one correctly rounded reciprocal of the finalize's denominator instead of ten divisions (each ~10 VALU): the
   // quotients below are products with it, within 1 ulp of the divisions (round 6, the L1 epilogue of the fit forwards)
@@ -2173,7 +2180,10 @@ __device__ __forceinline__ void pixel_upstream(const ViewK& v, int p, float4 s, 
     if (l1.t_rgb) {
       const float t = clamp01(r) - l1.t_rgb[3 * p + k];
       l_rgb += fabsf(t);
-      gk = sign0(t) * (l1.g_scale / (3.0f * HWf));
+      if constexpr (SSIM)
+        gk = sign0(t) * (((1.0f - l1.w_dssim) * l1.g_scale) / (3.0f * HWf)) + g_ssim[k];
+      else
+        gk = sign0(t) * (l1.g_scale / (3.0f * HWf));
     } else {
       gk = g_rgb[3 * p + k];
     }
@@ -4509,19 +4519,15 @@ __device__ __forceinline__ void ssim_stage(const float* __restrict__ src, int H,
 // GRAD: also writes, per value, the three maps the backward convolves (planes of H*W*C floats):
 //   maps[0] = dm/dmx with sx and sxy expressed through mx: 2 (my (A2 - A1) - mx m (B2 - B1)) / (B1 B2)
 //   maps[1] = dm/dsx = -m / B2            maps[2] = dm/dsxy = 2 A1 / (B1 B2)
+// The forward of one tile from its two staged windows tx, ty (published by a barrier): the separable sums, the tile's
+// sum of m into partial[tile] and (GRAD) the three maps.
 template <int C, bool GRAD>
-__global__ __launch_bounds__(256) void k_ssim_fwd(const float* __restrict__ x, const float* __restrict__ y, int H, int W,
-                                                  float* __restrict__ partial, float* __restrict__ maps) {
+__device__ __forceinline__ void ssim_fwd_tile(const float* tx, const float* ty, float (*hs)[SE * ST * C], float* red, int H,
+                                              int W, float* __restrict__ partial, float* __restrict__ maps) {
   constexpr int TC = ST * C, SP = SE * C;
-  __shared__ float tx[SE * SP], ty[SE * SP];
-  __shared__ float hs[5][SE * TC];
-  __shared__ float red[256];
   const int t = threadIdx.x;
   const int WC = W * C;
   const int y0 = blockIdx.y * ST, v0 = blockIdx.x * TC;
-  ssim_stage<C>(x, H, WC, y0, v0, tx);
-  ssim_stage<C>(y, H, WC, y0, v0, ty);
-  __syncthreads();
   for (int o = t; o < SE * TC; o += 256) {
     const int r = o / TC, c = o - r * TC;
     const float* px = tx + r * SP + c;
@@ -4580,6 +4586,55 @@ __global__ __launch_bounds__(256) void k_ssim_fwd(const float* __restrict__ x, c
     __syncthreads();
   }
   if (t == 0) partial[blockIdx.y * gridDim.x + blockIdx.x] = red[0];
+}
+
+template <int C, bool GRAD>
+__global__ __launch_bounds__(256) void k_ssim_fwd(const float* __restrict__ x, const float* __restrict__ y, int H, int W,
+                                                  float* __restrict__ partial, float* __restrict__ maps) {
+  constexpr int TC = ST * C, SP = SE * C;
+  __shared__ float tx[SE * SP], ty[SE * SP];
+  __shared__ float hs[5][SE * TC];
+  __shared__ float red[256];
+  const int y0 = blockIdx.y * ST, v0 = blockIdx.x * TC;
+  ssim_stage<C>(x, H, W * C, y0, v0, tx);
+  ssim_stage<C>(y, H, W * C, y0, v0, ty);
+  __syncthreads();
+  ssim_fwd_tile<C, GRAD>(tx, ty, hs, red, H, W, partial, maps);
+}
+
+// The rendered colour of a pixel from its saved sums s = (W, C_r, C_g, C_b), exactly as write_pixel wrote it.
+__device__ __forceinline__ float saved_colour(const ViewK& v, float4 s, int k) {
+  const float den = 1.0f + s.x;
+  return clamp01((view_bg(v, k) + (k == 0 ? s.y : (k == 1 ? s.z : s.w))) / den);
+}
+
+// k_ssim_fwd<3, true> of a view's render against its target, the rendered image x staged from the saved sums of
+// gr_fwd_render instead of an image (gr_bwd_fit_ssim: the fit path writes none); same grid (one block per render tile),
+// same partial sums and maps, bit for bit.
+__global__ __launch_bounds__(256) void k_ssim_fwd_saved(ViewK v, const float4* __restrict__ saved4,
+                                                        const float* __restrict__ y, float* __restrict__ partial,
+                                                        float* __restrict__ maps) {
+  constexpr int C = 3, TC = ST * C, SP = SE * C;
+  __shared__ float tx[SE * SP], ty[SE * SP];
+  __shared__ float hs[5][SE * TC];
+  __shared__ float red[256];
+  const int H = v.H, W = v.W;
+  const int y0 = blockIdx.y * ST, x0 = blockIdx.x * ST;
+  for (int e = threadIdx.x; e < SE * SE; e += 256) {
+    const int r = e / SE, c = e - r * SE;
+    const int gy = y0 - SR + r, gx = x0 - SR + c;
+    float px[3] = {0.0f, 0.0f, 0.0f};
+    if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
+      const float4 s = saved4[(int64_t)gy * W + gx];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) px[k] = saved_colour(v, s, k);
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) tx[r * SP + c * C + k] = px[k];
+  }
+  ssim_stage<C>(y, H, W * C, y0, blockIdx.x * TC, ty);
+  __syncthreads();
+  ssim_fwd_tile<C, true>(tx, ty, hs, red, H, W, partial, maps);
 }
 
 __global__ __launch_bounds__(256) void k_ssim_final(const float* __restrict__ partial, int blocks, int64_t n,
@@ -4645,6 +4700,141 @@ __global__ __launch_bounds__(256) void k_ssim_bwd(const float* __restrict__ x, c
     const int64_t off = (int64_t)gy * WC + gv;
     gx[off] = scale * fmaf(y[off], a2, fmaf(2.0f * x[off], a1, a0));
   }
+}
+
+// The view loss of a D-SSIM fit from the per-tile sums (tile_loss_total with the structural term):
+//   (1 - l) mean|out - t| + l (1 - mean m) + w_sil mean|alpha - m| (+ w_depth mean|d_pred - t_d| with n3 > 0),
+// the sum of m from the forward's per-tile partial sums (an earlier launch) in k_ssim_final's order, the tiles' L1 sums
+// written through in this launch.  One block of 256 threads; double sums in a fixed order.
+__device__ __forceinline__ void tile_loss_total_ssim(const float* __restrict__ tile_loss, const float* __restrict__ ssim_partial,
+                                                     int tiles, int64_t n1, int64_t n2, float w_sil, int64_t n3,
+                                                     float w_depth, float w_dssim, float* __restrict__ loss,
+                                                     double (*r)[256]) {
+  const int t = threadIdx.x;
+  double s1 = 0.0, s2 = 0.0, s3 = 0.0, s4 = 0.0;
+  for (int i = t; i < tiles; i += 256) {
+    s1 += (double)ld_through(tile_loss + 4 * i);
+    s2 += (double)ld_through(tile_loss + 4 * i + 1);
+    if (n3 > 0) s3 += (double)ld_through(tile_loss + 4 * i + 2);
+    s4 += (double)ssim_partial[i];
+  }
+  r[0][t] = s1;
+  r[1][t] = s2;
+  r[2][t] = s3;
+  r[3][t] = s4;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (t < w) {
+      r[0][t] += r[0][t + w];
+      r[1][t] += r[1][t + w];
+      r[2][t] += r[2][t + w];
+      r[3][t] += r[3][t + w];
+    }
+    __syncthreads();
+  }
+  if (t != 0) return;
+  float l = (1.0f - w_dssim) * (float)(r[0][0] / (double)n1);
+  l = l + w_dssim * (float)(1.0 - r[3][0] / (double)n1);
+  if (n2 > 0) l = l + w_sil * (float)(r[1][0] / (double)n2);
+  if (n3 > 0) l = l + w_depth * (float)(r[2][0] / (double)n3);
+  *loss = l;
+}
+
+// k_ssim_bwd<3> fused with k_pixel_grads for the fit loss with a D-SSIM term (gr_bwd_fit_ssim): one block per 16 x 16
+// render tile (GR_SSIM_TILE == GR_TILE) convolves the forward's three maps as k_ssim_bwd does, forms per value
+//   g_ssim = -(l g / (3 HW)) (conv(maps[0]) + 2 x conv(maps[1]) + y conv(maps[2])),  l = w_dssim, g = g_scale,
+// x the rendered colour recomputed from the saved sums (saved_colour), y the target, and hands it to pixel_upstream
+// with the L1 term's (1 - l) share: no gradient image is written or read.  Then the tile's fragments, loss sums and,
+// in the last tile to arrive, the view loss, as k_pixel_grads.
+// LDS (two arrays, 39,312 B; 39,348 B with the loss sums' words: four blocks per CU): tm[3][26 * 78] the staged maps (24,336 B) and hs[3][26 * 48] their
+// horizontal sums (14,976 B).  tm is dead after the horizontal pass; its space is then reused, in turn, as
+// sA[3][768] (the three convolved values of every value of the tile, row-major as the image: value o of thread o, o +
+// 256, o + 512, read back by pixel (py, px) at 48 py + 3 px + k: stride 3 across lanes, one address per bank), as
+// sU[6][256] (the upstream vectors for tile_fragments, written after tile_loss_sums' barrier has ended every read of
+// sA) and as the last tile's double[4][256].
+__global__ __launch_bounds__(256) void k_ssim_pixel_grads(ViewK v, const float4* __restrict__ saved4,
+                                                          const float* __restrict__ savedD, const float* __restrict__ maps,
+                                                          const float* __restrict__ ssim_partial, uint4* __restrict__ UF,
+                                                          int pieces, L1Args l1, bool depth, int* __restrict__ ticket) {
+  constexpr int C = 3, TC = ST * C, SP = SE * C;
+  static_assert(ST == T && ST * ST == TP, "an SSIM tile is a render tile");
+  __shared__ __attribute__((aligned(16))) float tm[3][SE * SP];
+  __shared__ float hs[3][SE * TC];
+  static_assert(sizeof(tm) >= 3 * ST * TC * sizeof(float) && sizeof(tm) >= 6 * TP * sizeof(float) &&
+                    sizeof(tm) >= 4 * 256 * sizeof(double),
+                "the overlays of tm");
+  const int tile = blockIdx.x, tid = threadIdx.x;
+  const int tx = tile % v.tiles_x, ty = tile / v.tiles_x;
+  const int x = tx * T + (tid & (T - 1)), y = ty * T + (tid >> 4);
+  const int H = v.H, WC = v.W * C;
+  const int64_t N = (int64_t)H * WC;
+  const int y0 = ty * ST, v0 = tx * TC;
+  // this pixel's sums and target: loaded ahead of the convolution
+  const bool inside = x < v.W && y < v.H;
+  const int p = inside ? y * v.W + x : 0;
+  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+  float Dp = 0.0f, tgt[3] = {0.f, 0.f, 0.f};
+  if (inside) {
+    s = saved4[p];
+    Dp = savedD[p];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) tgt[k] = l1.t_rgb[3 * p + k];
+  }
+  for (int q = 0; q < 3; ++q) ssim_stage<C>(maps + q * N, H, WC, y0, v0, tm[q]);
+  __syncthreads();
+  for (int o = tid; o < SE * TC; o += 256) {
+    const int r = o / TC, c = o - r * TC;
+    const int e = r * SP + c;
+    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f;
+#pragma unroll
+    for (int k = 0; k <= 2 * SR; ++k) {
+      const float g = SSIM_G[k];
+      a0 = fmaf(g, tm[0][e + k * C], a0);
+      a1 = fmaf(g, tm[1][e + k * C], a1);
+      a2 = fmaf(g, tm[2][e + k * C], a2);
+    }
+    hs[0][o] = a0;
+    hs[1][o] = a1;
+    hs[2][o] = a2;
+  }
+  __syncthreads();  // (tm is free from here)
+  float (*sA)[ST * TC] = reinterpret_cast<float (*)[ST * TC]>(&tm[0][0]);
+  for (int o = tid; o < ST * TC; o += 256) {
+    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f;
+#pragma unroll
+    for (int k = 0; k <= 2 * SR; ++k) {
+      const float g = SSIM_G[k];
+      a0 = fmaf(g, hs[0][o + k * TC], a0);
+      a1 = fmaf(g, hs[1][o + k * TC], a1);
+      a2 = fmaf(g, hs[2][o + k * TC], a2);
+    }
+    sA[0][o] = a0;
+    sA[1][o] = a1;
+    sA[2][o] = a2;
+  }
+  __syncthreads();
+  float u[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+  float l_rgb = 0.f, l_sil = 0.f;
+  if (inside) {
+    const float scale = -((l1.w_dssim * l1.g_scale) / (3.0f * ((float)v.W * (float)v.H)));
+    const int o = (tid >> 4) * TC + (tid & (T - 1)) * C;
+    float gs[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      gs[k] = scale * fmaf(tgt[k], sA[2][o + k], fmaf(2.0f * saved_colour(v, s, k), sA[1][o + k], sA[0][o + k]));
+    pixel_upstream<true>(v, p, s, Dp, nullptr, nullptr, nullptr, l1, u, l_rgb, l_sil, gs);
+  }
+  tile_loss_sums(tile, tid, l_rgb, l_sil, l1.tile_loss);  // (its barrier ends every read of sA)
+  float (*sU)[TP] = reinterpret_cast<float (*)[TP]>(&tm[0][0]);
+#pragma unroll
+  for (int k = 0; k < 5; ++k) sU[k][tid] = u[k];
+  __syncthreads();
+  tile_fragments(sU, UF + (size_t)tile * UF_FRAGS, tid, pieces, depth);
+  __shared__ int last;
+  const int tiles = v.tiles_x * v.tiles_y;
+  if (arrive_last_tile(ticket, tiles, tile, &last))  // (tile_loss_sums' stores are write-through)
+    tile_loss_total_ssim(l1.tile_loss, ssim_partial, tiles, l1.n1, l1.n2, l1.w_sil, l1.t_depth ? l1.n1 / 3 : 0, l1.w_depth,
+                         l1.w_dssim, l1.loss_out, reinterpret_cast<double (*)[256]>(&tm[0][0]));
 }
 
 // The fit loop's parameter update (fit_multiview_stub.py:268-275 activations, :307-308 regulariser,
@@ -5523,13 +5713,19 @@ gr_status gr_fwd_render_l1(const gr_view* v, int n, const gr_plan* plan, const v
 
 }  // extern "C" (bwd_impl is internal)
 
+static bool ssim_shape_ok(int height, int width, int channels);
+static size_t ssim_partial_bytes(int height, int width);
+
 static gr_status bwd_impl(const gr_view* v, int n, const gr_plan* plan, const float* means, const float* scales,
                           const float* colors, int color_dim, const float* opacities, const void* geom, const void* bins,
                           const float* saved, const float* g_rgb, const float* g_alpha, const float* g_depth,
                           const float* t_rgb, const float* t_mask, float w_sil, float g_scale, float* loss_out,
                           float* d_means, float* d_scales, float* d_colors, float* d_opacities, int accumulate, void* ws,
                           size_t ws_bytes, void* stream, const float* t_depth = nullptr, float w_depth = 0.0f,
-                          const int* sum_index = nullptr, float* g_sums = nullptr, float* g_sums3 = nullptr) {
+                          const int* sum_index = nullptr, float* g_sums = nullptr, float* g_sums3 = nullptr,
+                          float w_dssim = -1.0f) {
+  // w_dssim >= 0: the gr_bwd_fit_ssim entries (the workspace of gr_bwd_ssim_bytes); > 0: the photometric term is
+  // (1 - l) L1 + l D-SSIM, its forward from the saved sums (k_ssim_fwd_saved) and k_ssim_pixel_grads in k_pixel_grads' place
   gr_status st = check_view(v);
   if (st != GR_OK) return st;
   if ((g_depth || (t_rgb && t_depth)) && v->no_depth_grad)
@@ -5549,7 +5745,11 @@ static gr_status bwd_impl(const gr_view* v, int n, const gr_plan* plan, const fl
     return set_error(GR_ERR_INVALID_ARGUMENT, "null pointer");
   if (t_rgb && (!loss_out || !ws)) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_bwd_l1: null loss or workspace");
   const int64_t num_pairs = plan->num_pairs;
-  if ((num_pairs > 0 || t_rgb) && (!ws || ws_bytes < gr_bwd_bytes(v, n, plan)))
+  const bool ssim = w_dssim > 0.0f;
+  if (ssim && !ssim_shape_ok(v->height, v->width, 3))
+    return set_error(GR_ERR_INVALID_ARGUMENT, "gr_bwd_fit_ssim: the view exceeds the D-SSIM kernels' 2^30 values");
+  const size_t ws_need = w_dssim >= 0.0f ? gr_bwd_ssim_bytes(v, n, plan) : gr_bwd_bytes(v, n, plan);
+  if ((num_pairs > 0 || t_rgb) && (!ws || ws_bytes < ws_need))
     return set_error(GR_ERR_WORKSPACE, "backward workspace too small");
   hipStream_t s = (hipStream_t)stream;
   const ViewK vk = make_viewk(v);
@@ -5587,7 +5787,17 @@ static gr_status bwd_impl(const gr_view* v, int n, const gr_plan* plan, const fl
   // (z - depth) / (W + 1e-6) is what needs f32-grade W and D): the splat runs on two round-to-nearest
   // pieces (~2^-16 per product, unbiased) whatever the view's mode, except at f32 grade (no_depth_grad = 2).
   const int pieces = (v->no_depth_grad == 2 || depth) ? 3 : 2;
-  if (num_pairs > 0 || t_rgb) {
+  if (ssim) {
+    // the D-SSIM forward's workspace (gr_ssim_ws_bytes: per-tile partial sums, then the three maps) follows gr_bwd_bytes
+    float* partial = (float*)((char*)ws + gr_bwd_bytes(v, n, plan));
+    float* maps = (float*)((char*)partial + ssim_partial_bytes(v->height, v->width));
+    l1.w_dssim = w_dssim;
+    hipLaunchKernelGGL(k_ssim_fwd_saved, dim3(vk.tiles_x, vk.tiles_y), dim3(256), 0, s, vk, (const float4*)saved, t_rgb,
+                       partial, maps);
+    hipLaunchKernelGGL(k_ssim_pixel_grads, dim3(tiles), dim3(256), 0, s, vk, (const float4*)saved, saved + 4 * HW,
+                       (const float*)maps, (const float*)partial, UF, pieces, l1, depth, ticket);
+    GR_HIP_TRY(hipGetLastError());
+  } else if (num_pairs > 0 || t_rgb) {
     hipLaunchKernelGGL(k_pixel_grads, dim3(tiles), dim3(256), 0, s, vk, (const float4*)saved, saved + 4 * HW, g_rgb,
                        g_alpha, g_depth, UF, pieces, l1, depth, ticket);
     GR_HIP_TRY(hipGetLastError());
@@ -5705,6 +5915,37 @@ gr_status gr_bwd_fit_gather(const gr_view* v, int n, const gr_plan* plan, const 
   return bwd_impl(v, n, plan, nullptr, nullptr, nullptr, 3, nullptr, geom, bins, saved, nullptr, nullptr, nullptr,
                   target_rgb, target_mask, w_sil, g_scale, loss_out, nullptr, nullptr, nullptr, nullptr, 0, ws, ws_bytes,
                   stream, target_depth, w_depth, nullptr, sums, sums3);
+}
+
+size_t gr_bwd_ssim_bytes(const gr_view* v, int n, const gr_plan* plan) {
+  return gr_bwd_bytes(v, n, plan) + align_up(gr_ssim_ws_bytes(v->height, v->width, 3, 1));
+}
+
+gr_status gr_bwd_fit_ssim(const gr_view* v, int n, const gr_plan* plan, const float* means, const float* scales,
+                          const float* colors, int color_dim, const float* opacities, const void* geom, const void* bins,
+                          const float* saved, const float* target_rgb, const float* target_mask, float w_sil,
+                          const float* target_depth, float w_depth, float g_scale, float w_dssim, float* loss_out,
+                          float* d_means, float* d_scales, float* d_colors, float* d_opacities, int accumulate, void* ws,
+                          size_t ws_bytes, void* stream) {
+  if (!target_rgb) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_bwd_fit_ssim: target_rgb is null");
+  if (!(w_dssim >= 0.0f && w_dssim <= 1.0f))
+    return set_error(GR_ERR_INVALID_ARGUMENT, "gr_bwd_fit_ssim: w_dssim must be in [0, 1]");
+  return bwd_impl(v, n, plan, means, scales, colors, color_dim, opacities, geom, bins, saved, nullptr, nullptr, nullptr,
+                  target_rgb, target_mask, w_sil, g_scale, loss_out, d_means, d_scales, d_colors, d_opacities,
+                  accumulate, ws, ws_bytes, stream, target_depth, w_depth, nullptr, nullptr, nullptr, w_dssim);
+}
+
+gr_status gr_bwd_fit_ssim_gather(const gr_view* v, int n, const gr_plan* plan, const void* geom, const void* bins,
+                                 const float* saved, const float* target_rgb, const float* target_mask, float w_sil,
+                                 const float* target_depth, float w_depth, float g_scale, float w_dssim, float* loss_out,
+                                 void* ws, size_t ws_bytes, float* sums, float* sums3, void* stream) {
+  if (!target_rgb) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_bwd_fit_ssim_gather: target_rgb is null");
+  if (!sums) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_bwd_fit_ssim_gather: sums is null");
+  if (!(w_dssim >= 0.0f && w_dssim <= 1.0f))
+    return set_error(GR_ERR_INVALID_ARGUMENT, "gr_bwd_fit_ssim_gather: w_dssim must be in [0, 1]");
+  return bwd_impl(v, n, plan, nullptr, nullptr, nullptr, 3, nullptr, geom, bins, saved, nullptr, nullptr, nullptr,
+                  target_rgb, target_mask, w_sil, g_scale, loss_out, nullptr, nullptr, nullptr, nullptr, 0, ws, ws_bytes,
+                  stream, target_depth, w_depth, nullptr, sums, sums3, w_dssim);
 }
 
 gr_status gr_bwd_l1(const gr_view* v, int n, const gr_plan* plan, const float* means, const float* scales,

@@ -389,9 +389,12 @@ class ViewShardedFitter:
     def __init__(self, params: dict, cams: list, targets: list, width: int, height: int, lr: float = 0.02,
                  masks: Optional[list] = None, depths: Optional[list] = None, silhouette_weight: float = 0.2,
                  depth_weight: float = 0.05, reg_opacity: float = 1e-3, reg_scale: float = 1e-3,
-                 render_fn: RenderFn = hip_render, group=None, reorder: bool = True, dssim_weight: float = 0.0):
+                 render_fn: RenderFn = hip_render, group=None, reorder: bool = True, dssim_weight: float = 0.0,
+                 dssim_fused: bool = False):
         # dssim_weight l > 0: a view's photometric term is (1 - l) mean|pred - tgt| + l dssim(pred, tgt)
         # (losses.dssim_loss) on the per-view autograd path; 0 (default): the L1 fit, every path as it was
+        # dssim_fused (with l > 0, the HIP render op): the fused path's D-SSIM form (_views_direct_ssim or the native
+        # executor: gr_bwd_fit_ssim_gather per view, no autograd and no gradient image) instead of the autograd path
         # reorder: keep the Gaussians in spatial (Morton) order, re-established after every
         # densify/prune (spatial_order); off only to compare with an unpermuted run
         # perm: self.params[k][i] = canonical[k][perm[i]], the canonical order being the stub's (the
@@ -420,6 +423,7 @@ class ViewShardedFitter:
         if not 0.0 <= dssim_weight <= 1.0:
             raise ValueError(f"dssim_weight must be in [0, 1], got {dssim_weight}")
         self.w_dssim = float(dssim_weight)
+        self.dssim_fused = bool(dssim_fused)
         self.reg_opacity, self.reg_scale = reg_opacity, reg_scale
         self.render_fn = render_fn
         self.group = group
@@ -565,7 +569,14 @@ class ViewShardedFitter:
         three-piece splits have 16-pixel kernels only)."""
         return (16 if F32_GRADE else FIT_TILE) or 16
 
+    def _ssim_form(self) -> bool:
+        """The fused path runs its D-SSIM form (dssim_fused with a D-SSIM term): whole views with 16-pixel tiles, the
+        per-view schedule only (no batched / graph step, no tile-row bands: an SSIM window crosses band rows)."""
+        return self.dssim_fused and self.w_dssim > 0.0
+
     def _bands_ok(self) -> bool:
+        if self._ssim_form():
+            return False
         V, W = len(self.targets), self.world
         r = V % W if W > 1 else 0
         if not (BAND_SPLIT and r and not self._depth_grad()):
@@ -700,8 +711,9 @@ class ViewShardedFitter:
         """The fused path (_views_direct, or _views_direct_depth with a depth term): HIP render op, the
         view loss and its gradients in the C ABI, no autograd per view.  Needs float32 parameters and
         targets / masks / depths of exactly the image's shape (checked at construction).  A D-SSIM term
-        (dssim_weight > 0) is not fused into the splat epilogues: such a fit takes the per-view autograd path."""
-        if self.w_dssim > 0.0:
+        (dssim_weight > 0) is not fused into the splat epilogues: such a fit takes the per-view autograd path, or with
+        dssim_fused the fused path's D-SSIM form (_ssim_form)."""
+        if self.w_dssim > 0.0 and not self.dssim_fused:
             return False
         return (self.render_fn is hip_render and device.type == "cuda" and FUSED_LOSS and DIRECT_BACKWARD
                 and self._images_ok and all(p.dtype == torch.float32 for p in self.params.values()))
@@ -722,7 +734,7 @@ class ViewShardedFitter:
                 reg_fn = (lambda: reg_t) if reg_t is not None else None
                 reg = None
                 if self._native_exec() and GATHER:
-                    total = self._views_native(means, scales, colors, opacities, self._depth_grad())
+                    total = self._views_native(means, scales, colors, opacities, self._depth_grad(), ssim=self._ssim_form())
                     # the regulariser's small kernels after the executor's call (the host starts the views'
                     # preparations first), on the preparation stream behind the last preparation when the executor
                     # runs on this driver's streams (as the Python schedule does; no extra hardware queue)
@@ -735,6 +747,9 @@ class ViewShardedFitter:
                         main.wait_stream(rs)
                     elif reg_fn:
                         reg = reg_fn()
+                elif self._ssim_form():
+                    reg = reg_fn() if reg_fn else None
+                    total = self._views_direct_ssim(means, scales, colors, opacities)
                 elif self._depth_grad():
                     reg = reg_fn() if reg_fn else None
                     total = self._views_direct_depth(means, scales, colors, opacities)
@@ -749,7 +764,9 @@ class ViewShardedFitter:
             return self._fused_param_step(scales, opacities, loss)
         means, scales, colors, opacities = activations(self.params)
         if self._direct(device) and means.shape[0] > 0:
-            if self._depth_grad():
+            if self._ssim_form():
+                total = self._views_direct_ssim(means, scales, colors, opacities)
+            elif self._depth_grad():
                 total = self._views_direct_depth(means, scales, colors, opacities)
             else:
                 total, _ = self._views_direct(means, scales, colors, opacities)
@@ -833,9 +850,10 @@ class ViewShardedFitter:
             return self.width * self.height <= NATIVE_EXEC_MAX_PIXELS
         return str(NATIVE_EXEC) not in ("0", "False", "")
 
-    def _views_native(self, means, scales, colors, opacities, depth: bool, sized=None) -> torch.Tensor:
+    def _views_native(self, means, scales, colors, opacities, depth: bool, sized=None, ssim: bool = False) -> torch.Tensor:
         """_views_direct / _views_direct_depth through the native executor (gr_fit_views): one C call per
-        step; returns the sum of the view losses and leaves the stream accumulators in self._acc_parts."""
+        step; returns the sum of the view losses and leaves the stream accumulators in self._acc_parts.
+        ssim: _views_direct_ssim's form (gr_fit_views_ssim)."""
         device = means.device
         m, s, c, o = (t.detach().float().contiguous() for t in (means, scales, colors, opacities))
         views = self.my_views
@@ -844,7 +862,7 @@ class ViewShardedFitter:
             return torch.zeros((), device=device)
         ns = max(1, min(NUM_STREAMS, len(views)))
         w_sil = self.w_sil if (self.masks is not None and self.w_sil > 0.0) else 0.0
-        key = (tuple(views), depth, F32_GRADE, w_sil > 0.0, str(device), sized is not None)
+        key = (tuple(views), depth, F32_GRADE, w_sil > 0.0, str(device), sized is not None, ssim)
         cache = getattr(self, "_native_targets", None)
         if cache is None or cache[0] != key:
             arr = (tr._native.GrFitTarget * len(views))()
@@ -860,7 +878,8 @@ class ViewShardedFitter:
                     arr[j].view = gvd[i] if sized is None else tr.sized_view(gvd[i])
                     arr[j].target_depth = self.depths[i].data_ptr()
                 else:
-                    arr[j].view = self._fit_view(i, device) if sized is None else tr.sized_view(self._fit_view(i, device))
+                    gvf = self._ssim_view(i, device) if ssim else self._fit_view(i, device)
+                    arr[j].view = gvf if sized is None else tr.sized_view(gvf)
                     arr[j].target_depth = None
                 arr[j].target_rgb = self.targets[self._vi(i)].data_ptr()
                 arr[j].target_mask = self.masks[self._vi(i)].data_ptr() if w_sil > 0.0 else None
@@ -894,11 +913,14 @@ class ViewShardedFitter:
             self._native_acc = cached = (shapes, acc, (ctypes.c_void_p * (4 * ns))(*[t.data_ptr() for a in acc for t in a]))
         acc, ptrs = cached[1], cached[2]
         L = tr._native.lib()
-        tr._native.check(L.gr_fit_views(tr._native.executor(device.index or 0), ctypes.byref(cfg), len(views), cache[1],
-                                        int(m.shape[0]), tr._native.ptr(m), tr._native.ptr(s), tr._native.ptr(c),
-                                        tr._color_dim(c), tr._native.ptr(o), ctypes.c_float(w_sil),
-                                        ctypes.c_float(self.w_depth), ctypes.c_float(1.0 / len(self.targets)),
-                                        tr._native.ptr(losses_v), ptrs, ctypes_stream(device)), "gr_fit_views")
+        head = (tr._native.executor(device.index or 0), ctypes.byref(cfg), len(views), cache[1], int(m.shape[0]),
+                tr._native.ptr(m), tr._native.ptr(s), tr._native.ptr(c), tr._color_dim(c), tr._native.ptr(o),
+                ctypes.c_float(w_sil), ctypes.c_float(self.w_depth), ctypes.c_float(1.0 / len(self.targets)))
+        tail = (tr._native.ptr(losses_v), ptrs, ctypes_stream(device))
+        if ssim:
+            tr._native.check(L.gr_fit_views_ssim(*head, ctypes.c_float(self.w_dssim), *tail), "gr_fit_views_ssim")
+        else:
+            tr._native.check(L.gr_fit_views(*head, *tail), "gr_fit_views")
         self._acc_parts = acc
         self._native_keep = (m, s, c, o)  # read by the executor's streams until the caller's stream passes them
         return losses_v.sum()
@@ -1015,11 +1037,32 @@ class ViewShardedFitter:
         self._acc_parts = acc[:used] if used > 0 else [tuple(torch.zeros_like(t) for t in (m, s, c, o))]
         return (losses_v[:len(views)].sum() if views else torch.zeros((), device=device)), tail
 
-    def _views_direct_depth(self, means, scales, colors, opacities, sized=None) -> torch.Tensor:
+    def _ssim_view(self, i: int, device) -> "tr._native.GrView":
+        """The gr_view of view i for the fused path's D-SSIM form without a depth term: _fit_view's (one FIT_CUTOFF
+        zone, no depth gradient) with 16-pixel tiles, the SSIM kernels' tile; built once."""
+        cache = self.__dict__.setdefault("_gvs_cache", {})
+        gv = cache.get((i, F32_GRADE))
+        if gv is None:
+            cam = self.cams[i]
+            gv = cache[(i, F32_GRADE)] = tr.make_view(cam.view, cam.proj, self.width, self.height, self._background(device),
+                                                      cutoff=tr.FIT_CUTOFF, core_cutoff=tr.FIT_CUTOFF, depth_grad=False)
+            if F32_GRADE:
+                gv.no_depth_grad = 2
+        return gv
+
+    def _views_direct_ssim(self, means, scales, colors, opacities) -> torch.Tensor:
+        """The fused path's D-SSIM form (dssim_fused): _views_direct_depth's schedule with, per view, the HIP forward
+        keeping its saved sums (no image) and gr_bwd_fit_ssim_gather, whose photometric term is (1 - l) L1 + l D-SSIM;
+        with or without a depth term.  Returns the sum of the view losses."""
+        return self._views_direct_depth(means, scales, colors, opacities, ssim=True)
+
+    def _views_direct_depth(self, means, scales, colors, opacities, sized=None, ssim: bool = False) -> torch.Tensor:
         """The fused path with the depth term (fit_multiview_stub.py:301-305): per view the HIP forward in the
         default precision mode (depth output, f32-grade W and D, the depth-gradient footprint), then
         gr_bwd_fit (L1 + silhouette + depth loss gradients and the render backward) adding the gradient into
-        the stream's accumulator set (in view order: deterministic).  Returns the sum of the view losses."""
+        the stream's accumulator set (in view order: deterministic).  Returns the sum of the view losses.
+        ssim (_views_direct_ssim): gr_bwd_fit_ssim_gather in gr_bwd_fit_gather's place, and without a depth term the
+        views of _ssim_view and no depth sums."""
         device = means.device
         m, s, c, o = (t.detach().float().contiguous() for t in (means, scales, colors, opacities))
         views = self.my_views
@@ -1049,7 +1092,11 @@ class ViewShardedFitter:
             self._gvd_cache = cache = {}
         ahead: dict = {}
 
+        depth = self._depth_grad()
+
         def gv_of(i):
+            if ssim and not depth:
+                return self._ssim_view(i, device)
             if i not in cache:
                 cam = self.cams[i]
                 cache[i] = tr.make_view(cam.view, cam.proj, self.width, self.height, self._background(device),
@@ -1085,10 +1132,16 @@ class ViewShardedFitter:
             with torch.cuda.stream(streams[k]):
                 _, _, _, rs = tr.forward_native(m, s, c, o, pv.gv, pv, images=False)  # the backward reads the sums
                 pv = None
-                sums, sums3 = tr.backward_fit_gather_native(rs, self.targets[i], self.masks[i] if w_sil > 0.0 else None,
-                                                            w_sil, self.depths[i], self.w_depth, g_scale,
-                                                            losses_v[j:j + 1])
-                pending[k].append((rs.gv, sums, sums3))
+                if ssim:
+                    sums, sums3 = tr.backward_fit_ssim_gather_native(
+                        rs, self.targets[i], self.masks[i] if w_sil > 0.0 else None, w_sil,
+                        self.depths[i] if depth else None, self.w_depth if depth else 0.0, g_scale, self.w_dssim,
+                        losses_v[j:j + 1])
+                else:
+                    sums, sums3 = tr.backward_fit_gather_native(rs, self.targets[i], self.masks[i] if w_sil > 0.0 else None,
+                                                                w_sil, self.depths[i], self.w_depth, g_scale,
+                                                                losses_v[j:j + 1])
+                pending[k].append((rs.gv, sums, sums3) if sums3 is not None else (rs.gv, sums))
                 rs = None
             prepare_upto(j + PREP_AHEAD)
             if len(pending[k]) >= sizes[k][0]:
@@ -1265,7 +1318,10 @@ class ViewShardedFitter:
     # ---- the fused step as one HIP graph (GR_GRAPH) -------------------------------------------------------------
     def _graph_ok(self, device) -> bool:
         """The graph applies: the fused path with its one-launch parameter update (world size 1), the Python
-        schedule without a separate binning stream, and the optimizer state made by an eager step."""
+        schedule without a separate binning stream, and the optimizer state made by an eager step.  Not the D-SSIM
+        form: the batched and graph steps have none."""
+        if self._ssim_form():
+            return False
         mode = self._graph_mode()
         if not (mode != "0" and self.world == 1 and device.type == "cuda" and BIN_STREAM == "" and self._direct(device)
                 and self.params["means"].shape[0] > 0 and self._fused_step_ok()):
@@ -1683,6 +1739,9 @@ def main(argv=None) -> None:
     ap.add_argument("--depth_weight", type=float, default=0.05)
     ap.add_argument("--dssim_weight", type=float, default=0.0,
                     help="l in (1 - l) L1 + l (1 - SSIM) for the photometric term (0: the reference's L1 fit)")
+    ap.add_argument("--dssim_fused", action="store_true",
+                    help="with --dssim_weight > 0 on the HIP device: the fused path's D-SSIM form (the D-SSIM backward "
+                         "fused with the render backward's upstream pass) instead of the per-view autograd path")
     ap.add_argument("--reg_opacity", type=float, default=0.001)
     ap.add_argument("--reg_scale", type=float, default=0.001)
     ap.add_argument("--seed", type=int, default=None, help="torch.manual_seed before initialisation")
@@ -1735,7 +1794,8 @@ def main(argv=None) -> None:
     params = build_params(args.num_gaussians, device, args.use_sh, args.sh_degree)
     fitter = ViewShardedFitter(params, cams, targets, args.width, args.height, lr=args.lr, masks=masks, depths=depths,
                                silhouette_weight=args.silhouette_weight, depth_weight=args.depth_weight,
-                               reg_opacity=args.reg_opacity, reg_scale=args.reg_scale, dssim_weight=args.dssim_weight)
+                               reg_opacity=args.reg_opacity, reg_scale=args.reg_scale, dssim_weight=args.dssim_weight,
+                               dssim_fused=args.dssim_fused)
     loss_log = []
     pending = []  # the step tensors not yet read: a replayed step found to have overflowed is redone and its loss
     #               rewritten in place one step later (graph_sync), so the host reads them after that

@@ -750,6 +750,56 @@ def backward_fit_gather_native(st: RenderState, target, mask, w_sil: float, dept
     return sums, sums3
 
 
+def _ssim_ws(L, st: RenderState, dev) -> torch.Tensor:
+    return torch.empty((_ws_round(L.gr_bwd_ssim_bytes(ctypes.byref(st.gv), st.n, ctypes.byref(st.plan))),),
+                       dtype=torch.uint8, device=dev)
+
+
+def backward_fit_ssim_native(means, scales, colors, opacities, st: RenderState, target, mask, w_sil: float, depth_target,
+                             w_depth: float, g_scale: float, w_dssim: float, loss_out, grads, accumulate: bool) -> None:
+    """gr_bwd_fit_ssim on the current stream: as ``backward_fit_native`` for the view loss ``(1 - l) mean|out - target|
+    + l dssim(out, target) + w_sil mean|alpha - mask| (+ the depth term)``, l = ``w_dssim`` in [0, 1]: the D-SSIM
+    forward from the saved sums and its backward fused with the upstream pass, no image and no gradient image
+    (``mask`` / ``depth_target`` may be None; a depth target needs the view rendered with depth_grad=True)."""
+    L = _native.lib()
+    dev = means.device
+    _check_params(means, scales, colors, opacities)
+    _check_operand(target, (st.gv.height, st.gv.width, 3), "target", dev)
+    _check_operand(mask, (st.gv.height, st.gv.width), "mask", dev)
+    _check_operand(depth_target, (st.gv.height, st.gv.width), "depth_target", dev)
+    ws = _ssim_ws(L, st, dev)
+    dm, ds, dc, do = grads
+    _native.check(L.gr_bwd_fit_ssim(ctypes.byref(st.gv), st.n, ctypes.byref(st.plan), _native.ptr(means), _native.ptr(scales),
+                                    _native.ptr(colors), _color_dim(colors), _native.ptr(opacities), _native.ptr(st.geom),
+                                    _native.ptr(st.bins), _native.ptr(st.saved), _native.ptr(target), _native.ptr(mask),
+                                    ctypes.c_float(w_sil), _native.ptr(depth_target), ctypes.c_float(w_depth),
+                                    ctypes.c_float(g_scale), ctypes.c_float(w_dssim), _native.ptr(loss_out),
+                                    _native.ptr(dm), _native.ptr(ds), _native.ptr(dc), _native.ptr(do),
+                                    1 if accumulate else 0, _native.ptr(ws), ws.numel(), _stream(dev)), "gr_bwd_fit_ssim")
+
+
+def backward_fit_ssim_gather_native(st: RenderState, target, mask, w_sil: float, depth_target, w_depth: float,
+                                    g_scale: float, w_dssim: float, loss_out):
+    """gr_bwd_fit_ssim_gather on the current stream: ``backward_fit_ssim_native`` up to the view's per-Gaussian sums;
+    returns (sums (n, 8), depth sums (n,) or None without a depth target) for reduce_sums_native (the view's geom,
+    bins and saved sums are free after it)."""
+    L = _native.lib()
+    dev = st.saved.device
+    _check_operand(target, (st.gv.height, st.gv.width, 3), "target", dev)
+    _check_operand(mask, (st.gv.height, st.gv.width), "mask", dev)
+    _check_operand(depth_target, (st.gv.height, st.gv.width), "depth_target", dev)
+    ws = _ssim_ws(L, st, dev)
+    sums = torch.empty((st.n, 8), dtype=torch.float32, device=dev)
+    sums3 = torch.empty((st.n,), dtype=torch.float32, device=dev) if depth_target is not None else None
+    _native.check(L.gr_bwd_fit_ssim_gather(ctypes.byref(st.gv), st.n, ctypes.byref(st.plan), _native.ptr(st.geom),
+                                           _native.ptr(st.bins), _native.ptr(st.saved), _native.ptr(target),
+                                           _native.ptr(mask), ctypes.c_float(w_sil), _native.ptr(depth_target),
+                                           ctypes.c_float(w_depth), ctypes.c_float(g_scale), ctypes.c_float(w_dssim),
+                                           _native.ptr(loss_out), _native.ptr(ws), ws.numel(), _native.ptr(sums),
+                                           _native.ptr(sums3), _stream(dev)), "gr_bwd_fit_ssim_gather")
+    return sums, sums3
+
+
 def reduce_sums_native(means, scales, colors, opacities, batch, grads, accumulate: bool) -> None:
     """gr_reduce_sums on the current stream: ``batch`` = [(gr_view, sums from gather_view_native), ...] or
     [(gr_view, sums, depth sums from backward_fit_gather_native), ...] (at most _native.REDUCE_MAX_VIEWS); the views'
