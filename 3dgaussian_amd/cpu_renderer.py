@@ -22,6 +22,8 @@ Memory stays O(chunk * (H + W) + H * W) per view instead of the reference's ~40 
 """
 from __future__ import annotations
 
+import contextlib
+
 import torch
 
 # Gaussians per GEMM chunk (bounds the (G, 5, W) operand)
@@ -153,11 +155,44 @@ class _Splat(torch.autograd.Function):
         return d_px, d_py, d_sx, d_sy, d_ov, d_c, d_za, g_bg, None, None
 
 
+_position_sink = None  # capture_position_grads: called with each render's (d_px, d_py, width, height) in its backward
+
+
+@contextlib.contextmanager
+def capture_position_grads(sink):
+    """Every render() made inside the context reports the gradient of whatever is later differentiated with respect to
+    its Gaussians' pixel centres: ``sink(d_px, d_py, width, height)`` ((N,) each) runs once in that render's backward
+    (_Splat.backward forms both; hooks on px / py hand them over).  What the fit's density statistics read on this
+    device, where no fused path exists (fit_multiview.ViewShardedFitter(density_stats=True))."""
+    global _position_sink
+    prev, _position_sink = _position_sink, sink
+    try:
+        yield
+    finally:
+        _position_sink = prev
+
+
+def _hook_position_grads(px, py, sink, width: int, height: int) -> None:
+    got = {}
+
+    def hook(name):
+        def fn(g):
+            got[name] = g
+            if len(got) == 2:
+                sink(got.pop("px").detach(), got.pop("py").detach(), width, height)
+        return fn
+
+    px.register_hook(hook("px"))
+    py.register_hook(hook("py"))
+
+
 def render(means, scales, colors, opacities, view, proj, width: int, height: int, background):
     """Differentiable dense render on the tensors' (non-HIP) device: (out (H,W,3), alpha, depth)."""
     view = view.to(dtype=means.dtype, device=means.device)
     proj = proj.to(dtype=means.dtype, device=means.device)
     px, py, valid, za = _project(means, view, proj, width, height)
+    if _position_sink is not None and px.requires_grad:
+        _hook_position_grads(px, py, _position_sink, width, height)
     col = _colors(colors, means, view).clamp(0.0, 1.0)
     fx, fy = proj[0, 0].abs(), proj[1, 1].abs()
     sx = (scales[:, 0].abs() * 0.5 * width * fx / za).clamp_min(1.0)

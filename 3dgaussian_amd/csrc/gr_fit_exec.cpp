@@ -7,7 +7,7 @@
 // (the small-view configs and the per-rank share of a multi-GPU step are host-bound in Python).
 //
 // Only the public C ABI (gr_fwd_prepare_views_async, gr_fwd_render_l1, gr_bwd_splat, gr_gather_view,
-// gr_reduce_sums, gr_fwd_render, gr_bwd_fit_gather, gr_bwd_fit_ssim_gather) and the HIP runtime are used.
+// gr_reduce_sums, gr_density_stats, gr_fwd_render, gr_bwd_fit_gather, gr_bwd_fit_ssim_gather) and the HIP runtime are used.
 // Workspaces are the executor's own, kept across steps and reused only in stream order: each render stream owns its view workspace
 // (bins, forward scratch, backward workspace, saved sums) and a ring of per-view sums for its reduction
 // batch; the geoms are a ring of slots written on the preparation stream, a slot being rewritten only
@@ -101,6 +101,7 @@ struct gr_executor {
   std::vector<StreamWs> ws;        // per render stream
   std::vector<GeomSlot> geoms;     // ring of geom slots
   std::vector<hipStream_t> last;   // the previous call's render streams 1.. and preparation stream
+  float* const* stats = nullptr;   // gr_executor_density_stats: one [n][2] buffer per render stream, or none
 };
 
 #define GR_EXEC_TRY(expr)                                                            \
@@ -204,6 +205,12 @@ static gr_status fit_views_checked(gr_executor* ex, const gr_fit_config* cfg, in
   return st;
 }
 
+gr_status gr_executor_density_stats(gr_executor* ex, float* const* stats_per_stream) {
+  if (!ex) return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, "gr_executor_density_stats: null executor");
+  ex->stats = stats_per_stream;
+  return GR_OK;
+}
+
 gr_status gr_fit_views(gr_executor* ex, const gr_fit_config* cfg, int num_views, const gr_fit_target* views, int n,
                        const float* means, const float* scales, const float* colors, int color_dim,
                        const float* opacities, float w_sil, float w_depth, float g_scale, float* losses,
@@ -234,6 +241,8 @@ static gr_status fit_views_on_device(gr_executor* ex, const gr_fit_config* cfg, 
   for (int k = 0; k < ns; ++k)
     for (int q = 0; q < 4; ++q)
       if (!acc[4 * k + q]) return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, "gr_fit_views: null accumulator");
+  for (int k = 0; ex->stats && k < ns; ++k)
+    if (!ex->stats[k]) return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, "gr_fit_views: null density stats buffer");
   hipStream_t main = (hipStream_t)stream;
   // streams, events and the plan array, grown on demand and kept
   while (!cfg->render_streams && (int)ex->side.size() < ns - 1) {
@@ -376,6 +385,8 @@ static gr_status enqueue_views(gr_executor* ex, const gr_fit_config* cfg, int nu
     }
     GR_EXEC_CALL(gr_reduce_sums(nb, b, n, means, scales, colors, color_dim, opacities, acc[4 * k + 0], acc[4 * k + 1],
                                 acc[4 * k + 2], acc[4 * k + 3], started[k], st[k]));
+    if (ex->stats)  // the batch's density statistics beside its chain rule (gr_executor_density_stats)
+      GR_EXEC_CALL(gr_density_stats(nb, b, n, means, scales, opacities, 1.0f / g_scale, ex->stats[k], st[k]));
     pending[k].clear();
     started[k] = 1;
     return GR_OK;

@@ -4035,6 +4035,43 @@ __global__ __launch_bounds__(256) void k_reduce_sums(SBatch B, int n, const floa
   for (int q = 0; q < CD; ++q) out.color(q, gr.c[q]);
 }
 
+// Density statistics of a batch of gathered views (gr_density_stats): one lane per Gaussian, the views in batch
+// order.  Per view that saw the Gaussian (k_reduce_sums' `on` test on the same unpacking of its sums row) the norm
+// of the view loss's gradient with respect to the Gaussian's NDC x / y, from the two position moments exactly as
+// proj_grads forms d px, d py and their NDC factors; the upstream scale of the step (g_scale) is divided out.
+// One float2 load and store per Gaussian, no atomics: deterministic.  A kernel of its own (~30 VGPRs) rather than
+// a mode of k_reduce_sums, whose 240 VGPRs at SH degree 3 and results stay as they are.
+__global__ __launch_bounds__(256) void k_density_stats(SBatch B, int n, const float* __restrict__ means,
+                                                       const float* __restrict__ scales, const float* __restrict__ opac,
+                                                       float inv_g_scale, float2* __restrict__ stats) {
+  const int i = blockIdx.x * 256 + (int)threadIdx.x;
+  if (i >= n) return;
+  const float mx = means[3 * (size_t)i], my = means[3 * (size_t)i + 1], mz = means[3 * (size_t)i + 2];
+  const float s0 = scales[3 * (size_t)i], s1 = scales[3 * (size_t)i + 1];
+  const float op = opac[i];
+  const float o = op < 0.0f ? 0.0f : op;
+  float g = 0.0f, seen = 0.0f;
+  for (int vi = 0; vi < B.nv; ++vi) {
+    const float4 a = B.r[vi].sums[2 * (size_t)i], b = B.r[vi].sums[2 * (size_t)i + 1];
+    const float s3 = B.r[vi].sums3 ? B.r[vi].sums3[i] : 0.0f;
+    const bool on = a.x != 0.f || a.y != 0.f || a.z != 0.f || a.w != 0.f || b.x != 0.f || b.y != 0.f || b.z != 0.f ||
+                    b.w != 0.f || s3 != 0.f;
+    if (!on) continue;
+    const ViewK& v = B.r[vi].v;
+    Proj p;
+    project(v, mx, my, mz, s0, s1, p);
+    // [o S0, o S2, S4, S6 | o S1, S8, S5, S7]: the position moments S5 = b.z, S6 = a.w
+    const float dpx = o * b.z / (p.sx * p.sx), dpy = o * a.w / (p.sy * p.sy);
+    const float dndx = dpx * 0.5f * (v.W - 1), dndy = dpy * 0.5f * (v.H - 1);
+    g += inv_g_scale * hypotf(dndx, dndy);
+    seen += 1.0f;
+  }
+  float2 st = stats[i];
+  st.x += g;
+  st.y += seen;
+  stats[i] = st;
+}
+
 // The projection half of the chain rule (torch_renderer.py:57-78, 146-150) from a Gaussian's sums S (SURVEY.md
 // App. A): the gradients of its clamped sigmas, of its camera-space point pc and of its clip-space point (shared
 // by chain_rule and the camera gradient, k_camera_grad).
@@ -6329,6 +6366,33 @@ gr_status gr_reduce_sums(int num_views, const gr_sums_view* views, int n, const 
                        d_colors, d_opacities, accumulate, (const int*)nullptr);
   GR_HIP_TRY(hipGetLastError());
   prof_mark(PROF_REDUCE, s);
+  return GR_OK;
+}
+
+gr_status gr_density_stats(int num_views, const gr_sums_view* views, int n, const float* means, const float* scales,
+                           const float* opacities, float inv_g_scale, float* stats, void* stream) {
+  if (num_views < 1 || num_views > GR_REDUCE_MAX_VIEWS)
+    return set_error(GR_ERR_INVALID_ARGUMENT, "gr_density_stats: num_views must be in [1, GR_REDUCE_MAX_VIEWS]");
+  if (n < 0) return set_error(GR_ERR_INVALID_ARGUMENT, "n must be >= 0");
+  if (n == 0) return GR_OK;
+  if (!views || !means || !scales || !opacities || !stats)
+    return set_error(GR_ERR_INVALID_ARGUMENT, "gr_density_stats: null pointer");
+  SBatch B;
+  B.nv = 0;
+  for (int k = 0; k < num_views; ++k) {
+    gr_status st = check_view(&views[k].view);
+    if (st != GR_OK) return st;
+    if (!views[k].sums) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_density_stats: null sums");
+    if (views[k].view.rows > 0) continue;  // a band: its partial gradient norm is no share of the view's
+    B.r[B.nv].v = make_viewk(&views[k].view);
+    B.r[B.nv].sums = (const float4*)views[k].sums;
+    B.r[B.nv].sums3 = views[k].sums3;
+    ++B.nv;
+  }
+  if (B.nv == 0) return GR_OK;
+  hipLaunchKernelGGL(k_density_stats, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, B, n, means, scales,
+                     opacities, inv_g_scale, (float2*)stats);
+  GR_HIP_TRY(hipGetLastError());
   return GR_OK;
 }
 

@@ -828,6 +828,33 @@ def reduce_sums_native(means, scales, colors, opacities, batch, grads, accumulat
                   "gr_reduce_sums")
 
 
+def density_stats_native(means, scales, opacities, batch, inv_g_scale: float, stats) -> None:
+    """gr_density_stats on the current stream, beside ``reduce_sums_native`` on the same ``batch``: per Gaussian,
+    ``stats[:, 0]`` += the batch's views' norms of the view loss's gradient w.r.t. the Gaussian's NDC x / y
+    (``inv_g_scale`` = 1 / the step's g_scale divides the upstream scale out), ``stats[:, 1]`` += the number of views
+    that saw it.  ``stats``: (n, 2) float32, one per stream.  Band views (rows > 0) contribute nothing."""
+    L = _native.lib()
+    if not 1 <= len(batch) <= _native.REDUCE_MAX_VIEWS:
+        raise ValueError(f"1 to {_native.REDUCE_MAX_VIEWS} views per gr_density_stats batch")
+    n = int(means.shape[0])
+    dev = means.device
+    _check_operand(means, (n, 3), "means", dev)
+    _check_operand(scales, (n, 3), "scales", dev)
+    _check_operand(opacities, (n,), "opacities", dev)
+    _check_operand(stats, (n, 2), "stats", dev)
+    arr = (_native.GrSumsView * len(batch))()
+    for k, item in enumerate(batch):
+        gv, sums = item[0], item[1]
+        sums3 = item[2] if len(item) > 2 else None
+        _check_operand(sums, (n, 8), "sums", dev)
+        _check_operand(sums3, (n,), "sums3", dev)
+        arr[k].view = gv
+        arr[k].sums = sums.data_ptr()
+        arr[k].sums3 = sums3.data_ptr() if sums3 is not None else None
+    _native.check(L.gr_density_stats(len(batch), arr, n, _native.ptr(means), _native.ptr(scales), _native.ptr(opacities),
+                                     ctypes.c_float(inv_g_scale), _native.ptr(stats), _stream(dev)), "gr_density_stats")
+
+
 def _grad_background(st: RenderState, background: torch.Tensor, g_out: torch.Tensor) -> torch.Tensor:
     """d(out)/d(bg) = sum_p g_out * [0<=out_r<=1] / (1+W)  (torch_renderer.py:194-196)."""
     HW = st.gv.width * st.gv.height
@@ -1198,5 +1225,5 @@ def render_gaussians_torch(
 __all__ = ["Camera", "get_default_device", "perspective", "look_at", "render_gaussians_torch", "rasterize",
            "make_view", "prepare_view", "prepare_native", "Prepared", "forward_native", "backward_native",
            "backward_l1_native", "backward_fit_native", "backward_fit_gather_native", "forward_l1_native", "backward_splat_native", "reduce_views_native",
-           "gather_view_native", "reduce_sums_native",
+           "gather_view_native", "reduce_sums_native", "density_stats_native",
            "DEFAULT_CUTOFF", "DEPTH_GRAD_CUTOFF", "DEFAULT_CORE_CUTOFF", "FIT_CUTOFF", "default_cutoff"]

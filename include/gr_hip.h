@@ -338,6 +338,26 @@ gr_status gr_reduce_sums(int num_views, const gr_sums_view* views, int n, const 
                          const float* opacities, float* d_means, float* d_scales, float* d_colors,
                          float* d_opacities, int accumulate, void* stream);
 
+/* Density statistics of a gr_reduce_sums batch (an extension: the reference's densify rule,
+ * fit_multiview_stub.py:140-197, reads opacities only; adaptive density control reads each Gaussian's screen-space
+ * positional gradient, which the chain rule folds into d_means and never exposes).  Called beside gr_reduce_sums on
+ * the same batch and stream (one launch, k_density_stats, one lane per Gaussian).  Per Gaussian i and view v of the
+ * batch, in batch order, with S5, S6 the position moments of the view's sums row (unpacked as gr_reduce_sums does),
+ * sx, sy the view's projected sigmas and o = max(opacity, 0):
+ *     dpx = o S5 / sx^2,  dpy = o S6 / sy^2,   g_v = inv_g_scale * hypot(dpx (W - 1) / 2, dpy (H - 1) / 2)
+ * i.e. with inv_g_scale = 1 / g_scale of the step the norm of the *unscaled view loss's* gradient with respect to
+ * the Gaussian's NDC x / y: the unit of splatting trainers' densify thresholds, independent of the number of views.
+ * A view sees the Gaussian when its sums row (sums3 included when present) is not all zero.  Once per call
+ *     stats[i][0] += sum_v g_v,   stats[i][1] += number of seeing views      (stats: [n][2] float32, device)
+ *   - views with rows > 0 (bands of a view split across ranks) are skipped: a band's partial gradient norm is not a
+ *     share of the whole view's
+ *   - num_views outside [1, GR_REDUCE_MAX_VIEWS], or a null pointer with n > 0: GR_ERR_INVALID_ARGUMENT; n == 0: no-op
+ *   - one 8-byte load and store per Gaussian, no atomics: deterministic; stream-ordered, no allocation.  Two streams
+ *     must not add into one stats buffer (keep one per stream, as the gradient accumulators). */
+gr_status gr_density_stats(int num_views, const gr_sums_view* views, int n, const float* means,
+                           const float* scales, const float* opacities, float inv_g_scale, float* stats,
+                           void* stream);
+
 /* gr_bwd_fit / gr_bwd_fit_gather for the loss Gaussian-splatting trainers minimise (an extension, as gr_ssim_*):
  *   loss = (1 - l) mean|out - target_rgb| + l (1 - mean SSIM(out, target_rgb)) + w_sil mean|alpha - target_mask|
  *          + w_depth mean|depth / (max(depth) + 1e-6) - target_depth|,   l = w_dssim in [0, 1]
@@ -423,6 +443,13 @@ gr_status gr_fit_views_ssim(gr_executor* executor, const gr_fit_config* config, 
                             const float* colors, int color_dim, const float* opacities, float w_sil,
                             float w_depth, float g_scale, float w_dssim, float* losses, float* const* acc,
                             void* stream);
+/* Density statistics from the executor's steps: with stats_per_stream set, gr_fit_views and gr_fit_views_ssim enqueue
+ * gr_density_stats (inv_g_scale = 1 / g_scale of the call) right after each gr_reduce_sums, on the same stream, into
+ * stats_per_stream[k] ([n][2] floats, device) for render stream k < min(num_streams, num_views): one buffer per
+ * stream, as the accumulators; the caller zeroes them and sums them in stream order.  The pointer array is read
+ * during those calls (not copied) and must stay valid until it is replaced.  NULL (the default): no statistics,
+ * the calls exactly as before.  Bit-identical to fit_multiview.py's Python schedule with density_stats. */
+gr_status gr_executor_density_stats(gr_executor* executor, float* const* stats_per_stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Legacy uint8 surface (host pointers), replaces gr::render_gaussians (renderer.h:33-39).    */
