@@ -77,6 +77,7 @@ class GrPlan(ctypes.Structure):
 CAMERA_GRADS = 35  # GR_CAMERA_GRADS: d view (16), d proj (16), d cam_pos (3)
 REDUCE_MAX_VIEWS = 16  # GR_REDUCE_MAX_VIEWS
 PREPARE_MAX_VIEWS = 8  # GR_PREPARE_MAX_VIEWS
+EVAL_METRICS = 3  # GR_EVAL_METRICS: mean|x - y|, mean (x - y)^2, mean SSIM of gr_eval_view
 
 
 class GrReduceView(ctypes.Structure):
@@ -217,6 +218,10 @@ _SIG = {
     "gr_fit_views": (ctypes.c_int, [_P, ctypes.POINTER(GrFitConfig), ctypes.c_int, ctypes.POINTER(GrFitTarget), ctypes.c_int,
                                     _P, _P, _P, ctypes.c_int, _P, ctypes.c_float, ctypes.c_float, ctypes.c_float, _P,
                                     ctypes.POINTER(ctypes.c_void_p), _P]),
+    "gr_eval_ws_bytes": (ctypes.c_size_t, [_VP]),
+    "gr_eval_view": (ctypes.c_int, [_VP, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "gr_eval_views": (ctypes.c_int, [_P, ctypes.POINTER(GrFitConfig), ctypes.c_int, ctypes.POINTER(GrFitTarget), ctypes.c_int,
+                                     _P, _P, _P, ctypes.c_int, _P, _P, _P]),
     "gr_render_u8": (ctypes.c_int, [ctypes.POINTER(GrRenderParams), ctypes.c_int, _P, _P, _P, _P, _P]),
     "gr_geom_layout": (None, [ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
     "gr_bins_layout": (None, [_VP, ctypes.c_int, _PP, ctypes.POINTER(ctypes.c_size_t)]),

@@ -4558,7 +4558,9 @@ __device__ __forceinline__ void ssim_stage(const float* __restrict__ src, int H,
 //   maps[1] = dm/dsx = -m / B2            maps[2] = dm/dsxy = 2 A1 / (B1 B2)
 // The forward of one tile from its two staged windows tx, ty (published by a barrier): the separable sums, the tile's
 // sum of m into partial[tile] and (GRAD) the three maps.
-template <int C, bool GRAD>
+// FORM: the caller's own instantiation, the same code (k_eval_view passes 1: sharing k_ssim_fwd<3, false>'s instantiation
+// made that kernel's last tree step compile to other, equivalent instructions).
+template <int C, bool GRAD, int FORM = 0>
 __device__ __forceinline__ void ssim_fwd_tile(const float* tx, const float* ty, float (*hs)[SE * ST * C], float* red, int H,
                                               int W, float* __restrict__ partial, float* __restrict__ maps) {
   constexpr int TC = ST * C, SP = SE * C;
@@ -4687,6 +4689,94 @@ __global__ __launch_bounds__(256) void k_ssim_final(const float* __restrict__ pa
     __syncthreads();
   }
   if (t == 0) *dssim = (float)(1.0 - r[0] / (double)n);
+}
+
+// View metrics for held-out evaluation (gr_eval_view): k_ssim_fwd<3, false> of a view's render against its target with
+// the rendered image staged from the saved sums as k_ssim_fwd_saved does (same grid, the same partial sums of m bit for
+// bit, no maps), and from the same two staged windows, without a second global read, the tile's sums of |x - y| and
+// (x - y)^2 over its in-image values (three values per thread, then the fixed tree of the SSIM sum).  Three float
+// partials per tile: partial[q * plane + tile], q = 0 the SSIM sum, 1 the absolute, 2 the squared differences.
+// LDS as the forward's (the second tree runs in hs, free by then): three workgroups per CU.
+__global__ __launch_bounds__(256) void k_eval_view(ViewK v, const float4* __restrict__ saved4, const float* __restrict__ y,
+                                                   float* __restrict__ partial, int plane) {
+  constexpr int C = 3, TC = ST * C, SP = SE * C;
+  __shared__ float tx[SE * SP], ty[SE * SP];
+  __shared__ float hs[5][SE * TC];
+  __shared__ float red[256];
+  const int H = v.H, W = v.W, WC = W * C;
+  const int t = threadIdx.x;
+  const int y0 = blockIdx.y * ST, x0 = blockIdx.x * ST, v0 = blockIdx.x * TC;
+  for (int e = t; e < SE * SE; e += 256) {
+    const int r = e / SE, c = e - r * SE;
+    const int gy = y0 - SR + r, gx = x0 - SR + c;
+    float px[3] = {0.0f, 0.0f, 0.0f};
+    if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
+      const float4 s = saved4[(int64_t)gy * W + gx];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) px[k] = saved_colour(v, s, k);
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) tx[r * SP + c * C + k] = px[k];
+  }
+  ssim_stage<C>(y, H, WC, y0, v0, ty);
+  __syncthreads();
+  float a1 = 0.0f, a2 = 0.0f;
+  for (int o = t; o < ST * TC; o += 256) {
+    const int r = o / TC, c = o - r * TC;
+    if (y0 + r < H && v0 + c < WC) {
+      const int at = (r + SR) * SP + SR * C + c;
+      const float d = tx[at] - ty[at];
+      a1 += fabsf(d);
+      a2 = fmaf(d, d, a2);
+    }
+  }
+  ssim_fwd_tile<C, false, 1>(tx, ty, hs, red, H, W, partial, nullptr);
+  // behind ssim_fwd_tile's last barrier nothing reads hs any more, and red[0] only thread 0 (which rewrites it itself)
+  float* red2 = &hs[0][0];
+  red[t] = a1;
+  red2[t] = a2;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (t < w) {
+      red[t] += red[t + w];
+      red2[t] += red2[t + w];
+    }
+    __syncthreads();
+  }
+  if (t == 0) {
+    const int tile = blockIdx.y * gridDim.x + blockIdx.x;
+    partial[plane + tile] = red[0];
+    partial[2 * plane + tile] = red2[0];
+  }
+}
+
+// The three means of gr_eval_view from k_eval_view's partials, each column summed in double in k_ssim_final's order;
+// the SSIM metric is 1 - gr_ssim_fwd's dssim, formed as a caller holding that float would form it.
+__global__ __launch_bounds__(256) void k_eval_final(const float* __restrict__ partial, int plane, int blocks, int64_t n,
+                                                    float* __restrict__ metrics) {
+  __shared__ double r[3][256];
+  const int t = threadIdx.x;
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0;  // (the three columns' loads of a tile in flight together)
+  for (int i = t; i < blocks; i += 256) {
+    s0 += (double)partial[i];
+    s1 += (double)partial[plane + i];
+    s2 += (double)partial[2 * plane + i];
+  }
+  r[0][t] = s0;
+  r[1][t] = s1;
+  r[2][t] = s2;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (t < w)
+      for (int q = 0; q < 3; ++q) r[q][t] += r[q][t + w];
+    __syncthreads();
+  }
+  if (t == 0) {
+    const float dssim = (float)(1.0 - r[0][0] / (double)n);
+    metrics[0] = (float)(r[1][0] / (double)n);
+    metrics[1] = (float)(r[2][0] / (double)n);
+    metrics[2] = 1.0f - dssim;
+  }
 }
 
 // d dssim / d x, the same tiling: the three maps are convolved with the window (symmetric, zero padding: the
@@ -6775,6 +6865,35 @@ gr_status gr_ssim_bwd(const float* x, const float* y, int height, int width, int
     case 3: hipLaunchKernelGGL(k_ssim_bwd<3>, grid, dim3(256), 0, s, x, y, height, width, maps, g_loss, g_x); break;
     default: hipLaunchKernelGGL(k_ssim_bwd<4>, grid, dim3(256), 0, s, x, y, height, width, maps, g_loss, g_x); break;
   }
+  GR_HIP_TRY(hipGetLastError());
+  return GR_OK;
+}
+
+// View metrics: three planes of per-tile partial sums (k_eval_view), each of the D-SSIM forward's size.
+size_t gr_eval_ws_bytes(const gr_view* v) {
+  if (!v || !ssim_shape_ok(v->height, v->width, 3)) return 0;
+  return GR_EVAL_METRICS * ssim_partial_bytes(v->height, v->width);
+}
+
+gr_status gr_eval_view(const gr_view* v, const float* saved, const float* target_rgb, float* metrics, void* ws,
+                       size_t ws_bytes, void* stream) {
+  gr_status st = check_view(v);
+  if (st != GR_OK) return st;
+  if (tile_of(v) != T)
+    return set_error(GR_ERR_INVALID_ARGUMENT, "gr_eval_view: 32-pixel tiles (gr_view.tile = 32): an SSIM tile is a 16-pixel render tile");
+  if (v->rows > 0) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_eval_view: a band of tile rows (gr_view.rows): whole views only");
+  if (!ssim_shape_ok(v->height, v->width, 3))
+    return set_error(GR_ERR_INVALID_ARGUMENT, "gr_eval_view: the view exceeds the D-SSIM kernels' 2^30 values");
+  if (!saved || !target_rgb || !metrics || !ws) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_eval_view: null pointer");
+  if (ws_bytes < gr_eval_ws_bytes(v)) return set_error(GR_ERR_WORKSPACE, "gr_eval_view: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const ViewK vk = make_viewk(v);
+  const int plane = (int)(ssim_partial_bytes(v->height, v->width) / sizeof(float));
+  hipLaunchKernelGGL(k_eval_view, dim3(vk.tiles_x, vk.tiles_y), dim3(256), 0, s, vk, (const float4*)saved, target_rgb,
+                     (float*)ws, plane);
+  GR_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_eval_final, dim3(1), dim3(256), 0, s, (const float*)ws, plane, vk.tiles_x * vk.tiles_y,
+                     (int64_t)v->height * v->width * 3, metrics);
   GR_HIP_TRY(hipGetLastError());
   return GR_OK;
 }

@@ -25,6 +25,7 @@ from __future__ import annotations
 import argparse
 import contextlib
 import ctypes
+import json
 import math
 import os
 import sys
@@ -1799,6 +1800,151 @@ class ViewShardedFitter:
         torch.cuda.synchronize(self.params["means"].device)
         self._graph_check(self.params["means"].device)
 
+    # ---- evaluation (held-out view metrics) ---------------------------------------------------------------------
+    def _eval_view(self, cam, device) -> "tr._native.GrView":
+        """The gr_view an evaluation renders ``cam`` with: the one render_gaussians_torch(..., depth_grad=False) makes
+        for the fitter's background (16-pixel tiles, default_cutoff(False), the default core cutoff), built once per
+        camera object (kept with it, so the key stays its own)."""
+        cache = self.__dict__.setdefault("_eval_gv", {})
+        hit = cache.get(id(cam))
+        if hit is None or hit[0] is not cam or hit[2] != str(device):
+            gv = tr.make_view(cam.view, cam.proj, self.width, self.height, self._background(device), depth_grad=False)
+            cache[id(cam)] = hit = (cam, gv, str(device))
+        return hit[1]
+
+    def _eval_native_ok(self, device, targets) -> bool:
+        """evaluate() through the HIP metrics kernel: the preconditions of _direct() that concern it (the HIP render
+        op, float32 parameters, targets of exactly the image's shape read through raw pointers)."""
+        shape = (self.height, self.width, 3)
+        return (self.render_fn is hip_render and device.type == "cuda"
+                and all(p.dtype == torch.float32 for p in self.params.values())
+                and all(isinstance(t, torch.Tensor) and tuple(t.shape) == shape and t.dtype == torch.float32
+                        and t.is_contiguous() and t.device == device for t in targets))
+
+    def _eval_activations(self, device):
+        """The step's own activations (gr_fit_activations where the fused step forms them, else activations())."""
+        if (device.type == "cuda" and self.params["means"].shape[0] > 0 and self._fused_step_ok()):
+            return activations_native(self.params)[:4]
+        return tuple(t.detach() for t in activations(self.params))
+
+    def _eval_streams(self, device, ns: int):
+        """The fit step's own render and preparation streams (made here when no step has run yet)."""
+        side = getattr(self, "_side", None)
+        if ns > 1 and (side is None or len(side) != ns - 1 or side[0].device != device):
+            self._side = side = [torch.cuda.Stream(device) for _ in range(ns - 1)]
+        prep = getattr(self, "_prep", None)
+        if prep is None or prep.device != device:
+            self._prep = prep = torch.cuda.Stream(device, priority=PREP_PRIORITY)
+        return (side[:ns - 1] if ns > 1 else []), prep
+
+    def _eval_native(self, m, s, c, o, gvs, targets, out) -> None:
+        """gr_eval_views: the views' metrics into ``out`` (len(gvs), 3) through the native executor, one C call."""
+        device = m.device
+        ns = max(1, min(NUM_STREAMS, len(gvs)))
+        arr = (tr._native.GrFitTarget * len(gvs))()
+        for j, (gv, t) in enumerate(zip(gvs, targets)):
+            arr[j].view = gv
+            arr[j].target_rgb = t.data_ptr()
+            arr[j].target_mask = None
+            arr[j].target_depth = None
+        cfg = tr._native.GrFitConfig(NUM_STREAMS, PREP_AHEAD, PREP_GROUP, PREP_FIRST, REDUCE_BATCH, min(REDUCE_TAIL, REDUCE_BATCH))
+        if EXEC_STREAMS:  # the driver's own torch streams, as _views_native
+            side, prep = self._eval_streams(device, ns)
+            rs = (ctypes.c_void_p * max(1, ns - 1))(*[st.cuda_stream for st in side])  # (read during the call only)
+            cfg.render_streams = rs
+            cfg.prep_stream = prep.cuda_stream
+        tr._native.check(tr._native.lib().gr_eval_views(
+            tr._native.executor(device.index or 0), ctypes.byref(cfg), len(gvs), arr, int(m.shape[0]), tr._native.ptr(m),
+            tr._native.ptr(s), tr._native.ptr(c), tr._color_dim(c), tr._native.ptr(o), tr._native.ptr(out),
+            ctypes_stream(device)), "gr_eval_views")
+        self._eval_keep = (m, s, c, o)  # read by the executor's streams until the caller's stream passes them
+
+    def _eval_direct(self, m, s, c, o, gvs, targets, out) -> None:
+        """The Python schedule of the same calls: preparations ahead on the preparation stream, view j on render
+        stream j % NUM_STREAMS: forward_native (saved sums only) + eval_view_native into ``out[j]``."""
+        device = m.device
+        main = torch.cuda.current_stream(device)
+        ns = max(1, min(NUM_STREAMS, len(gvs)))
+        side, prep = self._eval_streams(device, ns)
+        streams = [main] + side
+        for st in streams[1:]:
+            st.wait_stream(main)
+        prep.wait_stream(main)
+        pins = self._plan_pins(len(gvs))
+        ahead: dict = {}
+        views = list(range(len(gvs)))
+        prepare_upto = self._prep_groups(views, ahead, lambda js: tr.prepare_views_native(
+            m, s, c, o, [gvs[q] for q in js], [pins[q] for q in js]), prep)
+        for j in views:
+            k = j % ns
+            prepare_upto(j)
+            pv = ahead.pop(j)
+            streams[k].wait_event(pv.event)
+            pv.geom.record_stream(streams[k])
+            with torch.cuda.stream(streams[k]):
+                _, _, _, rs = tr.forward_native(m, s, c, o, pv.gv, pv, images=False)
+                pv = None
+                tr.eval_view_native(rs, targets[j], out[j])
+                rs = None
+            prepare_upto(j + PREP_AHEAD)
+        for st in streams[1:]:
+            main.wait_stream(st)
+        main.wait_stream(prep)
+
+    def evaluate(self, cams: Optional[list] = None, targets: Optional[list] = None) -> dict:
+        """Per-view metrics of the current Gaussians against target images: float64 numpy arrays ``l1`` (mean|x - y|),
+        ``mse``, ``psnr`` (-10 log10 mse, formed on the host in double; inf at zero error) and ``ssim`` in the order of
+        the views passed, and their means ``mean_l1`` .. ``mean_ssim``.  Default views: the fitter's own training
+        views; held-out ones are passed as ``cams`` and ``targets`` ((H, W, 3) images).  The rendered image is the one
+        render_gaussians_torch(..., depth_grad=False) gives for the saved Gaussians with the fitter's background
+        (16-pixel tiles, the 7-sigma footprint: the image a user will render, not the fit path's footprint).
+        A collective: view i belongs to rank i % world, the results meet in one all-reduce of a zero-filled (V, 3)
+        tensor (one non-zero contributor per entry: exact), every rank returns the same dict.
+        On the HIP device (the HIP render op, float32 parameters and exact-shape float32 targets) the metrics come from
+        the saved sums without an image (gr_eval_view), through the native executor (gr_eval_views) where the fit step
+        uses it, else a Python schedule of the same calls; otherwise render_fn under no_grad and
+        losses.image_metrics.  Changes nothing of the fit: no gradient, optimizer, density or random state."""
+        self.graph_sync()
+        if (cams is None) != (targets is None):
+            raise ValueError("evaluate: pass both cams and targets, or neither (the training views)")
+        if cams is None:
+            cams, targets = self.cams, self.targets
+        if len(cams) != len(targets):
+            raise ValueError(f"evaluate: {len(cams)} cameras for {len(targets)} targets")
+        V = len(targets)
+        device = self.params["means"].device
+        n = int(self.params["means"].shape[0])
+        mine = list(range(self.rank, V, self.world))
+        res = torch.zeros((V, tr._native.EVAL_METRICS), dtype=torch.float32, device=device)
+        with torch.no_grad():
+            means, scales, colors, opacities = self._eval_activations(device)
+            if mine and n > 0 and self._eval_native_ok(device, [targets[i] for i in mine]):
+                m, s, c, o = (t.detach().float().contiguous() for t in (means, scales, colors, opacities))
+                gvs = [self._eval_view(cams[i], device) for i in mine]
+                out = torch.empty((len(mine), tr._native.EVAL_METRICS), dtype=torch.float32, device=device)
+                if self._native_exec() and GATHER:
+                    self._eval_native(m, s, c, o, gvs, [targets[i] for i in mine], out)
+                else:
+                    self._eval_direct(m, s, c, o, gvs, [targets[i] for i in mine], out)
+                res[mine] = out
+            else:
+                for i in mine:
+                    kw = {"depth_grad": False} if self.render_fn is hip_render else {}
+                    pred = self.render_fn(means, scales, colors, opacities, cams[i], self.width, self.height,
+                                          self._background(device), **kw)
+                    pred = pred[0] if isinstance(pred, tuple) else pred
+                    mt = losses.image_metrics(pred, targets[i].to(device))
+                    res[i] = torch.stack([mt["l1"], mt["mse"], mt["ssim"]]).to(res)
+        if self.world > 1:
+            dist.all_reduce(res, group=self.group)
+        a = res.double().cpu().numpy()
+        l1, mse, ssim = a[:, 0].copy(), a[:, 1].copy(), a[:, 2].copy()
+        with np.errstate(divide="ignore"):
+            psnr = -10.0 * np.log10(mse)
+        mean = lambda x: float(x.mean()) if V else float("nan")  # noqa: E731
+        return {"l1": l1, "mse": mse, "psnr": psnr, "ssim": ssim, "mean_l1": mean(l1), "mean_mse": mean(mse),
+                "mean_psnr": mean(psnr), "mean_ssim": mean(ssim)}
+
     def densify_and_prune(self, max_gaussians: int, densify_ratio: float, prune_opacity: float,
                           on_device: Optional[bool] = None, mode: str = "opacity", grad_threshold: float = 0.0002,
                           split_scale: float = 0.01) -> None:
@@ -1930,6 +2076,13 @@ def main(argv=None) -> None:
     ap.add_argument("--reg_opacity", type=float, default=0.001)
     ap.add_argument("--reg_scale", type=float, default=0.001)
     ap.add_argument("--seed", type=int, default=None, help="torch.manual_seed before initialisation")
+    ap.add_argument("--holdout_every", type=int, default=0,
+                    help="K > 0: the views with index %% K == 0 (in the sorted target order) are kept out of the fit and "
+                         "evaluated (PSNR / SSIM / L1 per view, eval.json); 0 (default): every view is fitted")
+    ap.add_argument("--eval_interval", type=int, default=0,
+                    help="M > 0: evaluate every M iterations and after the last (the held-out views, or without "
+                         "--holdout_every the training views); 0 (default): once after the last iteration, and only "
+                         "with --holdout_every")
     ap.add_argument("--device", default="", help="cpu: host tensors (cpu_renderer, gloo); default: the HIP device")
     args = ap.parse_args(argv)
 
@@ -1976,6 +2129,22 @@ def main(argv=None) -> None:
     else:
         cams = orbit_cameras(len(targets), args.width, args.height, device)
 
+    all_cams = cams  # (the preview renders view 0 of all)
+    hold = []
+    if args.holdout_every < 0 or args.eval_interval < 0:
+        raise ValueError("--holdout_every and --eval_interval must not be negative")
+    if args.holdout_every > 0:
+        # held-out views: out of the targets, cameras, masks, depths (and so of the densify extent below)
+        hold = [i for i in range(len(targets)) if i % args.holdout_every == 0]
+        train = [i for i in range(len(targets)) if i % args.holdout_every != 0]
+        if not train:
+            raise ValueError(f"--holdout_every {args.holdout_every} leaves no training view of {len(targets)}")
+        eval_cams, eval_targets = [cams[i] for i in hold], [targets[i] for i in hold]
+        pick = lambda xs: None if xs is None else [xs[i] for i in train]  # noqa: E731
+        targets, masks, depths, cams = pick(targets), pick(masks), pick(depths), pick(cams)
+    do_eval = args.holdout_every > 0 or args.eval_interval > 0
+    eval_log = [] if do_eval else None
+
     params = build_params(args.num_gaussians, device, args.use_sh, args.sh_degree)
     fitter = ViewShardedFitter(params, cams, targets, args.width, args.height, lr=args.lr, masks=masks, depths=depths,
                                silhouette_weight=args.silhouette_weight, depth_weight=args.depth_weight,
@@ -1995,6 +2164,16 @@ def main(argv=None) -> None:
             fitter.graph_sync()
             loss_log.extend(float(t) for t in pending)
             pending = []
+        if do_eval and ((args.eval_interval > 0 and (it + 1) % args.eval_interval == 0) or it + 1 == args.iters):
+            # a collective (every rank); the held-out views if there are any, else the training views
+            r = fitter.evaluate(eval_cams, eval_targets) if hold else fitter.evaluate()
+            n_now = int(fitter.params["means"].shape[0])
+            eval_log.append({"iter": it + 1, "n": n_now, "views": hold if hold else list(range(len(targets))),
+                             "psnr": r["psnr"].tolist(), "ssim": r["ssim"].tolist(), "l1": r["l1"].tolist(),
+                             "mean_psnr": r["mean_psnr"], "mean_ssim": r["mean_ssim"], "mean_l1": r["mean_l1"]})
+            if rank == 0:
+                print(f"eval iter {it+1:4d}  N={n_now}  PSNR={r['mean_psnr']:.3f} dB  SSIM={r['mean_ssim']:.5f}  "
+                      f"L1={r['mean_l1']:.6f}  ({'held-out' if hold else 'training'} views: {len(r['psnr'])})")
         if (it + 1) % args.prune_interval == 0 or (it + 1) % args.densify_interval == 0:
             fitter.densify_and_prune(args.max_gaussians,
                                      args.densify_ratio if (it + 1) % args.densify_interval == 0 else 0.0,
@@ -2007,14 +2186,15 @@ def main(argv=None) -> None:
                       f"p90={r['p90']:.3e} p99={r['p99']:.3e} max={r['max']:.3e}, {r['over']} at or over "
                       f"{args.densify_grad_threshold:g}; N -> {fitter.params['means'].shape[0]}")
     if rank == 0:
-        save_outputs(fitter, cams, args, Path(args.out_dir), loss_log)
+        save_outputs(fitter, all_cams, args, Path(args.out_dir), loss_log, eval_log)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
 
 
-def save_outputs(fitter: ViewShardedFitter, cams, args, out_dir: Path, loss_log) -> None:
-    """gaussians_fitted.npz / loss.txt / preview_view0.png exactly as fit_multiview_stub.py:327-380."""
+def save_outputs(fitter: ViewShardedFitter, cams, args, out_dir: Path, loss_log, eval_log=None) -> None:
+    """gaussians_fitted.npz / loss.txt / preview_view0.png exactly as fit_multiview_stub.py:327-380; with ``eval_log``
+    (--holdout_every / --eval_interval: one dict per evaluation) also eval.json."""
     from PIL import Image
 
     out_dir.mkdir(parents=True, exist_ok=True)
@@ -2032,6 +2212,8 @@ def save_outputs(fitter: ViewShardedFitter, cams, args, out_dir: Path, loss_log)
         arrays["dssim_weight"] = torch.tensor(float(args.dssim_weight))
     np.savez(out_dir / "gaussians_fitted.npz", **{k: v.detach().cpu().numpy().astype(np.float32) for k, v in arrays.items()})
     (out_dir / "loss.txt").write_text("\n".join(f"{v:.8f}" for v in loss_log), encoding="utf-8")
+    if eval_log is not None:
+        (out_dir / "eval.json").write_text(json.dumps(eval_log, indent=1), encoding="utf-8")
     with torch.no_grad():
         pred0 = tr.render_gaussians_torch(means, scales, sh if sh is not None else colors, opacities, cams[0],
                                           width=args.width, height=args.height,

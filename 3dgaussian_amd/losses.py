@@ -152,4 +152,23 @@ def ssim(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
         return 1.0 - _DSSIMLoss.apply(x, y)
 
 
-__all__ = ["l1_loss", "dssim_loss", "ssim"]
+def psnr(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """-10 log10(mean((a - b)^2)) of two images with values in [0, 1] (peak 1), ``inf`` at zero error; any device."""
+    with torch.no_grad():
+        if a.shape != b.shape:
+            raise ValueError(f"psnr: shape mismatch {tuple(a.shape)} vs {tuple(b.shape)}")
+        d = a.detach().float() - b.detach().float()
+        return -10.0 * torch.log10(torch.mean(d * d))
+
+
+def image_metrics(pred: torch.Tensor, target: torch.Tensor) -> dict:
+    """The view metrics of held-out evaluation from two (H, W, C) images, composed from existing ops (the reference
+    route of ViewShardedFitter.evaluate, and what it uses off the HIP device): 0-d tensors ``l1`` = mean|pred -
+    target|, ``mse`` = mean (pred - target)^2, ``psnr`` (``psnr``) and ``ssim`` (``ssim``).  No gradient."""
+    with torch.no_grad():
+        x, y = _ssim_args("image_metrics", pred.detach(), target)
+        d = x - y
+        return {"l1": torch.mean(torch.abs(d)), "mse": torch.mean(d * d), "psnr": psnr(x, y), "ssim": ssim(x, y)}
+
+
+__all__ = ["l1_loss", "dssim_loss", "ssim", "psnr", "image_metrics"]

@@ -855,6 +855,20 @@ def density_stats_native(means, scales, opacities, batch, inv_g_scale: float, st
                                      ctypes.c_float(inv_g_scale), _native.ptr(stats), _stream(dev)), "gr_density_stats")
 
 
+def eval_view_native(st: RenderState, target, metrics_out) -> None:
+    """gr_eval_view on the current stream: ``metrics_out`` (``_native.EVAL_METRICS`` float32 on the device) receives
+    mean|out - target|, mean (out - target)^2 and the mean SSIM of the view's render against ``target`` (H, W, 3), the
+    rendered colours formed from the state's saved sums (no image read or written; a ``forward_native`` state with
+    or without images, 16-pixel tiles, a whole view)."""
+    L = _native.lib()
+    dev = st.saved.device
+    _check_operand(target, (st.gv.height, st.gv.width, 3), "target", dev)
+    _check_operand(metrics_out, (_native.EVAL_METRICS,), "metrics_out", dev)
+    ws = torch.empty((int(L.gr_eval_ws_bytes(ctypes.byref(st.gv))),), dtype=torch.uint8, device=dev)
+    _native.check(L.gr_eval_view(ctypes.byref(st.gv), _native.ptr(st.saved), _native.ptr(target), _native.ptr(metrics_out),
+                                 _native.ptr(ws), ws.numel(), _stream(dev)), "gr_eval_view")
+
+
 def _grad_background(st: RenderState, background: torch.Tensor, g_out: torch.Tensor) -> torch.Tensor:
     """d(out)/d(bg) = sum_p g_out * [0<=out_r<=1] / (1+W)  (torch_renderer.py:194-196)."""
     HW = st.gv.width * st.gv.height
@@ -1225,5 +1239,5 @@ def render_gaussians_torch(
 __all__ = ["Camera", "get_default_device", "perspective", "look_at", "render_gaussians_torch", "rasterize",
            "make_view", "prepare_view", "prepare_native", "Prepared", "forward_native", "backward_native",
            "backward_l1_native", "backward_fit_native", "backward_fit_gather_native", "forward_l1_native", "backward_splat_native", "reduce_views_native",
-           "gather_view_native", "reduce_sums_native", "density_stats_native",
+           "gather_view_native", "reduce_sums_native", "density_stats_native", "eval_view_native",
            "DEFAULT_CUTOFF", "DEPTH_GRAD_CUTOFF", "DEFAULT_CORE_CUTOFF", "FIT_CUTOFF", "default_cutoff"]

@@ -451,6 +451,35 @@ gr_status gr_fit_views_ssim(gr_executor* executor, const gr_fit_config* config, 
  * the calls exactly as before.  Bit-identical to fit_multiview.py's Python schedule with density_stats. */
 gr_status gr_executor_density_stats(gr_executor* executor, float* const* stats_per_stream);
 
+/* View metrics for held-out evaluation (an extension: the reference fit loop reports its training loss only): of a
+ * rendered view against a target image, over all H*W*3 values,
+ *   metrics[0] = mean|x - y|,  metrics[1] = mean (x - y)^2,  metrics[2] = mean SSIM(x, y)  (the SSIM of gr_ssim_fwd),
+ * x the rendered colour clamp((bg + C) / (1 + W)) formed from the saved sums of gr_fwd_render / gr_fwd_render_saved
+ * (background / background_dev of the view honoured), y = target_rgb ((H,W,3) float32 device).  No image is read or
+ * written: one launch per 16 x 16 tile stages both windows as the fused D-SSIM forward does and writes three float
+ * partial sums into ws, one single-block launch sums them in double and writes the three means (device floats).
+ * metrics[2] is 1 - gr_ssim_fwd(image, target) bit for bit, the image being gr_fwd_render's of the same view.
+ *   - the view: 16-pixel tiles, whole (tile = 32, rows > 0: GR_ERR_INVALID_ARGUMENT), within gr_ssim_fwd's limits
+ *   - null pointers: GR_ERR_INVALID_ARGUMENT; ws shorter than gr_eval_ws_bytes: GR_ERR_WORKSPACE (nothing is launched)
+ *   - stream-ordered, no allocation, no atomics, deterministic */
+#define GR_EVAL_METRICS 3 /* mean|x-y|, mean (x-y)^2, mean SSIM, over all H*W*3 values */
+size_t gr_eval_ws_bytes(const gr_view* v);
+gr_status gr_eval_view(const gr_view* v, const float* saved, const float* target_rgb,
+                       float* metrics /* device, GR_EVAL_METRICS floats */, void* ws, size_t ws_bytes, void* stream);
+/* gr_eval_view over several views of the same Gaussians: the per-view schedule of gr_fit_views without a backward.
+ * Preparations ahead on the preparation stream (prep_group, prep_first, prep_ahead), view j on render stream
+ * j % num_streams: gr_fwd_render keeping the saved sums only (no images, no depth output; the views are passed with
+ * no_depth_grad = 1), then gr_eval_view into metrics[j] (device, [num_views][GR_EVAL_METRICS]).  reduce_batch,
+ * reduce_tail, target_mask and target_depth are ignored; config->caps must be NULL (the plans are read on the host).
+ * Workspaces (the saved sums and the metrics' partial sums per stream among them) are the executor's own, reused in
+ * stream order; the accumulators, the density statistics and every other piece of the executor's state are left
+ * untouched.  Ordered after and before `stream` as gr_fit_views; n == 0 or num_views == 0: no-op.  Deterministic;
+ * bit-identical to per-view gr_fwd_render + gr_eval_view calls. */
+gr_status gr_eval_views(gr_executor* executor, const gr_fit_config* config, int num_views,
+                        const gr_fit_target* views, int n, const float* means, const float* scales,
+                        const float* colors, int color_dim, const float* opacities,
+                        float* metrics /* device [num_views][GR_EVAL_METRICS] */, void* stream);
+
 /* ------------------------------------------------------------------------------------------ */
 /* Legacy uint8 surface (host pointers), replaces gr::render_gaussians (renderer.h:33-39).    */
 /* Semantics of renderer_cpu.cpp: 3-sigma box, w < 1e-5 skip, uint8 round-half-up, A = 255.  */
