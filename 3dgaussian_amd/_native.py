@@ -213,6 +213,10 @@ _SIG = {
     "gr_density_stats": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(GrSumsView), ctypes.c_int, _P, _P, _P,
                                         ctypes.c_float, _P, _P]),
     "gr_executor_density_stats": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_void_p)]),
+    "gr_camera_grads_ws_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    "gr_camera_grads_sums": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(GrSumsView), ctypes.c_int, _P, _P, _P,
+                                            ctypes.c_int, _P, ctypes.POINTER(ctypes.c_void_p), _P, ctypes.c_size_t, _P]),
+    "gr_executor_camera_grads": (ctypes.c_int, [_P, _P]),
     "gr_executor_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
     "gr_executor_destroy": (None, [_P]),
     "gr_fit_views": (ctypes.c_int, [_P, ctypes.POINTER(GrFitConfig), ctypes.c_int, ctypes.POINTER(GrFitTarget), ctypes.c_int,

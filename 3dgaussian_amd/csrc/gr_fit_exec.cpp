@@ -7,7 +7,7 @@
 // (the small-view configs and the per-rank share of a multi-GPU step are host-bound in Python).
 //
 // Only the public C ABI (gr_fwd_prepare_views_async, gr_fwd_render_l1, gr_bwd_splat, gr_gather_view,
-// gr_reduce_sums, gr_density_stats, gr_fwd_render, gr_bwd_fit_gather, gr_bwd_fit_ssim_gather) and the HIP runtime are used.
+// gr_reduce_sums, gr_density_stats, gr_camera_grads_sums, gr_fwd_render, gr_bwd_fit_gather, gr_bwd_fit_ssim_gather) and the HIP runtime are used.
 // Workspaces are the executor's own, kept across steps and reused only in stream order: each render stream owns its view workspace
 // (bins, forward scratch, backward workspace, saved sums) and a ring of per-view sums for its reduction
 // batch; the geoms are a ring of slots written on the preparation stream, a slot being rewritten only
@@ -83,6 +83,7 @@ struct Buf {
 struct StreamWs {  // one render stream's buffers
   Buf bins, scratch, ws, saved;
   Buf eval;                      // gr_eval_views: the view metrics' partial sums
+  Buf cam;                       // gr_executor_camera_grads: a batch's camera-gradient partials
   std::vector<Buf> sums, sums3;  // one per view of a reduction batch (sums3: the depth-loss path's depth sums)
 };
 
@@ -105,6 +106,7 @@ struct gr_executor {
   std::vector<GeomSlot> geoms;     // ring of geom slots
   std::vector<hipStream_t> last;   // the previous call's render streams 1.. and preparation stream
   float* const* stats = nullptr;   // gr_executor_density_stats: one [n][2] buffer per render stream, or none
+  float* cams = nullptr;           // gr_executor_camera_grads: [num_views][GR_CAMERA_GRADS] rows (view j -> row j), or none
 };
 
 #define GR_EXEC_TRY(expr)                                                            \
@@ -164,6 +166,7 @@ void gr_executor_destroy(gr_executor* ex) {
     w.ws.release();
     w.saved.release();
     w.eval.release();
+    w.cam.release();
     for (auto& b : w.sums) b.release();
     for (auto& b : w.sums3) b.release();
   }
@@ -212,6 +215,12 @@ static gr_status fit_views_checked(gr_executor* ex, const gr_fit_config* cfg, in
 gr_status gr_executor_density_stats(gr_executor* ex, float* const* stats_per_stream) {
   if (!ex) return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, "gr_executor_density_stats: null executor");
   ex->stats = stats_per_stream;
+  return GR_OK;
+}
+
+gr_status gr_executor_camera_grads(gr_executor* ex, float* d_cameras) {
+  if (!ex) return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, "gr_executor_camera_grads: null executor");
+  ex->cams = d_cameras;
   return GR_OK;
 }
 
@@ -392,6 +401,7 @@ static gr_status enqueue_views(gr_executor* ex, const gr_fit_config* cfg, int nu
   };
 
   struct Pending {
+    int j;  // the view's index in the call (its camera-gradient row)
     gr_view view;
     float* sums;
     float* sums3;  // depth sums (depth-loss path) or null
@@ -416,6 +426,13 @@ static gr_status enqueue_views(gr_executor* ex, const gr_fit_config* cfg, int nu
                                 acc[4 * k + 2], acc[4 * k + 3], started[k], st[k]));
     if (ex->stats)  // the batch's density statistics beside its chain rule (gr_executor_density_stats)
       GR_EXEC_CALL(gr_density_stats(nb, b, n, means, scales, opacities, 1.0f / g_scale, ex->stats[k], st[k]));
+    if (ex->cams && !metrics) {  // the batch's camera gradients, view j into row j (gr_executor_camera_grads)
+      float* rows[GR_REDUCE_MAX_VIEWS];
+      for (int q = 0; q < nb; ++q) rows[q] = ex->cams + (size_t)GR_CAMERA_GRADS * pending[k][q].j;
+      Buf& cw = ex->ws[k].cam;
+      GR_EXEC_TRY(cw.fit(gr_camera_grads_ws_bytes(n, nb), st[k]));
+      GR_EXEC_CALL(gr_camera_grads_sums(nb, b, n, means, scales, colors, color_dim, opacities, rows, cw.p, cw.cap, st[k]));
+    }
     pending[k].clear();
     started[k] = 1;
     return GR_OK;
@@ -463,7 +480,7 @@ static gr_status enqueue_views(gr_executor* ex, const gr_fit_config* cfg, int nu
       GR_EXEC_CALL(gr_bwd_fit_ssim_gather(&v, n, &plan, geom[j], bins, (const float*)W.saved.p, views[j].target_rgb,
                                           views[j].target_mask, w_sil, views[j].target_depth, w_depth, g_scale, w_dssim,
                                           losses + j, ws, W.ws.cap, (float*)sb.p, p3, s));
-      pending[k].push_back({v, (float*)sb.p, p3});
+      pending[k].push_back({j, v, (float*)sb.p, p3});
     } else if (!depth) {
       GR_EXEC_CALL(gr_fwd_render_l1(&v, n, &plan, geom[j], bins, W.bins.cap, scratch, W.scratch.cap, views[j].target_rgb,
                                     views[j].target_mask, w_sil, g_scale, losses + j, nullptr, nullptr, ws, W.ws.cap, s));
@@ -471,7 +488,7 @@ static gr_status enqueue_views(gr_executor* ex, const gr_fit_config* cfg, int nu
       Buf& sb = W.sums[pending[k].size()];
       GR_EXEC_TRY(sb.fit(sums_bytes, s));
       GR_EXEC_CALL(gr_gather_view(&v, n, &plan, geom[j], bins, ws, (float*)sb.p, s));
-      pending[k].push_back({v, (float*)sb.p, nullptr});
+      pending[k].push_back({j, v, (float*)sb.p, nullptr});
     } else {
       GR_EXEC_TRY(W.saved.fit(gr_saved_floats(&v) * sizeof(float), s));
       GR_EXEC_CALL(gr_fwd_render(&v, n, &plan, geom[j], bins, W.bins.cap, scratch, W.scratch.cap, nullptr, nullptr,
@@ -483,7 +500,7 @@ static gr_status enqueue_views(gr_executor* ex, const gr_fit_config* cfg, int nu
       GR_EXEC_CALL(gr_bwd_fit_gather(&v, n, &plan, geom[j], bins, (const float*)W.saved.p, views[j].target_rgb,
                                      views[j].target_mask, w_sil, views[j].target_depth, w_depth, g_scale, losses + j, ws,
                                      W.ws.cap, (float*)sb.p, (float*)s3.p, s));
-      pending[k].push_back({v, (float*)sb.p, (float*)s3.p});
+      pending[k].push_back({j, v, (float*)sb.p, (float*)s3.p});
     }
     // the geom slot may be refilled once this stream has passed its last reader
     GeomSlot& gsl = ex->geoms[slot_of[j]];

@@ -4291,6 +4291,94 @@ __global__ __launch_bounds__(64) void k_camera_final(const double* __restrict__ 
   if (lane == 0) out[q] = (float)s;
 }
 
+// Camera gradients of a batch of gathered views (gr_camera_grads_sums: the fit's pose refinement).  One lane per
+// Gaussian, its parameters loaded once for the batch, then the views in batch order: per view k_camera_grad's
+// terms from the view's sums row (k_reduce_sums' unpacking and `on` test; a row that is all zero adds nothing),
+// its block reduction (wave butterfly in double, then the four waves in order) and the block's partial to
+// part[view][block][CAM_GRADS].  The LDS rows alternate between two sets, so one barrier per view orders them.  A
+// view's partials depend on nothing but that view: its row is the same bits whatever shares the batch.
+template <int CD>
+__global__ __launch_bounds__(256) void k_camera_grad_views(SBatch B, int n, const float* __restrict__ means,
+                                                           const float* __restrict__ scales,
+                                                           const float* __restrict__ colors,
+                                                           const float* __restrict__ opac, double* __restrict__ part) {
+  __shared__ double sh[2][4][CAM_GRADS];
+  const int i = blockIdx.x * 256 + (int)threadIdx.x;
+  const int w = (int)threadIdx.x >> 6;
+  const bool live = i < n;
+  float mx = 0.f, my = 0.f, mz = 0.f, s0 = 0.f, s1 = 0.f, op = 0.f;
+  if (live) {
+    mx = means[3 * (size_t)i], my = means[3 * (size_t)i + 1], mz = means[3 * (size_t)i + 2];
+    s0 = scales[3 * (size_t)i], s1 = scales[3 * (size_t)i + 1];
+    op = opac[i];
+  }
+  for (int vi = 0; vi < B.nv; ++vi) {
+    double acc[CAM_GRADS];
+#pragma unroll
+    for (int q = 0; q < CAM_GRADS; ++q) acc[q] = 0.0;
+    if (live) {
+      const float4 a = B.r[vi].sums[2 * (size_t)i], b = B.r[vi].sums[2 * (size_t)i + 1];
+      const float s3 = B.r[vi].sums3 ? B.r[vi].sums3[i] : 0.0f;
+      const float S[NPART] = {a.x, b.x, a.y, s3, a.z, b.z, a.w, b.w, b.y};
+      const bool on = a.x != 0.f || a.y != 0.f || a.z != 0.f || a.w != 0.f || b.x != 0.f || b.y != 0.f || b.z != 0.f ||
+                      b.w != 0.f || s3 != 0.f;
+      if (on) {
+        const ViewK& v = B.r[vi].v;
+        Proj p;
+        project(v, mx, my, mz, s0, s1, p);
+        ProjGrad<float> pg;
+        proj_grads<float>(v, p, op < 0.0f ? 0.0f : op, S, pg);
+        const float mh[4] = {mx, my, mz, 1.0f};
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            acc[r * 4 + j] = (double)pg.dpc[r] * (double)mh[j];
+            acc[16 + r * 4 + j] = (double)pg.dclip[r] * (double)p.pc[j];
+          }
+        const float sg0 = v.P[0] > 0.f ? 1.f : (v.P[0] < 0.f ? -1.f : 0.f);
+        const float sg5 = v.P[5] > 0.f ? 1.f : (v.P[5] < 0.f ? -1.f : 0.f);
+        acc[16 + 0] += (double)(pg.dsx * (fabsf(s0) * 0.5f * (float)v.W / p.za) * sg0);
+        acc[16 + 5] += (double)(pg.dsy * (fabsf(s1) * 0.5f * (float)v.H / p.za) * sg5);
+        if constexpr (CD != 3) {
+          ColGrad<CD, float> cg;
+          color_grads<CD, float>(v, mx, my, mz, colors + (size_t)CD * i, S, cg);
+#pragma unroll
+          for (int j = 0; j < 3; ++j) acc[32 + j] = (double)cg.dd[j];
+        }
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < CAM_GRADS; ++q)
+#pragma unroll
+      for (int m = 32; m >= 1; m >>= 1) acc[q] += __shfl_xor(acc[q], m);
+    double(*row)[CAM_GRADS] = sh[vi & 1];
+    if ((threadIdx.x & 63) == 0)
+#pragma unroll
+      for (int q = 0; q < CAM_GRADS; ++q) row[w][q] = acc[q];
+    __syncthreads();
+    if ((int)threadIdx.x < CAM_GRADS) {
+      const int q = threadIdx.x;
+      part[((size_t)vi * gridDim.x + blockIdx.x) * CAM_GRADS + q] = ((row[0][q] + row[1][q]) + row[2][q]) + row[3][q];
+    }
+  }
+}
+
+// k_camera_final over a (component, view) grid: block (q, vi) sums component q of view vi over the blocks in
+// k_camera_final's order and writes the view's own output row.
+struct CamRows {
+  float* out[GR_REDUCE_MAX_VIEWS];
+};
+__global__ __launch_bounds__(64) void k_camera_final_views(const double* __restrict__ part, int blocks, CamRows rows) {
+  const int q = blockIdx.x, vi = blockIdx.y, lane = threadIdx.x;
+  const double* p = part + (size_t)vi * blocks * CAM_GRADS;
+  double s = 0.0;
+  for (int b = lane; b < blocks; b += 64) s += p[(size_t)b * CAM_GRADS + q];
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m);
+  if (lane == 0) rows.out[vi][q] = (float)s;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Legacy uint8 surface (renderer_cpu.cpp:34-260 semantics).
 // ------------------------------------------------------------------------------------------------
@@ -6482,6 +6570,58 @@ gr_status gr_density_stats(int num_views, const gr_sums_view* views, int n, cons
   if (B.nv == 0) return GR_OK;
   hipLaunchKernelGGL(k_density_stats, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, B, n, means, scales,
                      opacities, inv_g_scale, (float2*)stats);
+  GR_HIP_TRY(hipGetLastError());
+  return GR_OK;
+}
+
+size_t gr_camera_grads_ws_bytes(int n, int num_views) {
+  if (n <= 0 || num_views <= 0) return 0;
+  return (size_t)num_views * (size_t)blocks_for(n) * CAM_GRADS * sizeof(double);
+}
+
+gr_status gr_camera_grads_sums(int num_views, const gr_sums_view* views, int n, const float* means, const float* scales,
+                               const float* colors, int color_dim, const float* opacities, float* const* d_camera,
+                               void* ws, size_t ws_bytes, void* stream) {
+  if (num_views < 1 || num_views > GR_REDUCE_MAX_VIEWS)
+    return set_error(GR_ERR_INVALID_ARGUMENT, "gr_camera_grads_sums: num_views must be in [1, GR_REDUCE_MAX_VIEWS]");
+  if (color_dim != 3 && color_dim != 12 && color_dim != 48)
+    return set_error(GR_ERR_INVALID_ARGUMENT, "colors must be (N,3) or SH coeffs (N,4,3) / (N,16,3)");
+  if (n < 0) return set_error(GR_ERR_INVALID_ARGUMENT, "n must be >= 0");
+  if (!d_camera) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_camera_grads_sums: null output rows");
+  for (int k = 0; k < num_views; ++k)
+    if (!d_camera[k]) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_camera_grads_sums: null output row");
+  hipStream_t s = (hipStream_t)stream;
+  if (n == 0) {  // no Gaussian: every term is zero
+    for (int k = 0; k < num_views; ++k) GR_HIP_TRY(hipMemsetAsync(d_camera[k], 0, CAM_GRADS * sizeof(float), s));
+    return GR_OK;
+  }
+  if (!views || !means || !scales || !colors || !opacities || !ws)
+    return set_error(GR_ERR_INVALID_ARGUMENT, "gr_camera_grads_sums: null pointer");
+  SBatch B;
+  CamRows rows;
+  B.nv = num_views;
+  for (int k = 0; k < num_views; ++k) {
+    gr_status st = check_view(&views[k].view);
+    if (st != GR_OK) return st;
+    if (!views[k].sums) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_camera_grads_sums: null sums");
+    B.r[k].v = make_viewk(&views[k].view);
+    B.r[k].sums = (const float4*)views[k].sums;
+    B.r[k].sums3 = views[k].sums3;
+    rows.out[k] = d_camera[k];
+  }
+  for (int k = num_views; k < GR_REDUCE_MAX_VIEWS; ++k) rows.out[k] = nullptr;
+  if (ws_bytes < gr_camera_grads_ws_bytes(n, num_views))
+    return set_error(GR_ERR_WORKSPACE, "gr_camera_grads_sums: workspace too small");
+  const int blocks = blocks_for(n);
+  double* part = (double*)ws;
+  if (color_dim == 3)
+    hipLaunchKernelGGL(k_camera_grad_views<3>, dim3(blocks), dim3(256), 0, s, B, n, means, scales, colors, opacities, part);
+  else if (color_dim == 12)
+    hipLaunchKernelGGL(k_camera_grad_views<12>, dim3(blocks), dim3(256), 0, s, B, n, means, scales, colors, opacities, part);
+  else
+    hipLaunchKernelGGL(k_camera_grad_views<48>, dim3(blocks), dim3(256), 0, s, B, n, means, scales, colors, opacities, part);
+  GR_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_camera_final_views, dim3(CAM_GRADS, num_views), dim3(64), 0, s, (const double*)part, blocks, rows);
   GR_HIP_TRY(hipGetLastError());
   return GR_OK;
 }

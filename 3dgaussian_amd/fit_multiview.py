@@ -412,6 +412,32 @@ def hip_render(means, scales, colors, opacities, cam, width, height, background,
                                      prepared=prepared, depth_grad=depth_grad)
 
 
+def pose_view(xi: torch.Tensor, view0: torch.Tensor) -> torch.Tensor:
+    """The view matrix of a camera whose pose is refined: ``E(xi) @ view0`` with ``xi = (omega, tau)`` (6 values),
+    ``E = [[R(omega), tau], [0, 1]]`` and R the rotation-vector exponential (Rodrigues), a left perturbation in the
+    camera's frame.  Plain differentiable torch; leading batch dimensions pass through (xi (..., 6), view0 (..., 4, 4)).
+    ``E(0) = I`` exactly (so ``pose_view(0, V) == V`` bit for bit), the Jacobian at 0 is the six generators of se(3),
+    and view0's last row is kept."""
+    xi = xi.to(view0.dtype)
+    w, tau = xi[..., :3], xi[..., 3:6]
+    t2 = (w * w).sum(-1)
+    small = t2 < 1e-12
+    t2s = torch.where(small, torch.ones_like(t2), t2)  # (no sqrt at 0: its derivative is not finite)
+    th = torch.sqrt(t2s)
+    a = torch.where(small, 1.0 - t2 / 6.0, torch.sin(th) / th)
+    b = torch.where(small, 0.5 - t2 / 24.0, 2.0 * torch.sin(0.5 * th) ** 2 / t2s)
+    z = torch.zeros_like(t2)
+    K = torch.stack([torch.stack([z, -w[..., 2], w[..., 1]], -1), torch.stack([w[..., 2], z, -w[..., 0]], -1),
+                     torch.stack([-w[..., 1], w[..., 0], z], -1)], -2)
+    eye = torch.eye(3, dtype=view0.dtype, device=view0.device)
+    KK = w[..., :, None] * w[..., None, :] - t2[..., None, None] * eye  # K @ K
+    E = torch.cat([eye + a[..., None, None] * K + b[..., None, None] * KK, tau[..., None]], dim=-1)
+    # the product term by term (element-wise operations only: the same bits for one view or a batch, on every rank)
+    top = (E[..., :, 0:1] * view0[..., 0:1, :] + E[..., :, 1:2] * view0[..., 1:2, :] + E[..., :, 2:3] * view0[..., 2:3, :]
+           + E[..., :, 3:4] * view0[..., 3:4, :])
+    return torch.cat([top, view0[..., 3:4, :]], dim=-2)
+
+
 class _EagerReplay:
     """GR_GRAPH=sized: replay() enqueues the device-sized step again instead of launching a captured graph."""
 
@@ -446,7 +472,8 @@ class ViewShardedFitter:
                  masks: Optional[list] = None, depths: Optional[list] = None, silhouette_weight: float = 0.2,
                  depth_weight: float = 0.05, reg_opacity: float = 1e-3, reg_scale: float = 1e-3,
                  render_fn: RenderFn = hip_render, group=None, reorder: bool = True, dssim_weight: float = 0.0,
-                 dssim_fused: bool = False, density_stats: bool = False):
+                 dssim_fused: bool = False, density_stats: bool = False, refine_cameras: bool = False,
+                 camera_lr: float = 1e-3, camera_fixed: tuple = (0,)):
         # dssim_weight l > 0: a view's photometric term is (1 - l) mean|pred - tgt| + l dssim(pred, tgt)
         # (losses.dssim_loss) on the per-view autograd path; 0 (default): the L1 fit, every path as it was
         # dssim_fused (with l > 0, the HIP render op): the fused path's D-SSIM form (_views_direct_ssim or the native
@@ -454,6 +481,9 @@ class ViewShardedFitter:
         # density_stats: accumulate every Gaussian's screen-space positional gradient over the views that see it
         # (density_state; what densify_and_prune(mode="gradient") reads): on the HIP device from the fused paths only
         # (gr_density_stats beside every gr_reduce_sums), on other devices from cpu_renderer's position gradients
+        # refine_cameras: the views' poses are fitted with the Gaussians (pose_view: a 6-vector per view, an Adam of its
+        # own at camera_lr; the views of camera_fixed keep their poses, which pins the scene's gauge): on the HIP device's
+        # fused paths from gr_camera_grads_sums beside every gr_reduce_sums, elsewhere through autograd
         # reorder: keep the Gaussians in spatial (Morton) order, re-established after every
         # densify/prune (spatial_order); off only to compare with an unpermuted run
         # perm: self.params[k][i] = canonical[k][perm[i]], the canonical order being the stub's (the
@@ -498,6 +528,21 @@ class ViewShardedFitter:
         self._stats = []  # one (n, 2) buffer per render stream: [sum of gradient norms, seeing views]
         if self.density_stats and dev.type == "cuda":
             self._density_check(dev)
+        self.refine_cameras = bool(refine_cameras)
+        if self.refine_cameras:
+            V = len(cams)
+            self.camera_lr = float(camera_lr)
+            self.camera_fixed = tuple(sorted({int(i) for i in camera_fixed}))
+            if any(not 0 <= i < V for i in self.camera_fixed):
+                raise ValueError(f"camera_fixed {camera_fixed}: view indices must be in [0, {V})")
+            self.cams = list(cams)  # (the refined cameras replace their entries: the caller's list stays as it is)
+            self._view0 = torch.stack([c.view.detach().to(device="cpu", dtype=torch.float64) for c in cams])  # (V, 4, 4)
+            self._xi = torch.zeros((V, 6), dtype=torch.float64)
+            self._xi_grad = torch.zeros((V, 6), dtype=torch.float64)
+            self._cam_opt = torch.optim.Adam([self._xi], lr=self.camera_lr)
+            self._cam_host = {}  # view -> its (view, proj) as host float32 arrays (what the gr_views are built from)
+            self._cam_rows = None  # the fused paths' per-step (len(my_views), 35) camera-gradient rows
+            self._cam_params = {}  # the autograd path's pose leaves of this step
 
     def canonical_params(self) -> dict:
         """The parameters in the stub's order (undoes the trainer's Morton permutation)."""
@@ -600,6 +645,130 @@ class ViewShardedFitter:
             c[self.perm] = tot
             tot = c
         return tot[:, 0].contiguous(), tot[:, 1].contiguous()
+
+    # ---- camera pose refinement (refine_cameras=True) -----------------------------------------------------------
+    def _cam_mats(self, i: int):
+        """(view, proj) of view i as make_view takes them: while refining, host arrays kept with the refined poses (no
+        device read per rebuilt gr_view); otherwise the camera's own tensors."""
+        if not self.refine_cameras:
+            return self.cams[i].view, self.cams[i].proj
+        hit = self._cam_host.get(i)
+        if hit is None:
+            cam = self.cams[i]
+            hit = self._cam_host[i] = (cam.view.detach().float().cpu().numpy().copy(),
+                                       cam.proj.detach().float().cpu().numpy().copy())
+        return hit
+
+    def _camera_rows(self, count: int, device) -> torch.Tensor:
+        """This step's camera-gradient rows, one per (virtual) view id of my_views, kept across steps."""
+        r = self._cam_rows
+        if r is None or r.shape[0] != max(1, count) or r.device != device:
+            self._cam_rows = r = torch.zeros((max(1, count), tr._native.CAMERA_GRADS), dtype=torch.float32, device=device)
+        return r
+
+    def _camera_ws(self, k: int, n: int, device) -> torch.Tensor:
+        """Render stream k's gr_camera_grads_sums workspace (reused in stream order)."""
+        ws = self.__dict__.setdefault("_cam_ws", {})
+        need = max(8, int(tr._native.lib().gr_camera_grads_ws_bytes(n, tr._native.REDUCE_MAX_VIEWS)))
+        t = ws.get(k)
+        if t is None or t.numel() < need or t.device != device:
+            ws[k] = t = torch.empty((need,), dtype=torch.uint8, device=device)
+        return t
+
+    def _camera_grads_batch(self, m, s, c, o, batch, js, k: int) -> None:
+        """gr_camera_grads_sums of a reduction batch on the current stream: batch entry q is view js[q] of my_views."""
+        rows = self._camera_rows(len(self.my_views), m.device)
+        tr.camera_grads_sums_native(m, s, c, o, batch, [rows[j] for j in js], ws=self._camera_ws(k, int(m.shape[0]), m.device))
+
+    def _camera_step_fused(self, device) -> None:
+        """After a fused step's streams joined: the rows of this rank's (virtual) views added per real view in my_views'
+        order (a view's bands add up), summed over the ranks, and the pose update on the host."""
+        V = len(self.targets)
+        views = self.my_views
+        tot = torch.zeros((V, tr._native.CAMERA_GRADS), dtype=torch.float32, device=device)
+        if views:
+            rows = self._camera_rows(len(views), device)
+            for j, i in enumerate(views):
+                tot[self._vi(i)] += rows[j]
+        if self.world > 1:
+            dist.all_reduce(tot, group=self.group)
+        if device.type == "cuda":
+            pin = self.__dict__.get("_cam_pin")
+            if pin is None or pin.shape != tot.shape:
+                self._cam_pin = pin = torch.empty(tot.shape, dtype=torch.float32, pin_memory=True)
+            pin.copy_(tot, non_blocking=True)
+            torch.cuda.current_stream(device).synchronize()
+            tot = pin
+        self._camera_update(self._camera_xi_grad(tot))
+
+    def _camera_xi_grad(self, rows: torch.Tensor) -> torch.Tensor:
+        """(V, 35) host rows (gr_bwd_camera's layout, one per view) -> d loss / d xi (V, 6) float64: d view completed
+        with the camera centre's term (torch_renderer._camera_grads), then the vector-Jacobian product through
+        pose_view, all views in one pass."""
+        sh = "colors_raw" not in self.params
+        dview = torch.stack([tr._camera_grads(rows[i], torch.from_numpy(self._cam_mats(i)[0]), None,
+                                              True, False, sh)[0].double() for i in range(rows.shape[0])])
+        xi = self._xi.detach().clone().requires_grad_(True)
+        (g,) = torch.autograd.grad((pose_view(xi, self._view0) * dview).sum(), xi)
+        return g
+
+    def _camera_leaf(self, i: int, device):
+        """The autograd path: view i's camera with its view matrix a function of a pose leaf of this step."""
+        xi = self._xi[i].detach().clone().requires_grad_(True)
+        self._cam_params[i] = xi
+        view = pose_view(xi, self._view0[i]).to(device=device, dtype=self.cams[i].view.dtype)
+        return tr.Camera(view=view, proj=self.cams[i].proj)
+
+    def _camera_step_autograd(self) -> None:
+        """After the autograd path's backward: d loss / d xi of this rank's views, summed over the ranks, the update."""
+        V = len(self.targets)
+        g = torch.zeros((V, 6), dtype=torch.float64)
+        for i, xi in self._cam_params.items():
+            if xi.grad is not None:
+                g[i] = xi.grad
+        self._cam_params = {}
+        if self.world > 1:
+            dev = self.params["means"].device
+            t = g.to(dev)
+            dist.all_reduce(t, group=self.group)
+            g = t.cpu()
+        self._camera_update(g)
+
+    def _camera_update(self, g: torch.Tensor) -> None:
+        """Adam on the pose deltas from the all-reduced d loss / d xi (every rank the same arithmetic on the same
+        numbers), the rows of camera_fixed left alone; then the cameras and everything built from their matrices."""
+        for i in self.camera_fixed:
+            g[i] = 0.0
+        self._xi_grad = g.clone()
+        self._xi.grad = g
+        self._cam_opt.step()
+        self._xi.grad = None
+        with torch.no_grad():
+            dev = self.params["means"].device
+            v32 = pose_view(self._xi, self._view0).to(torch.float32)  # formed in float64, rounded once
+            vdev = v32.to(dev)  # (one copy; the cameras' views are its rows)
+            vnp = v32.numpy()
+            for i, cam in enumerate(self.cams):
+                if i in self.camera_fixed:  # (a gradient that is always zero: Adam leaves the row at zero)
+                    continue
+                self.cams[i] = tr.Camera(view=vdev[i].to(cam.view.dtype), proj=cam.proj)
+                if i in self._cam_host:
+                    self._cam_host[i] = (vnp[i], self._cam_host[i][1])
+        # the gr_views that hold the matrices are rebuilt on their next use (band cuts keep their refresh points)
+        for name in ("_gv_cache", "_band_gv", "_gvd_cache", "_gvs_cache", "_native_targets", "_eval_gv"):
+            self.__dict__.pop(name, None)
+
+    def refined_cameras(self) -> list:
+        """The cameras at their current poses, in the fitter's view order."""
+        self.graph_sync()
+        return list(self.cams)
+
+    def camera_state(self) -> tuple:
+        """(xi, d loss / d xi of the last step), both (V, 6) float64 on the host: the pose deltas (pose_view) and the
+        gradient the last update used (rows of camera_fixed zero)."""
+        if not self.refine_cameras:
+            raise ValueError("camera_state: the fitter was made without refine_cameras")
+        return self._xi.detach().clone(), self._xi_grad.clone()
 
     def _background(self, device) -> torch.Tensor:
         # one persistent tensor: the renderer reads its value on the host once, not per view
@@ -790,8 +959,7 @@ class ViewShardedFitter:
             self._gv_cache = cache = {}
         gv = cache.get((i, F32_GRADE, FIT_TILE))
         if gv is None:
-            cam = self.cams[i]
-            gv = cache[(i, F32_GRADE, FIT_TILE)] = tr.make_view(cam.view, cam.proj, self.width, self.height,
+            gv = cache[(i, F32_GRADE, FIT_TILE)] = tr.make_view(*self._cam_mats(i), self.width, self.height,
                                                       self._background(device), cutoff=tr.FIT_CUTOFF,
                                                       core_cutoff=tr.FIT_CUTOFF, depth_grad=False,
                                                       tile=0 if F32_GRADE else FIT_TILE)
@@ -814,7 +982,8 @@ class ViewShardedFitter:
             # without a depth loss the depth output gets no gradient: the forward may accumulate W and D
             # at the colours' precision (gr_view.no_depth_grad)
             kw["depth_grad"] = "eager" if self._depth_grad() else False  # a depth loss differentiates depth
-        pred, alpha, depth = self.render_fn(means, scales, colors, opacities, self.cams[i], self.width, self.height,
+        cam = self._camera_leaf(i, device) if self.refine_cameras and torch.is_grad_enabled() else self.cams[i]
+        pred, alpha, depth = self.render_fn(means, scales, colors, opacities, cam, self.width, self.height,
                                             self._background(device), **kw)
         use_sil = self.masks is not None and self.w_sil > 0.0
         if self.w_dssim > 0.0:
@@ -895,7 +1064,10 @@ class ViewShardedFitter:
                 loss = total / len(self.targets)
                 if reg is not None:
                     loss = loss + reg
-            return self._fused_param_step(scales, opacities, loss)
+            out = self._fused_param_step(scales, opacities, loss)
+            if self.refine_cameras:  # the next step renders with this update
+                self._camera_step_fused(device)
+            return out
         means, scales, colors, opacities = activations(self.params)
         if self._direct(device) and means.shape[0] > 0:
             if self._ssim_form():
@@ -920,7 +1092,10 @@ class ViewShardedFitter:
             else:
                 torch.autograd.backward([means, scales, colors, opacities], list(self._acc))
             self._acc = None
-            return self._finish_step(loss)
+            out = self._finish_step(loss)
+            if self.refine_cameras:
+                self._camera_step_fused(device)
+            return out
         # HIP renderer: the next view's preparation is enqueued before this view renders, so the
         # host reads each view's pair count while the device is still busy (no idle gap per view);
         # views rotate over NUM_STREAMS HIP streams, so one view's latency-bound binning kernels run
@@ -985,7 +1160,10 @@ class ViewShardedFitter:
         if self.rank == 0:
             loss = loss + self.reg_opacity * opacities.mean() + self.reg_scale * scales.mean()
         loss.backward()
-        return self._finish_step(loss)
+        out = self._finish_step(loss)
+        if self.refine_cameras:  # autograd delivered d loss / d xi through pose_view (view_loss)
+            self._camera_step_autograd()
+        return out
 
     def _native_exec(self) -> bool:
         """Whether this step's views go through the native executor (GR_NATIVE_EXEC)."""
@@ -1011,12 +1189,11 @@ class ViewShardedFitter:
             arr = (tr._native.GrFitTarget * len(views))()
             for j, i in enumerate(views):
                 if depth:
-                    cam = self.cams[i]
                     gvd = getattr(self, "_gvd_cache", None)
                     if gvd is None:
                         self._gvd_cache = gvd = {}
                     if i not in gvd:
-                        gvd[i] = tr.make_view(cam.view, cam.proj, self.width, self.height, self._background(device),
+                        gvd[i] = tr.make_view(*self._cam_mats(i), self.width, self.height, self._background(device),
                                               depth_grad=True)
                     arr[j].view = gvd[i] if sized is None else tr.sized_view(gvd[i])
                     arr[j].target_depth = self.depths[i].data_ptr()
@@ -1063,6 +1240,9 @@ class ViewShardedFitter:
         if self.density_stats:  # the executor enqueues gr_density_stats beside each gr_reduce_sums of this call
             sp = (ctypes.c_void_p * ns)(*[b.data_ptr() for b in self._stats_bufs(ns, device)])
             tr._native.check(L.gr_executor_density_stats(head[0], sp), "gr_executor_density_stats")
+        if self.refine_cameras:  # and gr_camera_grads_sums after it: view j of this call into row j
+            tr._native.check(L.gr_executor_camera_grads(head[0], tr._native.ptr(self._camera_rows(len(views), device))),
+                             "gr_executor_camera_grads")
         try:
             if ssim:
                 tr._native.check(L.gr_fit_views_ssim(*head, ctypes.c_float(self.w_dssim), *tail), "gr_fit_views_ssim")
@@ -1071,6 +1251,8 @@ class ViewShardedFitter:
         finally:
             if self.density_stats:  # (the executor is the device's: other fits use it without statistics)
                 L.gr_executor_density_stats(head[0], None)
+            if self.refine_cameras:
+                L.gr_executor_camera_grads(head[0], None)
         self._acc_parts = acc
         self._native_keep = (m, s, c, o)  # read by the executor's streams until the caller's stream passes them
         return losses_v.sum()
@@ -1105,6 +1287,8 @@ class ViewShardedFitter:
             self._direct_acc = cached = (shapes, [tuple(torch.empty_like(t) for t in (m, s, c, o)) for _ in streams])
         acc = cached[1]
         stats = self._stats_bufs(len(streams), device) if self.density_stats else None
+        if self.refine_cameras:  # (made on the main stream, before the render streams wait for it)
+            self._camera_rows(len(views), device)
         for st in streams[1:]:
             st.wait_stream(main)
         w_sil = self.w_sil if (self.masks is not None and self.w_sil > 0.0) else 0.0
@@ -1133,6 +1317,7 @@ class ViewShardedFitter:
                 m, s, c, o, [tr.sized_view(self._fit_view(views[q], device)) for q in js], [sized.caps[q] for q in js],
                 [sized.observed[q] for q in js], sized.ovf), prep)
         pending: list = [[] for _ in streams]  # per stream: (render state, partials) awaiting their reduction
+        pending_js: list = [[] for _ in streams]  # their positions in `views` (the camera-gradient rows)
         started = [False] * ns
         sizes = _batch_sizes(ns, len(views))
 
@@ -1143,10 +1328,16 @@ class ViewShardedFitter:
                         tr.reduce_sums_native(m, s, c, o, pending[k], acc[k], accumulate=started[k])
                         if stats is not None:
                             tr.density_stats_native(m, s, o, pending[k], self._inv_g_scale(), stats[k])
+                        if self.refine_cameras:
+                            self._camera_grads_batch(m, s, c, o, pending[k], pending_js[k], k)
                     else:
+                        if self.refine_cameras:
+                            raise ValueError("refine_cameras: the fused path's camera gradient reads the gathered sums "
+                                             "(GR_GATHER=0 has none)")
                         tr.reduce_views_native(m, s, c, o, pending[k], acc[k], accumulate=started[k])
                 started[k] = True
                 pending[k] = []
+                pending_js[k] = []
 
         for j, i in enumerate(views):
             k = j % ns
@@ -1167,6 +1358,7 @@ class ViewShardedFitter:
                     rs = ws = None
             if rs is not None:
                 pending[k].append((rs, ws))
+            pending_js[k].append(j)
             prepare_upto(j + PREP_AHEAD)
             if len(pending[k]) >= sizes[k][0]:
                 reduce_pending(k)
@@ -1196,8 +1388,7 @@ class ViewShardedFitter:
         cache = self.__dict__.setdefault("_gvs_cache", {})
         gv = cache.get((i, F32_GRADE))
         if gv is None:
-            cam = self.cams[i]
-            gv = cache[(i, F32_GRADE)] = tr.make_view(cam.view, cam.proj, self.width, self.height, self._background(device),
+            gv = cache[(i, F32_GRADE)] = tr.make_view(*self._cam_mats(i), self.width, self.height, self._background(device),
                                                       cutoff=tr.FIT_CUTOFF, core_cutoff=tr.FIT_CUTOFF, depth_grad=False)
             if F32_GRADE:
                 gv.no_depth_grad = 2
@@ -1232,6 +1423,8 @@ class ViewShardedFitter:
             self._direct_acc = cached = (shapes, [tuple(torch.empty_like(t) for t in (m, s, c, o)) for _ in streams])
         acc = cached[1]
         stats = self._stats_bufs(len(streams), device) if self.density_stats else None
+        if self.refine_cameras:  # (made on the main stream, before the render streams wait for it)
+            self._camera_rows(len(views), device)
         for st in streams[1:]:
             st.wait_stream(main)
         w_sil = self.w_sil if (self.masks is not None and self.w_sil > 0.0) else 0.0
@@ -1252,8 +1445,7 @@ class ViewShardedFitter:
             if ssim and not depth:
                 return self._ssim_view(i, device)
             if i not in cache:
-                cam = self.cams[i]
-                cache[i] = tr.make_view(cam.view, cam.proj, self.width, self.height, self._background(device),
+                cache[i] = tr.make_view(*self._cam_mats(i), self.width, self.height, self._background(device),
                                         depth_grad=True)
             return cache[i]
 
@@ -1267,6 +1459,7 @@ class ViewShardedFitter:
         # per view its render and the depth-loss backward up to the per-Gaussian sums (gr_bwd_fit_gather); per batch
         # of a stream's views one chain-rule pass (gr_reduce_sums with the depth sums), as _views_direct
         pending: list = [[] for _ in streams]
+        pending_js: list = [[] for _ in streams]  # their positions in `views` (the camera-gradient rows)
         started = [False] * ns
         sizes = _batch_sizes(ns, len(views))
 
@@ -1276,8 +1469,11 @@ class ViewShardedFitter:
                     tr.reduce_sums_native(m, s, c, o, pending[k], acc[k], accumulate=started[k])
                     if stats is not None:
                         tr.density_stats_native(m, s, o, pending[k], self._inv_g_scale(), stats[k])
+                    if self.refine_cameras:
+                        self._camera_grads_batch(m, s, c, o, pending[k], pending_js[k], k)
                 started[k] = True
                 pending[k] = []
+                pending_js[k] = []
 
         for j, i in enumerate(views):
             k = j % ns
@@ -1298,6 +1494,7 @@ class ViewShardedFitter:
                                                                 w_sil, self.depths[i], self.w_depth, g_scale,
                                                                 losses_v[j:j + 1])
                 pending[k].append((rs.gv, sums, sums3) if sums3 is not None else (rs.gv, sums))
+                pending_js[k].append(j)
                 rs = None
             prepare_upto(j + PREP_AHEAD)
             if len(pending[k]) >= sizes[k][0]:
@@ -1478,6 +1675,8 @@ class ViewShardedFitter:
         form: the batched and graph steps have none."""
         if self._ssim_form() or self.density_stats:  # (a replayed step that overflowed is redone: its statistics
             return False                             # would count twice, so a fit that collects them steps eagerly)
+        if self.refine_cameras:  # (captured launches carry the view matrices as kernel arguments)
+            return False
         mode = self._graph_mode()
         if not (mode != "0" and self.world == 1 and device.type == "cuda" and BIN_STREAM == "" and self._direct(device)
                 and self.params["means"].shape[0] > 0 and self._fused_step_ok()):
@@ -2083,6 +2282,15 @@ def main(argv=None) -> None:
                     help="M > 0: evaluate every M iterations and after the last (the held-out views, or without "
                          "--holdout_every the training views); 0 (default): once after the last iteration, and only "
                          "with --holdout_every")
+    ap.add_argument("--refine_cameras", action="store_true",
+                    help="fit the training views' poses with the Gaussians (a 6-vector per view, pose_view) and write "
+                         "cameras_refined.npz (the --camera_npz schema)")
+    ap.add_argument("--camera_lr", type=float, default=1e-3,
+                    help="with --refine_cameras: Adam's learning rate of the pose deltas (chosen on the CPU dense renderer "
+                         "at 64x48, not measured on the GPU or on real data)")
+    ap.add_argument("--camera_fix", default="0",
+                    help="with --refine_cameras: comma list of training-view indices whose poses stay as given (they pin "
+                         "the scene's frame), or 'none'")
     ap.add_argument("--device", default="", help="cpu: host tensors (cpu_renderer, gloo); default: the HIP device")
     args = ap.parse_args(argv)
 
@@ -2131,6 +2339,7 @@ def main(argv=None) -> None:
 
     all_cams = cams  # (the preview renders view 0 of all)
     hold = []
+    train = list(range(len(targets)))
     if args.holdout_every < 0 or args.eval_interval < 0:
         raise ValueError("--holdout_every and --eval_interval must not be negative")
     if args.holdout_every > 0:
@@ -2145,11 +2354,20 @@ def main(argv=None) -> None:
     do_eval = args.holdout_every > 0 or args.eval_interval > 0
     eval_log = [] if do_eval else None
 
+    refine = {}
+    if args.refine_cameras:
+        fix = args.camera_fix.strip().lower()
+        fixed = () if fix in ("none", "") else tuple(int(x) for x in fix.split(","))
+        refine = dict(refine_cameras=True, camera_lr=args.camera_lr, camera_fixed=fixed)
+        if rank == 0 and hold:
+            print(f"refine_cameras: the {len(hold)} held-out views keep their input poses; the held-out metrics are "
+                  "taken at those poses")
     params = build_params(args.num_gaussians, device, args.use_sh, args.sh_degree)
     fitter = ViewShardedFitter(params, cams, targets, args.width, args.height, lr=args.lr, masks=masks, depths=depths,
                                silhouette_weight=args.silhouette_weight, depth_weight=args.depth_weight,
                                reg_opacity=args.reg_opacity, reg_scale=args.reg_scale, dssim_weight=args.dssim_weight,
-                               dssim_fused=args.dssim_fused, density_stats=args.densify_mode == "gradient")
+                               dssim_fused=args.dssim_fused, density_stats=args.densify_mode == "gradient",
+                               **refine)
     centres = torch.stack([torch.linalg.inv(c.view.detach().float().cpu())[:3, 3] for c in cams])
     extent = 1.1 * float((centres - centres.mean(dim=0)).norm(dim=1).max())
     loss_log = []
@@ -2185,6 +2403,10 @@ def main(argv=None) -> None:
                 print(f"densify at iter {it + 1}: avg gradient over {r['seen']} of {r['n']} Gaussians seen: p50={r['p50']:.3e} "
                       f"p90={r['p90']:.3e} p99={r['p99']:.3e} max={r['max']:.3e}, {r['over']} at or over "
                       f"{args.densify_grad_threshold:g}; N -> {fitter.params['means'].shape[0]}")
+    if args.refine_cameras:  # all input views in input order: the training views refined, the held-out ones as given
+        all_cams = list(all_cams)
+        for i, cam in zip(train, fitter.refined_cameras()):
+            all_cams[i] = cam
     if rank == 0:
         save_outputs(fitter, all_cams, args, Path(args.out_dir), loss_log, eval_log)
     if world > 1:
@@ -2214,6 +2436,10 @@ def save_outputs(fitter: ViewShardedFitter, cams, args, out_dir: Path, loss_log,
     (out_dir / "loss.txt").write_text("\n".join(f"{v:.8f}" for v in loss_log), encoding="utf-8")
     if eval_log is not None:
         (out_dir / "eval.json").write_text(json.dumps(eval_log, indent=1), encoding="utf-8")
+    if getattr(args, "refine_cameras", False):  # the --camera_npz schema: feed it back with --camera_npz
+        np.savez(out_dir / "cameras_refined.npz",
+                 view=np.stack([c.view.detach().cpu().numpy().astype(np.float32) for c in cams]),
+                 proj=np.stack([c.proj.detach().cpu().numpy().astype(np.float32) for c in cams]))
     with torch.no_grad():
         pred0 = tr.render_gaussians_torch(means, scales, sh if sh is not None else colors, opacities, cams[0],
                                           width=args.width, height=args.height,

@@ -855,6 +855,43 @@ def density_stats_native(means, scales, opacities, batch, inv_g_scale: float, st
                                      ctypes.c_float(inv_g_scale), _native.ptr(stats), _stream(dev)), "gr_density_stats")
 
 
+def camera_grads_sums_native(means, scales, colors, opacities, batch, rows, ws=None) -> None:
+    """gr_camera_grads_sums on the current stream, beside ``reduce_sums_native`` on the same ``batch``: entry q's
+    camera gradient (gr_bwd_camera's layout: d view 16, d proj 16, d cam_pos 3) of whatever its sums are the gradient
+    of goes to ``rows[q]``, a (``_native.CAMERA_GRADS``,) float32 device tensor (a row of a larger buffer will do),
+    overwritten.  Band views (rows > 0) get their additive share.  ``ws``: a uint8 device workspace of at least
+    ``gr_camera_grads_ws_bytes`` to reuse (stream-ordered); None allocates one."""
+    L = _native.lib()
+    if not 1 <= len(batch) <= _native.REDUCE_MAX_VIEWS:
+        raise ValueError(f"1 to {_native.REDUCE_MAX_VIEWS} views per gr_camera_grads_sums batch")
+    if len(rows) != len(batch):
+        raise ValueError(f"gr_camera_grads_sums: {len(batch)} views but {len(rows)} output rows")
+    _check_params(means, scales, colors, opacities)
+    n = int(means.shape[0])
+    dev = means.device
+    arr = (_native.GrSumsView * len(batch))()
+    out = (ctypes.c_void_p * len(batch))()
+    for k, item in enumerate(batch):
+        gv, sums = item[0], item[1]
+        sums3 = item[2] if len(item) > 2 else None
+        _check_operand(sums, (n, 8), "sums", dev)
+        _check_operand(sums3, (n,), "sums3", dev)
+        _check_operand(rows[k], (_native.CAMERA_GRADS,), "rows", dev)
+        arr[k].view = gv
+        arr[k].sums = sums.data_ptr()
+        arr[k].sums3 = sums3.data_ptr() if sums3 is not None else None
+        out[k] = rows[k].data_ptr()
+    need = int(L.gr_camera_grads_ws_bytes(n, len(batch)))
+    if ws is None:
+        ws = torch.empty((max(need, 8),), dtype=torch.uint8, device=dev)
+    elif (not isinstance(ws, torch.Tensor) or ws.dtype != torch.uint8 or ws.device != dev or not ws.is_contiguous()
+          or ws.numel() < need):
+        raise ValueError(f"ws: expected a contiguous uint8 tensor of at least {need} bytes on {dev}")
+    _native.check(L.gr_camera_grads_sums(len(batch), arr, n, _native.ptr(means), _native.ptr(scales), _native.ptr(colors),
+                                         _color_dim(colors), _native.ptr(opacities), out, _native.ptr(ws), ws.numel(),
+                                         _stream(dev)), "gr_camera_grads_sums")
+
+
 def eval_view_native(st: RenderState, target, metrics_out) -> None:
     """gr_eval_view on the current stream: ``metrics_out`` (``_native.EVAL_METRICS`` float32 on the device) receives
     mean|out - target|, mean (out - target)^2 and the mean SSIM of the view's render against ``target`` (H, W, 3), the
@@ -1239,5 +1276,5 @@ def render_gaussians_torch(
 __all__ = ["Camera", "get_default_device", "perspective", "look_at", "render_gaussians_torch", "rasterize",
            "make_view", "prepare_view", "prepare_native", "Prepared", "forward_native", "backward_native",
            "backward_l1_native", "backward_fit_native", "backward_fit_gather_native", "forward_l1_native", "backward_splat_native", "reduce_views_native",
-           "gather_view_native", "reduce_sums_native", "density_stats_native", "eval_view_native",
+           "gather_view_native", "reduce_sums_native", "density_stats_native", "camera_grads_sums_native", "eval_view_native",
            "DEFAULT_CUTOFF", "DEPTH_GRAD_CUTOFF", "DEFAULT_CORE_CUTOFF", "FIT_CUTOFF", "default_cutoff"]

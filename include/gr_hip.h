@@ -358,6 +358,27 @@ gr_status gr_density_stats(int num_views, const gr_sums_view* views, int n, cons
                            const float* scales, const float* opacities, float inv_g_scale, float* stats,
                            void* stream);
 
+/* Camera gradients of a gr_reduce_sums batch (an extension: the reference fit loop treats its cameras as exact,
+ * fit_multiview_stub.py:277-310; its renderer differentiates them, torch_renderer.py:140-150, which gr_bwd_camera
+ * covers for one view after gr_bwd).  Called beside gr_reduce_sums on the same batch and stream.  Row q of the
+ * batch goes to d_camera[q] (a host array of device rows of GR_CAMERA_GRADS floats, overwritten) in gr_bwd_camera's
+ * layout: d view (16, row-major), d proj (16), d cam_pos (3; zero for RGB colours), from entry q's sums row (sums3
+ * when set), unpacked as gr_reduce_sums does: the gradient of whatever the sums are the gradient of (g_scale x the
+ * view loss in the fit).  Two launches: k_camera_grad_views (one lane per Gaussian, its parameters loaded once, the
+ * views in batch order, per view a fixed-order block sum in double into ws) and k_camera_final_views (the blocks in
+ * a fixed order).
+ *   - a view's row does not depend on what shares its batch: bit-identical to a one-view call
+ *   - views with rows > 0 (bands) are included: a band's camera gradient is an additive share of the whole view's;
+ *     every batch entry has its own row, so two streams never write one row
+ *   - ws: gr_camera_grads_ws_bytes(n, num_views); shorter: GR_ERR_WORKSPACE
+ *   - num_views outside [1, GR_REDUCE_MAX_VIEWS], a bad color_dim, a null d_camera or row, a null pointer with
+ *     n > 0, a null sums: GR_ERR_INVALID_ARGUMENT; nothing is launched on a refusal; n == 0: the rows are zeroed
+ *   - no atomics, no allocation; stream-ordered; deterministic */
+size_t gr_camera_grads_ws_bytes(int n, int num_views);
+gr_status gr_camera_grads_sums(int num_views, const gr_sums_view* views, int n, const float* means,
+                               const float* scales, const float* colors, int color_dim, const float* opacities,
+                               float* const* d_camera, void* ws, size_t ws_bytes, void* stream);
+
 /* gr_bwd_fit / gr_bwd_fit_gather for the loss Gaussian-splatting trainers minimise (an extension, as gr_ssim_*):
  *   loss = (1 - l) mean|out - target_rgb| + l (1 - mean SSIM(out, target_rgb)) + w_sil mean|alpha - target_mask|
  *          + w_depth mean|depth / (max(depth) + 1e-6) - target_depth|,   l = w_dssim in [0, 1]
@@ -450,6 +471,12 @@ gr_status gr_fit_views_ssim(gr_executor* executor, const gr_fit_config* config, 
  * during those calls (not copied) and must stay valid until it is replaced.  NULL (the default): no statistics,
  * the calls exactly as before.  Bit-identical to fit_multiview.py's Python schedule with density_stats. */
 gr_status gr_executor_density_stats(gr_executor* executor, float* const* stats_per_stream);
+/* Camera gradients from the executor's steps: with d_cameras set (device, [num_views][GR_CAMERA_GRADS] floats of the
+ * following gr_fit_views / gr_fit_views_ssim calls), each batch's gr_camera_grads_sums is enqueued after its
+ * gr_reduce_sums (and density statistics) on the same stream, view j of the call writing row j; the partial-sum
+ * workspaces are the executor's own, one per render stream.  NULL (the default): none, the calls exactly as before.
+ * gr_eval_views ignores the setting.  Bit-identical to fit_multiview.py's Python schedule with refine_cameras. */
+gr_status gr_executor_camera_grads(gr_executor* executor, float* d_cameras);
 
 /* View metrics for held-out evaluation (an extension: the reference fit loop reports its training loss only): of a
  * rendered view against a target image, over all H*W*3 values,

@@ -1,0 +1,381 @@
+"""GPU: the camera gradients of the fused fit path (gr_camera_grads_sums / k_camera_grad_views,
+gr_executor_camera_grads) and ViewShardedFitter(refine_cameras=True) on the HIP device.
+
+* the kernel as a pure function of its inputs: synthetic sums (some rows all zero, sums3 on one view, negative
+  opacities), n not a multiple of the block, colour dims 3 / 12 / 48: a 1 / 3 / 16-view batch bit-identical to one-view
+  calls row by row, determinism, a band entry's own row, an all-zero view, n = 0, the argument errors;
+* through the fused path (forward_l1_native -> backward_splat_native -> gather_view_native -> camera_grads_sums_native at
+  both tile sizes, and the depth form through backward_fit_gather_native) against the float64 dense reference
+  (tests/camera_reference.py) at the project's camera-gradient bar;
+* the fitter: Python schedule and native executor bit-identical in the L1, depth and fused D-SSIM forms and equal to
+  single-view calls; off is off; against the host fitter; pose recovery; the unfused D-SSIM fit (autograd path).
+"""
+from __future__ import annotations
+
+import ctypes
+import importlib
+import math
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import oracle as orc
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+if HERE not in sys.path:
+    sys.path.insert(0, HERE)
+import camera_reference as cref  # noqa: E402
+from test_camera_refine_cpu import pose_errors, recovery_fitter  # noqa: E402
+from test_density_gpu import _batch, _synthetic  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+CAM_TOL = 1e-4  # tests/test_camera_grad.py's bar: relative L2 of d view / d proj
+CG = 35
+
+
+# ---- the kernel as a pure function ------------------------------------------------------------------------------------
+def _colors(n, cd, seed):
+    rng = np.random.default_rng(seed)
+    if cd == 3:
+        return rng.uniform(-0.2, 1.2, (n, 3)).astype(np.float32)  # some outside [0, 1] (the clamp's mask)
+    c = (rng.standard_normal((n, cd // 3, 3)) * 0.3).astype(np.float32)
+    c[:, 0, :] += 0.5
+    return c
+
+
+def _kernel_case(tr, n, cd, nviews, cuda, seed):
+    means, scales, opac, views, W, H = _synthetic(n, nviews, cuda, seed)
+    if nviews > 2:  # a view that saw nothing
+        views[2] = (views[2][0], views[2][1], np.zeros((n, 8), np.float32), None)
+    m, s, o = (torch.from_numpy(a).to(cuda) for a in (means, scales, opac))
+    c = torch.from_numpy(_colors(n, cd, seed + 1)).to(cuda)
+    return (m, s, c, o), _batch(tr, views, W, H, cuda)
+
+
+def _rows(tr, p, batch, cuda, fill=float("nan")):
+    rows = torch.full((len(batch), CG), fill, device=cuda)
+    tr.camera_grads_sums_native(*p, batch, list(rows))
+    return rows
+
+
+@pytest.mark.parametrize("cd", [3, 12, 48])
+@pytest.mark.parametrize("n", [1, 255, 257, 1000])
+def test_batches_are_bit_identical_to_one_view_calls(pkg, cuda, n, cd):
+    tr, nat = pkg.torch_renderer, pkg._native
+    p, batch = _kernel_case(tr, n, cd, 16, cuda, seed=100 * n + cd)
+    # a band entry (view 5 again, as a band of tile rows) gets its own row: the band's share of its sums
+    band = nat.GrView.from_buffer_copy(batch[5][0])
+    band.row0, band.rows = 1, 2
+    batch[15] = (band,) + tuple(batch[5][1:])
+    r16 = _rows(tr, p, batch, cuda)
+    ones = torch.cat([_rows(tr, p, [b], cuda) for b in batch])
+    r3 = _rows(tr, p, batch[:3], cuda)
+    again = _rows(tr, p, batch, cuda, fill=7.0)
+    torch.cuda.synchronize()
+    assert torch.isfinite(r16).all()
+    assert torch.equal(r16, ones) and torch.equal(r3, ones[:3]) and torch.equal(again, r16)
+    assert float(r16[2].abs().sum()) == 0.0  # the all-zero view
+    assert torch.equal(r16[15], r16[5])
+    assert float(r16[1, :16].abs().sum()) > 0.0  # (the view with depth sums)
+    if n > 1:  # (n = 1: view 5's only row is one of the all-zero ones, and one Gaussian may have opacity <= 0)
+        assert float(r16[5, :16].abs().sum()) > 0.0 and float(r16[5, 16:32].abs().sum()) > 0.0
+        assert float(r16[1, 16:32].abs().sum()) > 0.0 and (cd == 3 or float(r16[1, 32:].abs().sum()) > 0.0)
+    if cd == 3:
+        assert float(r16[:, 32:].abs().sum()) == 0.0  # d cam_pos: RGB colours do not see the camera centre
+    # bounded workspace reuse: a caller's own workspace of the stated size gives the same bits
+    ws = torch.empty((int(nat.lib().gr_camera_grads_ws_bytes(n, 16)),), dtype=torch.uint8, device=cuda)
+    rows = torch.zeros((16, CG), device=cuda)
+    tr.camera_grads_sums_native(*p, batch, list(rows), ws=ws)
+    assert torch.equal(rows, r16)
+
+
+def test_edge_cases_and_argument_errors(pkg, cuda):
+    tr, nat = pkg.torch_renderer, pkg._native
+    L = nat.lib()
+    n = 64
+    (m, s, c, o), batch = _kernel_case(tr, n, 3, 2, cuda, seed=6)
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    arr = (nat.GrSumsView * 17)()
+    for k in range(17):
+        arr[k].view, arr[k].sums = batch[0][0], batch[0][1].data_ptr()
+    SENT = 123.0
+    rows = torch.full((17, CG), SENT, device=cuda)
+    out = (ctypes.c_void_p * 17)(*[rows[k].data_ptr() for k in range(17)])
+    need = int(L.gr_camera_grads_ws_bytes(n, 16))
+    assert need == 16 * 1 * CG * 8 and int(L.gr_camera_grads_ws_bytes(257, 3)) == 3 * 2 * CG * 8
+    ws = torch.empty((need,), dtype=torch.uint8, device=cuda)
+
+    def call(nv, a, nn, pm, ps, pc, cd, po, rows_p, w, wb):
+        return L.gr_camera_grads_sums(nv, a, nn, pm, ps, pc, cd, po, rows_p, w, wb, stream)
+
+    ok = dict(nv=1, a=arr, nn=n, pm=nat.ptr(m), ps=nat.ptr(s), pc=nat.ptr(c), cd=3, po=nat.ptr(o), rows_p=out, w=nat.ptr(ws),
+              wb=need)
+    bad = [dict(nv=0), dict(nv=17), dict(cd=4), dict(nn=-1), dict(a=None), dict(pm=None), dict(ps=None), dict(pc=None),
+           dict(po=None), dict(rows_p=None), dict(w=None)]
+    for b in bad:
+        assert call(**{**ok, **b}) == nat.GR_ERR_INVALID_ARGUMENT, b
+    hole = (ctypes.c_void_p * 17)(*[rows[k].data_ptr() for k in range(17)])
+    hole[1] = None
+    assert call(**{**ok, "nv": 2, "rows_p": hole}) == nat.GR_ERR_INVALID_ARGUMENT  # a null row
+    assert call(**{**ok, "nn": 0, "rows_p": hole, "nv": 2}) == nat.GR_ERR_INVALID_ARGUMENT  # ... also with n == 0
+    arr[1].sums = None
+    assert call(**{**ok, "nv": 2}) == nat.GR_ERR_INVALID_ARGUMENT  # a null sums
+    arr[1].sums = batch[0][1].data_ptr()
+    assert call(**{**ok, "wb": int(L.gr_camera_grads_ws_bytes(n, 1)) - 1}) == nat.GR_ERR_WORKSPACE
+    assert call(**{**ok, "nv": 2, "wb": int(L.gr_camera_grads_ws_bytes(n, 1))}) == nat.GR_ERR_WORKSPACE
+    torch.cuda.synchronize()
+    assert bool((rows == SENT).all())  # nothing was launched by a refused call
+    # n == 0: the rows are zeroed (and only the batch's rows)
+    assert call(**{**ok, "nv": 2, "nn": 0, "pm": None, "ps": None, "pc": None, "po": None, "w": None, "wb": 0}) == nat.GR_OK
+    torch.cuda.synchronize()
+    assert float(rows[:2].abs().sum()) == 0.0 and bool((rows[2:] == SENT).all())
+    assert call(**ok) == nat.GR_OK
+    with pytest.raises(ValueError):
+        tr.camera_grads_sums_native(m, s, c, o, batch, list(rows[:1]))
+    with pytest.raises(ValueError):
+        tr.camera_grads_sums_native(m, s, c, o, [], [])
+    with pytest.raises(ValueError):
+        tr.camera_grads_sums_native(m, s, c, o, batch, list(torch.zeros((2, CG + 1), device=cuda)))
+    with pytest.raises(ValueError):
+        tr.camera_grads_sums_native(m, s, c, o, batch, list(rows[:2]), ws=torch.empty((8,), dtype=torch.uint8, device=cuda))
+    with pytest.raises(ValueError):
+        tr.camera_grads_sums_native(m, s, c, o, [(batch[0][0], batch[0][1][:-1])], list(rows[:1]))
+
+
+# ---- through the fused path against the float64 dense reference -------------------------------------------------------
+def _e2e_scene(case):
+    if case == "rgb_n300":
+        return orc.synthetic_scene(300, seed=1).arrays()
+    sc = orc.synthetic_scene(64, seed=2, sh=True)
+    colors = sc.colors.copy()
+    colors[:, 1:, :] = (np.random.default_rng(22).standard_normal((64, 3, 3)) * 0.3).astype(np.float32)
+    colors[:, 0, :] += 0.4
+    return sc.means, sc.scales, colors, sc.opacities
+
+
+def _drop_in_error(tr, t, view, proj, W, H, cuda, loss_fn, ref_v, ref_p, depth_grad):
+    """The existing drop-in route (render_gaussians_torch with camera tensors requiring grad: gr_bwd_camera) on the same
+    scene and loss, for the record."""
+    vt = torch.from_numpy(np.asarray(view, np.float32)).to(cuda).requires_grad_(True)
+    pt = torch.from_numpy(np.asarray(proj, np.float32)).to(cuda).requires_grad_(True)
+    out, alpha, depth = tr.render_gaussians_torch(*t, tr.Camera(view=vt, proj=pt), W, H, background=torch.zeros(3, device=cuda),
+                                                  max_gaussians=10000, return_aux=True, depth_grad=depth_grad)
+    loss_fn(out, alpha, depth).backward()
+    return orc.rel_l2(vt.grad.cpu().numpy(), ref_v.numpy()), orc.rel_l2(pt.grad.cpu().numpy(), ref_p.numpy())
+
+
+@pytest.mark.parametrize("form", ["tile16", "tile32", "depth"])
+@pytest.mark.parametrize("case", ["rgb_n300", "sh_n64"])
+def test_fused_path_camera_gradient_vs_dense_reference(pkg, cuda, case, form):
+    tr = pkg.torch_renderer
+    W, H = 64, 48
+    arrays = _e2e_scene(case)
+    view, proj = orc.orbit_cameras(8, W, H)[1]
+    t = [torch.from_numpy(np.ascontiguousarray(a)).to(cuda) for a in arrays]
+    g = torch.Generator(device=cuda).manual_seed(12)
+    target = torch.rand((H, W, 3), generator=g, device=cuda)
+    mask = (target.mean(dim=2) > 0.5).float().contiguous()
+    dtarget = torch.rand((H, W), generator=g, device=cuda)
+    w_sil, w_depth, g_scale = 0.2, 0.05, 0.25
+    loss = torch.zeros(1, device=cuda)
+    if form == "depth":
+        gv = tr.make_view(view, proj, W, H, None, depth_grad=True)
+        out, alpha, depth, st = tr.forward_native(*t, gv, tr.prepare_native(*t, gv))
+        sums, sums3 = tr.backward_fit_gather_native(st, target, mask, w_sil, dtarget, w_depth, g_scale, loss)
+        item = (st.gv, sums, sums3)
+    else:
+        gv = tr.make_view(view, proj, W, H, None, cutoff=tr.FIT_CUTOFF, core_cutoff=tr.FIT_CUTOFF, depth_grad=False,
+                          tile=int(form[4:]))
+        out, alpha, depth = torch.empty((H, W, 3), device=cuda), torch.empty((H, W), device=cuda), None
+        st, ws = tr.forward_l1_native(*t, gv, tr.prepare_native(*t, gv), target, mask, w_sil, g_scale, loss, out=out, alpha=alpha)
+        tr.backward_splat_native(st, ws)
+        item = (st.gv, tr.gather_view_native(st, ws))
+    row = torch.zeros(CG, device=cuda)
+    tr.camera_grads_sums_native(*t, [item], [row])
+    torch.cuda.synchronize()
+    sh = t[2].dim() == 3
+    vt, pt = torch.from_numpy(np.asarray(view, np.float32)), torch.from_numpy(np.asarray(proj, np.float32))
+    dview, dproj = tr._camera_grads(row.cpu(), vt, pt, True, True, sh)
+    # the upstream images of g_scale x the view loss, the kinks' signs (and the depth maximum) from the HIP images
+    F = torch.float64
+    g_out = g_scale * torch.sign(out.cpu().to(F) - target.cpu().to(F)) / (3 * H * W)
+    g_alpha = g_scale * w_sil * torch.sign(alpha.cpu().to(F) - mask.cpu().to(F)) / (H * W)
+    g_depth = None
+    if form == "depth":
+        d = depth.cpu().to(F).requires_grad_(True)
+        (g_depth,) = torch.autograd.grad(g_scale * w_depth * (d / (d.max() + 1e-6) - dtarget.cpu().to(F)).abs().mean(), d)
+    ref_v, ref_p, r_out, _, _ = cref.camera_grads(*t, view, proj, W, H, g_out, g_alpha, g_depth)
+    ev, ep = orc.rel_l2(dview.numpy(), ref_v.numpy()), orc.rel_l2(dproj.numpy(), ref_p.numpy())
+    img = orc.rel_l2(out.cpu().numpy(), r_out.numpy())
+
+    def loss_fn(o_, a_, d_):
+        v = (o_ - target).abs().mean() + w_sil * (a_ - mask).abs().mean()
+        if form == "depth":
+            v = v + w_depth * (d_ / (d_.max() + 1e-6) - dtarget).abs().mean()
+        return g_scale * v
+
+    dv, dp = _drop_in_error(tr, t, view, proj, W, H, cuda, loss_fn, ref_v, ref_p, form == "depth")
+    print(f"{case} {form}: fused path d_view relL2 {ev:.2e}, d_proj relL2 {ep:.2e} (image relL2 {img:.1e}); "
+          f"drop-in route (gr_bwd_camera) d_view {dv:.2e}, d_proj {dp:.2e}")
+    assert float(ref_v.norm()) > 0 and float(ref_p.norm()) > 0
+    assert ev <= CAM_TOL and ep <= CAM_TOL
+
+
+# ---- the fitter ---------------------------------------------------------------------------------------------------------
+FW, FH, FN, FV = 64, 48, 300, 6
+FORMS = {"l1": {}, "depth": {"depth": True}, "dssim_fused": {"dssim_weight": 0.2, "dssim_fused": True}}
+
+
+def _fit_scene(cuda):
+    fm = importlib.import_module("3dgaussian_amd.fit_multiview")
+    cams = fm.orbit_cameras(FV, FW, FH, cuda)
+    g = torch.Generator(device=cuda).manual_seed(21)
+    targets = [torch.rand((FH, FW, 3), generator=g, device=cuda) for _ in range(FV)]
+    masks = [(t.mean(dim=2) > 0.5).float() for t in targets]
+    depths = [torch.rand((FH, FW), generator=g, device=cuda) for _ in range(FV)]
+    return fm, cams, targets, masks, depths
+
+
+def _fitter(fm, cuda, cams, targets, masks, depths, form, **kw):
+    bench = importlib.import_module("bench")
+    opts = dict(FORMS[form])
+    d = depths if opts.pop("depth", False) else None
+    return fm.ViewShardedFitter(bench.synthetic_params(FN, cuda), cams, targets, FW, FH, masks=masks, depths=d, **opts, **kw)
+
+
+def _single_view_grad(fm, tr, f, cuda):
+    """The fitter's first step's d loss / d xi assembled from single-view camera_grads_sums_native calls and the host's
+    own arithmetic (_camera_grads for the camera centre's term, the vector-Jacobian product through pose_view)."""
+    m, s, c, o, _ = fm.activations_native(f.params)
+    w_sil, g_scale = f.w_sil, 1.0 / len(f.targets)
+    loss = torch.zeros(1, device=cuda)
+    rows = torch.zeros((FV, CG), device=cuda)
+    for i in range(FV):
+        if f._ssim_form() or f._depth_grad():
+            cam = f.cams[i]
+            gv = (tr.make_view(cam.view, cam.proj, FW, FH, f._background(cuda), depth_grad=True) if f._depth_grad()
+                  else f._ssim_view(i, cuda))
+            *_, rs = tr.forward_native(m, s, c, o, gv, tr.prepare_native(m, s, c, o, gv), images=False)
+            dt, wd = (f.depths[i], f.w_depth) if f._depth_grad() else (None, 0.0)
+            if f._ssim_form():
+                sums, sums3 = tr.backward_fit_ssim_gather_native(rs, f.targets[i], f.masks[i], w_sil, dt, wd, g_scale,
+                                                                 f.w_dssim, loss)
+            else:
+                sums, sums3 = tr.backward_fit_gather_native(rs, f.targets[i], f.masks[i], w_sil, dt, wd, g_scale, loss)
+            item = (rs.gv, sums, sums3) if sums3 is not None else (rs.gv, sums)
+        else:
+            gv = f._fit_view(i, cuda)
+            rs, ws = tr.forward_l1_native(m, s, c, o, gv, tr.prepare_native(m, s, c, o, gv), f.targets[i], f.masks[i], w_sil,
+                                          g_scale, loss)
+            tr.backward_splat_native(rs, ws)
+            item = (rs.gv, tr.gather_view_native(rs, ws))
+        tr.camera_grads_sums_native(m, s, c, o, [item], [rows[i]])
+    torch.cuda.synchronize()
+    g = f._camera_xi_grad(rows.cpu())  # the fitter's own host arithmetic on these rows
+    for i in f.camera_fixed:
+        g[i] = 0.0
+    # ... which is the plain vector-Jacobian product through pose_view, view by view
+    for i in range(FV):
+        xi = torch.zeros(6, dtype=torch.float64, requires_grad=True)
+        v0 = f.cams[i].view.detach().cpu().double()
+        (gi,) = torch.autograd.grad((fm.pose_view(xi, v0) * rows[i, :16].view(4, 4).cpu().double()).sum(), xi)
+        assert i in f.camera_fixed or torch.allclose(g[i], gi, rtol=1e-10, atol=1e-13 * float(gi.abs().max()))
+    return g
+
+
+@pytest.mark.parametrize("form", list(FORMS))
+def test_fitter_python_vs_native_vs_single_views(pkg, cuda, form):
+    tr = pkg.torch_renderer
+    fm, cams, targets, masks, depths = _fit_scene(cuda)
+    res = {}
+    saved = fm.NATIVE_EXEC, fm.NUM_STREAMS
+    try:
+        for native in (False, True):
+            fm.NATIVE_EXEC, fm.NUM_STREAMS = ("1" if native else "0"), 2
+            f = _fitter(fm, cuda, cams, targets, masks, depths, form, refine_cameras=True)
+            assert not f._graph_ok(cuda)  # captured launches would carry the matrices as kernel arguments
+            if not native:
+                want = _single_view_grad(fm, tr, f, cuda)
+            snap = []
+            for it in range(3):
+                loss = float(f.step())
+                if it in (0, 2):
+                    snap.append((loss, {k: v.detach().clone() for k, v in f.params.items()}, f.camera_state(),
+                                 torch.stack([c.view for c in f.refined_cameras()]).cpu()))
+            if not native:
+                g1 = snap[0][2][1]
+                assert torch.equal(g1, want) and float(g1[1:].abs().min()) > 0 and torch.isfinite(g1).all()
+                assert torch.equal(g1[0], torch.zeros(6, dtype=torch.float64))
+            res[native] = snap
+    finally:
+        fm.NATIVE_EXEC, fm.NUM_STREAMS = saved
+    for a, b in zip(res[False], res[True]):  # after 1 step and after 3 steps
+        assert a[0] == b[0]
+        assert all(torch.equal(a[1][k], b[1][k]) for k in a[1])
+        assert torch.equal(a[2][0], b[2][0]) and torch.equal(a[2][1], b[2][1]) and torch.equal(a[3], b[3])
+    xi3 = res[True][1][2][0]
+    assert torch.equal(xi3[0], torch.zeros(6, dtype=torch.float64)) and float(xi3[1:].abs().min()) > 0
+    assert torch.equal(res[True][1][3][0], cams[0].view.cpu()) and not torch.equal(res[True][1][3][1], cams[1].view.cpu())
+
+
+@pytest.mark.parametrize("mode", ["0", "batch"])
+def test_off_is_off(cuda, mode):
+    fm, cams, targets, masks, depths = _fit_scene(cuda)
+    saved = fm.GRAPH_MODE
+    runs = []
+    try:
+        fm.GRAPH_MODE = mode
+        for kw in ({}, {"refine_cameras": False}):
+            f = _fitter(fm, cuda, cams, targets, masks, depths, "l1", **kw)
+            losses = [f.step().clone() for _ in range(3)]
+            f.graph_sync()
+            runs.append((losses, {k: v.detach().clone() for k, v in f.params.items()}))
+    finally:
+        fm.GRAPH_MODE = saved
+    assert all(torch.equal(a, b) for a, b in zip(runs[0][0], runs[1][0]))
+    assert all(torch.equal(runs[0][1][k], runs[1][1][k]) for k in runs[0][1])
+
+
+def test_fitter_gradient_vs_the_host_fitter(cuda):
+    """The HIP fitter's first-step d loss / d xi against the CPU fitter's autograd value (the dense cpu_renderer) on
+    the recovery scene and its perturbed cameras."""
+    fm = importlib.import_module("3dgaussian_amd.fit_multiview")
+    host, _, _ = recovery_fitter(fm, 0, torch.device("cpu"))
+    host.step()
+    dev, _, _ = recovery_fitter(fm, 0, cuda)
+    dev.step()
+    gh, gd = host.camera_state()[1], dev.camera_state()[1]
+    rel = float((gd - gh).norm() / gh.norm())
+    print(f"HIP fitter first-step d loss / d xi vs the host fitter's autograd: relL2 {rel:.2e}")
+    assert float(gh.norm()) > 0 and rel <= CAM_TOL
+
+
+@pytest.mark.parametrize("seed", [0, 1])
+def test_recovery_on_the_device(cuda, seed):
+    fm = importlib.import_module("3dgaussian_amd.fit_multiview")
+    fit, true_views, init = recovery_fitter(fm, seed, cuda)
+    assert fit._direct(cuda) and not fit._depth_grad() and not fit._ssim_form()  # the fused L1 path, default tile
+    r0, c0 = pose_errors(init, true_views)
+    for _ in range(100):
+        fit.step()
+    r1, c1 = pose_errors([c.view.cpu().numpy() for c in fit.refined_cameras()], true_views)
+    print(f"seed {seed}: rotation error {math.degrees(r0):.3f} -> {math.degrees(r1):.3f} deg (ratio {r1 / r0:.3f}), "
+          f"centre error {c0:.4f} -> {c1:.4f} (ratio {c1 / c0:.3f})")
+    assert r1 <= 0.25 * r0 and c1 <= 0.25 * c0
+
+
+def test_unfused_dssim_fit_refines_through_autograd(cuda):
+    fm, cams, targets, masks, depths = _fit_scene(cuda)
+    bench = importlib.import_module("bench")
+    f = fm.ViewShardedFitter(bench.synthetic_params(FN, cuda), cams, targets, FW, FH, masks=masks, dssim_weight=0.2,
+                             refine_cameras=True)
+    assert not f._direct(cuda)  # the per-view autograd path (gr_bwd_camera delivers d view)
+    loss = f.step()
+    xi, g = f.camera_state()
+    assert torch.isfinite(loss) and torch.isfinite(g).all() and torch.isfinite(xi).all()
+    assert torch.equal(g[0], torch.zeros(6, dtype=torch.float64)) and float(g[1:].abs().min()) > 0
+    assert float(xi[1:].abs().min()) > 0 and not torch.equal(f.refined_cameras()[1].view, cams[1].view)
