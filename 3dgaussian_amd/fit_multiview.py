@@ -473,7 +473,8 @@ class ViewShardedFitter:
                  depth_weight: float = 0.05, reg_opacity: float = 1e-3, reg_scale: float = 1e-3,
                  render_fn: RenderFn = hip_render, group=None, reorder: bool = True, dssim_weight: float = 0.0,
                  dssim_fused: bool = False, density_stats: bool = False, refine_cameras: bool = False,
-                 camera_lr: float = 1e-3, camera_fixed: tuple = (0,)):
+                 camera_lr: float = 1e-3, camera_fixed: tuple = (0,), exposure: bool = False, exposure_lr: float = 1e-3,
+                 exposure_fixed: tuple = (0,)):
         # dssim_weight l > 0: a view's photometric term is (1 - l) mean|pred - tgt| + l dssim(pred, tgt)
         # (losses.dssim_loss) on the per-view autograd path; 0 (default): the L1 fit, every path as it was
         # dssim_fused (with l > 0, the HIP render op): the fused path's D-SSIM form (_views_direct_ssim or the native
@@ -484,6 +485,11 @@ class ViewShardedFitter:
         # refine_cameras: the views' poses are fitted with the Gaussians (pose_view: a 6-vector per view, an Adam of its
         # own at camera_lr; the views of camera_fixed keep their poses, which pins the scene's gauge): on the HIP device's
         # fused paths from gr_camera_grads_sums beside every gr_reduce_sums, elsewhere through autograd
+        # exposure: per-view exposure compensation, a 3 x 4 colour transform E per training view (from [I | 0]) fitted
+        # with the scene by an Adam of its own at exposure_lr: the photometric term (L1 and D-SSIM alike) compares
+        # E (pred, 1) with the target (the views of exposure_fixed keep theirs, which pins the overall brightness
+        # gauge), through autograd in view_loss.  Host tensors only: the HIP device has no exposure form yet, and a fit
+        # on it raises rather than leave the fused path; evaluate() renders without it
         # reorder: keep the Gaussians in spatial (Morton) order, re-established after every
         # densify/prune (spatial_order); off only to compare with an unpermuted run
         # perm: self.params[k][i] = canonical[k][perm[i]], the canonical order being the stub's (the
@@ -543,6 +549,27 @@ class ViewShardedFitter:
             self._cam_host = {}  # view -> its (view, proj) as host float32 arrays (what the gr_views are built from)
             self._cam_rows = None  # the fused paths' per-step (len(my_views), 35) camera-gradient rows
             self._cam_params = {}  # the autograd path's pose leaves of this step
+        self.exposure = bool(exposure)
+        if self.exposure:
+            if self.dssim_fused:
+                raise ValueError("exposure with dssim_fused: the fused D-SSIM form stages the colours inside its SSIM "
+                                 "kernels and has no exposure (use dssim_fused=False)")
+            if dev.type == "cuda":
+                raise ValueError("exposure on the HIP device: the fused fit path has no exposure form yet (fit on host "
+                                 "tensors, --device cpu)")
+            V = len(cams)
+            self.exposure_lr = float(exposure_lr)
+            self.exposure_fixed = tuple(sorted({int(i) for i in exposure_fixed}))
+            if any(not 0 <= i < V for i in self.exposure_fixed):
+                raise ValueError(f"exposure_fixed {exposure_fixed}: view indices must be in [0, {V})")
+            eye = torch.cat([torch.eye(3), torch.zeros(3, 1)], dim=1)
+            self._expo = eye.repeat(V, 1, 1).to(device=dev, dtype=torch.float32).contiguous()  # (V, 3, 4)
+            self._expo_grad = torch.zeros((V, 12), dtype=torch.float32, device=dev)  # d loss / d E of the last step
+            self._expo_free = torch.ones((V, 1), dtype=torch.float32, device=dev)  # 0 on the rows of exposure_fixed
+            for i in self.exposure_fixed:
+                self._expo_free[i] = 0.0
+            self._expo_opt = torch.optim.Adam([self._expo], lr=self.exposure_lr)
+            self._expo_leaves = {}  # the exposure leaves of this step
 
     def canonical_params(self) -> dict:
         """The parameters in the stub's order (undoes the trainer's Morton permutation)."""
@@ -770,6 +797,54 @@ class ViewShardedFitter:
             raise ValueError("camera_state: the fitter was made without refine_cameras")
         return self._xi.detach().clone(), self._xi_grad.clone()
 
+    # ---- exposure compensation (exposure=True) ------------------------------------------------------------------
+    def _exposure_leaf(self, i: int) -> torch.Tensor:
+        """View i's exposure as a leaf of this step."""
+        e = self._expo[i].detach().clone().requires_grad_(True)
+        self._expo_leaves[i] = e
+        return e
+
+    def _exposure_step_autograd(self) -> None:
+        """After the step's backward: d loss / d E of this rank's views, summed over the ranks, the update."""
+        V = len(self.targets)
+        g = torch.zeros((V, 12), dtype=torch.float32, device=self._expo.device)
+        for i, e in self._expo_leaves.items():
+            if e.grad is not None:
+                g[i] = e.grad.reshape(12)
+        self._expo_leaves = {}
+        if self.world > 1:
+            dist.all_reduce(g, group=self.group)
+        self._exposure_update(g)
+
+    def _exposure_update(self, g: torch.Tensor) -> None:
+        """Adam on the exposures from the all-reduced (V, 12) gradient (every rank the same arithmetic on the same
+        numbers), the rows of exposure_fixed zeroed: a gradient that is always zero leaves its row where it is."""
+        g = g * self._expo_free
+        self._expo_grad = g
+        self._expo.grad = g.view(-1, 3, 4)
+        self._expo_opt.step()
+        self._expo.grad = None
+
+    def exposure_state(self) -> tuple:
+        """(E, d loss / d E of the last step), both (V, 3, 4) float32 on the host, in the fitter's view order (rows of
+        exposure_fixed: E as it started, a zero gradient)."""
+        if not self.exposure:
+            raise ValueError("exposure_state: the fitter was made without exposure")
+        self.graph_sync()
+        return self._expo.detach().cpu().clone(), self._expo_grad.detach().cpu().reshape(-1, 3, 4).clone()
+
+    def set_exposures(self, E) -> None:
+        """Replace every view's exposure matrix: (V, 3, 4), e.g. `exposure` of an earlier fit's exposures.npz (the rows
+        of exposure_fixed too: they stay where this puts them).  The exposure Adam's moments are kept."""
+        if not self.exposure:
+            raise ValueError("set_exposures: the fitter was made without exposure")
+        E = torch.as_tensor(E, dtype=torch.float32)
+        if tuple(E.shape) != tuple(self._expo.shape):
+            raise ValueError(f"set_exposures: expected shape {tuple(self._expo.shape)}, got {tuple(E.shape)}")
+        self.graph_sync()
+        with torch.no_grad():
+            self._expo.copy_(E.to(self._expo.device))
+
     def _background(self, device) -> torch.Tensor:
         # one persistent tensor: the renderer reads its value on the host once, not per view
         if getattr(self, "_bg", None) is None or self._bg.device != device:
@@ -986,6 +1061,15 @@ class ViewShardedFitter:
         pred, alpha, depth = self.render_fn(means, scales, colors, opacities, cam, self.width, self.height,
                                             self._background(device), **kw)
         use_sil = self.masks is not None and self.w_sil > 0.0
+        if self.exposure:
+            # the photometric term (L1 and D-SSIM alike) compares the exposed colour pred @ E[:, :3].T + E[:, 3] with
+            # the target: formed channel by channel (element-wise products and sums, whose backward reduces over the
+            # pixels; as a matrix product its backward would be a (3, HW) x (HW, 3) BLAS call per view) and kept in the
+            # render's own memory layout (the loss's reductions then sum in the order they have without exposure, and
+            # identity E gives that fit's bits)
+            E = self._exposure_leaf(i).to(pred.device)
+            y = pred[..., 0:1] * E[:, 0] + pred[..., 1:2] * E[:, 1] + pred[..., 2:3] * E[:, 2] + E[:, 3]
+            pred = torch.empty_like(pred).copy_(y)
         if self.w_dssim > 0.0:
             # (1 - l) L1 + l D-SSIM for the photometric term; the silhouette term as below
             lam = self.w_dssim
@@ -1163,6 +1247,8 @@ class ViewShardedFitter:
         out = self._finish_step(loss)
         if self.refine_cameras:  # autograd delivered d loss / d xi through pose_view (view_loss)
             self._camera_step_autograd()
+        if self.exposure:  # ... and d loss / d E through the exposed colour
+            self._exposure_step_autograd()
         return out
 
     def _native_exec(self) -> bool:
@@ -2291,6 +2377,17 @@ def main(argv=None) -> None:
     ap.add_argument("--camera_fix", default="0",
                     help="with --refine_cameras: comma list of training-view indices whose poses stay as given (they pin "
                          "the scene's frame), or 'none'")
+    ap.add_argument("--exposure", action="store_true",
+                    help="fit a 3x4 exposure / white-balance transform per training view with the Gaussians (from "
+                         "identity; the photometric term compares the transformed render with the target) and write "
+                         "exposures.npz; host tensors only (--device cpu); held-out metrics (--holdout_every) are taken "
+                         "without exposure: held-out views have none, and the metric is of the image rendered from the "
+                         "saved Gaussians")
+    ap.add_argument("--exposure_lr", type=float, default=1e-3,
+                    help="with --exposure: Adam's learning rate of the exposure matrices")
+    ap.add_argument("--exposure_fix", default="0",
+                    help="with --exposure: comma list of training-view indices whose exposure stays at identity (they pin "
+                         "the overall brightness), or 'none'")
     ap.add_argument("--device", default="", help="cpu: host tensors (cpu_renderer, gloo); default: the HIP device")
     args = ap.parse_args(argv)
 
@@ -2362,6 +2459,10 @@ def main(argv=None) -> None:
         if rank == 0 and hold:
             print(f"refine_cameras: the {len(hold)} held-out views keep their input poses; the held-out metrics are "
                   "taken at those poses")
+    if args.exposure:
+        fix = args.exposure_fix.strip().lower()
+        fixed = () if fix in ("none", "") else tuple(int(x) for x in fix.split(","))
+        refine.update(exposure=True, exposure_lr=args.exposure_lr, exposure_fixed=fixed)
     params = build_params(args.num_gaussians, device, args.use_sh, args.sh_degree)
     fitter = ViewShardedFitter(params, cams, targets, args.width, args.height, lr=args.lr, masks=masks, depths=depths,
                                silhouette_weight=args.silhouette_weight, depth_weight=args.depth_weight,
@@ -2440,6 +2541,8 @@ def save_outputs(fitter: ViewShardedFitter, cams, args, out_dir: Path, loss_log,
         np.savez(out_dir / "cameras_refined.npz",
                  view=np.stack([c.view.detach().cpu().numpy().astype(np.float32) for c in cams]),
                  proj=np.stack([c.proj.detach().cpu().numpy().astype(np.float32) for c in cams]))
+    if getattr(args, "exposure", False):  # the training views' exposure matrices, in their order
+        np.savez(out_dir / "exposures.npz", exposure=fitter.exposure_state()[0].numpy().astype(np.float32))
     with torch.no_grad():
         pred0 = tr.render_gaussians_torch(means, scales, sh if sh is not None else colors, opacities, cams[0],
                                           width=args.width, height=args.height,
