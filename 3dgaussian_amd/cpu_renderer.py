@@ -199,3 +199,33 @@ def render(means, scales, colors, opacities, view, proj, width: int, height: int
     sy = (scales[:, 1].abs() * 0.5 * height * fy / za).clamp_min(1.0)
     ov = opacities.clamp_min(0.0) * valid.to(opacities.dtype)
     return _Splat.apply(px, py, sx, sy, ov, col, za, background, width, height)
+
+
+def peak_contribution(means, scales, opacities, view, proj, width: int, height: int) -> torch.Tensor:
+    """Per Gaussian, its largest blend weight in one view: ``peak[i] = max_p w_i(p) / (1 + W(p))`` over all pixels,
+    ``w`` the render's weights and ``W`` their sum (the dense definition: every Gaussian at every pixel, no gradient).
+    Compositing is ``out = clamp((bg + sum w c) / (1 + W))``, so removing Gaussian i moves no channel of any pixel of
+    this view by more than ``peak[i] / (1 - peak[i])``.  (N,) in the tensors' dtype; chunked over the Gaussians."""
+    with torch.no_grad():
+        means, scales, opacities = means.detach(), scales.detach(), opacities.detach()
+        view = view.to(dtype=means.dtype, device=means.device)
+        proj = proj.to(dtype=means.dtype, device=means.device)
+        px, py, valid, za = _project(means, view, proj, width, height)
+        fx, fy = proj[0, 0].abs(), proj[1, 1].abs()
+        sx = (scales[:, 0].abs() * 0.5 * width * fx / za).clamp_min(1.0)
+        sy = (scales[:, 1].abs() * 0.5 * height * fy / za).clamp_min(1.0)
+        ov = opacities.clamp_min(0.0) * valid.to(opacities.dtype)
+        n = means.shape[0]
+        Wt = torch.zeros((height, width), dtype=means.dtype, device=means.device)
+        for a, b in _chunks(n, width, height):
+            _, _, ex, ey = _factors(px[a:b], py[a:b], sx[a:b], sy[a:b], width, height)
+            Wt += ey.t() @ (ov[a:b, None] * ex)
+        r = 1.0 / (1.0 + Wt)
+        peak = torch.zeros((n,), dtype=means.dtype, device=means.device)
+        g = max(1, min(n, _CHUNK_ELEMS // max(1, width * height)))
+        for a in range(0, n, g):
+            b = min(n, a + g)
+            _, _, ex, ey = _factors(px[a:b], py[a:b], sx[a:b], sy[a:b], width, height)
+            w = ov[a:b, None, None] * ey[:, :, None] * ex[:, None, :]
+            peak[a:b] = (w * r[None]).flatten(1).max(dim=1).values
+    return peak

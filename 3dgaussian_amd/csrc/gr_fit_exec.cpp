@@ -17,6 +17,7 @@
 // so both give bit-identical losses and gradients (tests/test_fit_exec_gpu.py).
 // gr_eval_views is the same schedule without a backward: per view gr_fwd_render (saved sums only) and gr_eval_view, with a
 // partial-sum workspace per render stream; it writes nothing but those workspaces and the caller's metrics.
+// gr_contrib_views is gr_eval_views with gr_contrib_view in place of gr_eval_view: every view into the caller's one peak buffer.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -83,6 +84,7 @@ struct Buf {
 struct StreamWs {  // one render stream's buffers
   Buf bins, scratch, ws, saved;
   Buf eval;                      // gr_eval_views: the view metrics' partial sums
+  Buf contrib;                   // gr_contrib_views: the pairs' peak blend weights
   Buf cam;                       // gr_executor_camera_grads: a batch's camera-gradient partials
   std::vector<Buf> sums, sums3;  // one per view of a reduction batch (sums3: the depth-loss path's depth sums)
 };
@@ -123,12 +125,13 @@ struct gr_executor {
 static gr_status fit_views_on_device(gr_executor* ex, const gr_fit_config* cfg, int num_views, const gr_fit_target* views,
                                      int n, const float* means, const float* scales, const float* colors, int color_dim,
                                      const float* opacities, float w_sil, float w_depth, float g_scale, float w_dssim,
-                                     float* losses, float* const* acc, void* stream, float* metrics = nullptr);
+                                     float* losses, float* const* acc, void* stream, float* metrics = nullptr,
+                                     float* peak = nullptr);
 static gr_status enqueue_views(gr_executor* ex, const gr_fit_config* cfg, int num_views, const gr_fit_target* views, int n,
                                const float* means, const float* scales, const float* colors, int color_dim,
                                const float* opacities, float w_sil, float w_depth, float g_scale, float w_dssim, float* losses,
                                float* const* acc, const Sched& sc, const std::vector<hipStream_t>& st, hipStream_t prep,
-                               bool depth, int nslots, int& ngroups, float* metrics);
+                               bool depth, int nslots, int& ngroups, float* metrics, float* peak);
 
 extern "C" {
 
@@ -166,6 +169,7 @@ void gr_executor_destroy(gr_executor* ex) {
     w.ws.release();
     w.saved.release();
     w.eval.release();
+    w.contrib.release();
     w.cam.release();
     for (auto& b : w.sums) b.release();
     for (auto& b : w.sums3) b.release();
@@ -266,20 +270,44 @@ gr_status gr_eval_views(gr_executor* ex, const gr_fit_config* cfg, int num_views
   return st;
 }
 
+gr_status gr_contrib_views(gr_executor* ex, const gr_fit_config* cfg, int num_views, const gr_fit_target* views, int n,
+                           const float* means, const float* scales, const float* colors, int color_dim,
+                           const float* opacities, float* peak, void* stream) {
+  if (!ex || !cfg || (num_views > 0 && (!views || !peak)))
+    return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, "gr_contrib_views: null argument");
+  if (cfg->num_streams < 1 || cfg->prep_ahead < 1 || cfg->prep_group < 1 || cfg->prep_group > GR_PREPARE_MAX_VIEWS ||
+      cfg->prep_first < 1 || cfg->prep_first > GR_PREPARE_MAX_VIEWS)
+    return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, "gr_contrib_views: configuration out of range");
+  if (cfg->caps) return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, "gr_contrib_views: device-side sizing (caps) is not supported");
+  if (num_views <= 0 || n <= 0) return GR_OK;
+  gr_fit_config c = *cfg;  // no reductions: the batch settings are ignored
+  c.reduce_batch = 1;
+  c.reduce_tail = 0;
+  int prev_dev = 0;
+  GR_EXEC_TRY(hipGetDevice(&prev_dev));
+  GR_EXEC_TRY(hipSetDevice(ex->device));
+  const gr_status st = fit_views_on_device(ex, &c, num_views, views, n, means, scales, colors, color_dim, opacities, 0.0f, 0.0f,
+                                           1.0f, 0.0f, nullptr, nullptr, stream, nullptr, peak);
+  (void)hipSetDevice(prev_dev);
+  return st;
+}
+
 }  // extern "C"
 
 static gr_status fit_views_on_device(gr_executor* ex, const gr_fit_config* cfg, int num_views, const gr_fit_target* views,
                                      int n, const float* means, const float* scales, const float* colors, int color_dim,
                                      const float* opacities, float w_sil, float w_depth, float g_scale, float w_dssim,
-                                     float* losses, float* const* acc, void* stream, float* metrics) {
-  // metrics: gr_eval_views' form (no losses, accumulators or statistics: per view the render and gr_eval_view)
-  const bool depth = !metrics && views[0].target_depth != nullptr;
+                                     float* losses, float* const* acc, void* stream, float* metrics, float* peak) {
+  // metrics: gr_eval_views' form (no losses, accumulators or statistics: per view the render and gr_eval_view);
+  // peak: gr_contrib_views' (the same with gr_contrib_view)
+  const bool fwd_only = metrics || peak;
+  const bool depth = !fwd_only && views[0].target_depth != nullptr;
   const Sched sc = schedule(num_views, *cfg);
   const int ns = sc.ns;
-  for (int k = 0; !metrics && k < ns; ++k)
+  for (int k = 0; !fwd_only && k < ns; ++k)
     for (int q = 0; q < 4; ++q)
       if (!acc[4 * k + q]) return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, "gr_fit_views: null accumulator");
-  for (int k = 0; !metrics && ex->stats && k < ns; ++k)
+  for (int k = 0; !fwd_only && ex->stats && k < ns; ++k)
     if (!ex->stats[k]) return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, "gr_fit_views: null density stats buffer");
   hipStream_t main = (hipStream_t)stream;
   // streams, events and the plan array, grown on demand and kept
@@ -294,7 +322,7 @@ static gr_status fit_views_on_device(gr_executor* ex, const gr_fit_config* cfg, 
     ex->done.push_back(e);
   }
   if ((int)ex->ws.size() < ns) ex->ws.resize(ns);
-  for (int k = 0; !metrics && k < ns; ++k)
+  for (int k = 0; !fwd_only && k < ns; ++k)
     if ((int)ex->ws[k].sums.size() < cfg->reduce_batch) {
       ex->ws[k].sums.resize(cfg->reduce_batch);
       ex->ws[k].sums3.resize(cfg->reduce_batch);
@@ -349,7 +377,7 @@ static gr_status fit_views_on_device(gr_executor* ex, const gr_fit_config* cfg, 
       (void)hipStreamSynchronize(prep);
   };
   const gr_status status = enqueue_views(ex, cfg, num_views, views, n, means, scales, colors, color_dim, opacities, w_sil,
-                                         w_depth, g_scale, w_dssim, losses, acc, sc, st, prep, depth, nslots, ngroups, metrics);
+                                         w_depth, g_scale, w_dssim, losses, acc, sc, st, prep, depth, nslots, ngroups, metrics, peak);
   join();
   return status;
 }
@@ -358,7 +386,8 @@ static gr_status enqueue_views(gr_executor* ex, const gr_fit_config* cfg, int nu
                                const float* means, const float* scales, const float* colors, int color_dim,
                                const float* opacities, float w_sil, float w_depth, float g_scale, float w_dssim, float* losses,
                                float* const* acc, const Sched& sc, const std::vector<hipStream_t>& st, hipStream_t prep,
-                               bool depth, int nslots, int& ngroups, float* metrics) {
+                               bool depth, int nslots, int& ngroups, float* metrics, float* peak) {
+  const bool fwd_only = metrics || peak;  // gr_eval_views / gr_contrib_views: no backward, no reductions
   const int ns = sc.ns;
   const bool sized = cfg->caps != nullptr;  // device-side sizing: the plans are capacities, nothing to wait for
   const size_t geom_bytes = gr_geom_bytes(n);
@@ -457,7 +486,7 @@ static gr_status enqueue_views(gr_executor* ex, const gr_fit_config* cfg, int nu
     StreamWs& W = ex->ws[k];
     GR_EXEC_TRY(W.bins.fit(bins_bytes, s));
     GR_EXEC_TRY(W.scratch.fit(scratch_bytes, s));
-    if (!metrics) GR_EXEC_TRY(W.ws.fit(ws_bytes, s));
+    if (!fwd_only) GR_EXEC_TRY(W.ws.fit(ws_bytes, s));
     void *bins = W.bins.p, *scratch = W.scratch.p, *ws = W.ws.p;
     if (metrics) {
       // gr_eval_views: the saved sums only (no image, no depth output), then the view's metrics from them
@@ -467,6 +496,13 @@ static gr_status enqueue_views(gr_executor* ex, const gr_fit_config* cfg, int nu
                                  nullptr, (float*)W.saved.p, s));
       GR_EXEC_CALL(gr_eval_view(&v, (const float*)W.saved.p, views[j].target_rgb, metrics + (size_t)GR_EVAL_METRICS * j,
                                 W.eval.p, W.eval.cap, s));
+    } else if (peak) {
+      // gr_contrib_views: the saved sums only, then the view's peak blend weights into the one buffer (atomic maxima)
+      GR_EXEC_TRY(W.saved.fit(gr_saved_floats(&v) * sizeof(float), s));
+      GR_EXEC_TRY(W.contrib.fit(gr_contrib_ws_bytes(&v, n, &plan), s));
+      GR_EXEC_CALL(gr_fwd_render(&v, n, &plan, geom[j], bins, W.bins.cap, scratch, W.scratch.cap, nullptr, nullptr,
+                                 nullptr, (float*)W.saved.p, s));
+      GR_EXEC_CALL(gr_contrib_view(&v, n, &plan, geom[j], bins, (const float*)W.saved.p, peak, W.contrib.p, W.contrib.cap, s));
     } else if (ssim) {
       // the saved sums only (no image: the D-SSIM forward stages the colours from them); sums3 with a depth target
       GR_EXEC_TRY(W.saved.fit(gr_saved_floats(&v) * sizeof(float), s));
@@ -508,7 +544,7 @@ static gr_status enqueue_views(gr_executor* ex, const gr_fit_config* cfg, int nu
     gsl.pending = true;
     geom[j] = nullptr;
     GR_EXEC_CALL(prepare_upto(j + cfg->prep_ahead));
-    if (!metrics && (int)pending[k].size() >= sizes[k].front()) {
+    if (!fwd_only && (int)pending[k].size() >= sizes[k].front()) {
       GR_EXEC_CALL(reduce_pending(k));
       if (sizes[k].size() > 1) sizes[k].pop_front();
     }

@@ -3949,6 +3949,80 @@ __global__ __launch_bounds__(256) void k_gather_view_views(VBatch<k_gather_view_
   k_gather_view_body<DEPTH>(a.n, a.offsets, a.pos_of, a.rows, a.sums, a.depth3, a.sums3, BI{lb % gx, lb / gx}, BI{gx, (B.first[vb + 1] - B.first[vb]) / gx});
 }
 
+// ------------------------------------------------------------------------------------------------
+// Peak blend weight per Gaussian (gr_contrib_view): peak[i] = max(peak[i], max_p w_i(p) / (1 + W(p))) over the pixels
+// of Gaussian i's kept pairs (core and tail lists alike), W the view's weight sums as the render saved them.
+// k_contrib_view: the splats' mapping, one workgroup per non-empty work item.  The tile's r(p) = 1 / (1 + W(p)) is
+// staged once in LDS (0 outside the image: such a pixel never wins); then one lane per pair of the item: the 16 + 16
+// separable factors exp2(qx dx^2), o exp2(qy dy^2) in plain f32 at the forward's pixel centres, and per tile row the
+// maximum of ex[x] r(x, y) against broadcast LDS reads, scaled by the row's factor (all factors are >= 0 and an f32
+// multiply is monotonic, so max_x (ey ex r) = ey max_x (ex r) exactly).  No cross-lane step: the pair's value goes to
+// vals[k], k its sorted position (a coalesced store).
+__global__ __launch_bounds__(256, 4) void k_contrib_view(ViewK v, const int4* __restrict__ items, const int* __restrict__ num_items,
+                                                      const int* __restrict__ pairs, const float4* __restrict__ rec,
+                                                      const float4* __restrict__ saved4, float* __restrict__ vals) {
+  __shared__ __attribute__((aligned(16))) float r[TP];
+  const int nfull = num_items[1];  // the non-empty items are listed first
+  if ((int)blockIdx.x >= nfull) return;
+  const int4 it = items[xcd_item(blockIdx.x, nfull)];
+  const int tile = it.x >> 1, k0 = it.y, k1 = it.z;
+  const int tx = tile % v.tiles_x, ty = tile / v.tiles_x;
+  const int tid = threadIdx.x;
+  {
+    const int x = tx * T + (tid & (T - 1)), y = ty * T + (tid >> 4);
+    r[tid] = x < v.W && y < v.H ? 1.0f / (1.0f + saved4[(size_t)y * v.W + x].x) : 0.0f;
+  }
+  __syncthreads();
+  for (int k = k0 + tid; k < k1; k += 256) {
+    // r is read from LDS in every round: hoisted out of the loop its 256 values took every register of the SIMD
+    asm volatile("" ::: "memory");
+    const int g = pairs[k];
+    const float4 a = rec[(size_t)REC4 * g];
+    const float o = rec[(size_t)REC4 * g + 1].x;
+    f32x2_t ex[T / 2];
+#pragma unroll
+    for (int j = 0; j < T / 2; ++j) {
+      const float dx0 = ((float)(tx * T + 2 * j) + 0.5f) - a.x, dx1 = ((float)(tx * T + 2 * j + 1) + 0.5f) - a.x;
+      ex[j] = f32x2_t{__builtin_amdgcn_exp2f((dx0 * a.z) * dx0), __builtin_amdgcn_exp2f((dx1 * a.z) * dx1)};
+    }
+    float m = 0.0f;
+#pragma unroll
+    for (int y = 0; y < T; ++y) {
+      const float dy = ((float)(ty * T + y) + 0.5f) - a.y;
+      const float ey = o * __builtin_amdgcn_exp2f((dy * a.w) * dy);
+      f32x2_t mm = {0.0f, 0.0f};
+#pragma unroll
+      for (int j = 0; j < T / 4; ++j) {
+        const float4 u = *reinterpret_cast<const float4*>(r + y * T + 4 * j);
+        mm = __builtin_elementwise_max(mm, ex[2 * j] * f32x2_t{u.x, u.y});
+        mm = __builtin_elementwise_max(mm, ex[2 * j + 1] * f32x2_t{u.z, u.w});
+      }
+      m = fmaxf(m, ey * fmaxf(mm.x, mm.y));
+    }
+    vals[k] = m;
+  }
+}
+
+// One lane per Gaussian: the maximum of its pairs' values (its core pairs, then its tail pairs, contiguous in
+// emission order; pos_of gives their sorted positions, as in k_gather_view) and one unsigned atomic maximum on the
+// float's bits into peak[i] (non-negative floats order as their bit patterns; the lanes of a wave address 256
+// contiguous bytes).  A maximum does not depend on the order of arrival, so the result is the same bits whichever
+// views, on whichever streams, share the buffer.  A Gaussian without pairs in this view is not touched.
+__global__ __launch_bounds__(256) void k_contrib_gather(int n, const Cnt2* __restrict__ offsets, const int* __restrict__ pos_of,
+                                                        const float* __restrict__ vals, unsigned* __restrict__ peak) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const Cnt2 o0 = offsets[i], o1 = offsets[i + 1];
+  const unsigned cc = o1.c() - o0.c(), tc = o1.t() - o0.t();
+  if (cc + tc == 0) return;
+  const int* pc = pos_of + o0.c();
+  const int* pt = pos_of + (size_t)offsets[n].c() + o0.t();
+  float m = 0.0f;
+  for (unsigned j = 0; j < cc; ++j) m = fmaxf(m, vals[pc[j]]);
+  for (unsigned j = 0; j < tc; ++j) m = fmaxf(m, vals[pt[j]]);
+  atomicMax(peak + i, __float_as_uint(m));
+}
+
 
 // Chain rule of up to GR_REDUCE_MAX_VIEWS views' gathered sums: one lane per Gaussian; the crw waves of a
 // Gaussian group take views u, u + crw, ... (crw = 4 from three views, else the view count, so that no
@@ -7034,6 +7108,44 @@ gr_status gr_eval_view(const gr_view* v, const float* saved, const float* target
   GR_HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(k_eval_final, dim3(1), dim3(256), 0, s, (const float*)ws, plane, vk.tiles_x * vk.tiles_y,
                      (int64_t)v->height * v->width * 3, metrics);
+  GR_HIP_TRY(hipGetLastError());
+  return GR_OK;
+}
+
+// Peak blend weights: one float per pair (k_contrib_view's values by sorted position).
+size_t gr_contrib_ws_bytes(const gr_view* v, int n, const gr_plan* plan) {
+  if (!v || !plan || n <= 0 || plan->num_pairs <= 0) return 0;
+  return align_up((size_t)plan->num_pairs * sizeof(float));
+}
+
+gr_status gr_contrib_view(const gr_view* v, int n, const gr_plan* plan, const void* geom, const void* bins, const float* saved,
+                          float* peak, void* ws, size_t ws_bytes, void* stream) {
+  gr_status st = check_view(v);
+  if (st != GR_OK) return st;
+  if (tile_of(v) != T)
+    return set_error(GR_ERR_INVALID_ARGUMENT, "gr_contrib_view: 32-pixel tiles (gr_view.tile = 32): 16-pixel tiles only");
+  if (v->rows > 0) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_contrib_view: a band of tile rows (gr_view.rows): whole views only");
+  if (v->device_counts)
+    return set_error(GR_ERR_INVALID_ARGUMENT, "gr_contrib_view: device-sized views (device_counts = 1) are not supported");
+  if (!plan) return set_error(GR_ERR_INVALID_ARGUMENT, "plan is null");
+  if (plan->num_pairs < 0) return set_error(GR_ERR_OVERFLOW, "pair count overflows int32");
+  if (n < 0) return set_error(GR_ERR_INVALID_ARGUMENT, "n must be >= 0");
+  if (!geom || !bins || !saved || !peak) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_contrib_view: null pointer");
+  if (n == 0 || plan->num_pairs == 0) return GR_OK;  // no pair: every peak stays
+  if (!ws) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_contrib_view: null pointer");
+  if (ws_bytes < gr_contrib_ws_bytes(v, n, plan)) return set_error(GR_ERR_WORKSPACE, "gr_contrib_view: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const ViewK vk = make_viewk(v);
+  const int vtiles = 2 * vk.tiles_x * vk.tiles_y;
+  const TileCfg tc = tile_cfg(v, plan->num_pairs);
+  const Geom g = geom_view((void*)geom, n);
+  const Bins b = bins_view((void*)bins, vtiles, plan->num_pairs, tc.ch);
+  hipLaunchKernelGGL(k_contrib_view, dim3((unsigned)item_cap(vtiles, plan->num_pairs, tc.ch)), dim3(256), 0, s, vk,
+                     (const int4*)b.items, (const int*)b.num_items, (const int*)b.pairs, (const float4*)g.rec,
+                     (const float4*)saved, (float*)ws);
+  GR_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_contrib_gather, dim3(blocks_for(n)), dim3(256), 0, s, n, (const Cnt2*)g.offsets, (const int*)b.pos_of,
+                     (const float*)ws, (unsigned*)peak);
   GR_HIP_TRY(hipGetLastError());
   return GR_OK;
 }

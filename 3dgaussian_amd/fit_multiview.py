@@ -197,19 +197,44 @@ def activations_native(params: dict, reg=None, ws=None):
     return means, scales, colors, opacities, out
 
 
-def densify_and_prune(params: dict, max_gaussians: int, densify_ratio: float, prune_opacity: float) -> dict:
+def prune_by_contribution(peak: torch.Tensor, threshold: float, min_keep: int = 64) -> torch.Tensor:
+    """The keep mask of contribution-based pruning: ``peak > threshold`` (ViewShardedFitter.contribution_state: each
+    Gaussian's largest blend weight w / (1 + W) over the training views' pixels; removing one with peak <= t moves no
+    training pixel by more than t / (1 - t)); if fewer than ``min_keep`` survive, the ``min_keep`` largest ``peak``
+    instead, ties to the lower index (the opacity rule's floor of 64)."""
+    keep = peak > threshold
+    if int(keep.sum()) < min_keep:
+        top = torch.sort(peak, descending=True, stable=True).indices[:min(min_keep, peak.shape[0])]
+        keep = torch.zeros_like(keep, dtype=torch.bool)
+        keep[top] = True
+    return keep
+
+
+def _keep_mask(keep: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
+    """A caller's keep mask for the densify rules: (N,) bool on the rule's device."""
+    if keep.dtype != torch.bool or tuple(keep.shape) != tuple(like.shape):
+        raise ValueError(f"keep: expected a bool mask of shape {tuple(like.shape)}, got {keep.dtype} {tuple(keep.shape)}")
+    return keep.to(like.device)
+
+
+def densify_and_prune(params: dict, max_gaussians: int, densify_ratio: float, prune_opacity: float,
+                      keep: Optional[torch.Tensor] = None) -> dict:
     """fit_multiview_stub.py:140-197, evaluated on the host (CPU RNG for the jitter) so that every
-    rank that calls it with the same RNG state gets identical parameters."""
+    rank that calls it with the same RNG state gets identical parameters.  ``keep`` ((N,) bool, e.g.
+    prune_by_contribution's): the rows that survive, in place of the opacity rule and its floor of 64."""
     with torch.no_grad():
         cpu = {k: v.detach().cpu() for k, v in params.items()}
         means, scales_raw, op_raw = cpu["means"], cpu["scales_raw"], cpu["opacities_raw"]
         op = torch.sigmoid(op_raw)
         scales = torch.nn.functional.softplus(scales_raw) + 1e-3
-        keep = op > prune_opacity
-        if int(keep.sum()) < 64:
-            top_keep = torch.topk(op, k=min(64, op.shape[0]), largest=True).indices
-            keep = torch.zeros_like(keep, dtype=torch.bool)
-            keep[top_keep] = True
+        if keep is not None:
+            keep = _keep_mask(keep, op)
+        else:
+            keep = op > prune_opacity
+            if int(keep.sum()) < 64:
+                top_keep = torch.topk(op, k=min(64, op.shape[0]), largest=True).indices
+                keep = torch.zeros_like(keep, dtype=torch.bool)
+                keep[top_keep] = True
         means, scales_raw, op_raw, scales = means[keep], scales_raw[keep], op_raw[keep], scales[keep]
         op = torch.sigmoid(op_raw)
         n = means.shape[0]
@@ -234,23 +259,27 @@ def densify_and_prune(params: dict, max_gaussians: int, densify_ratio: float, pr
 
 
 def densify_and_prune_device(params: dict, max_gaussians: int, densify_ratio: float, prune_opacity: float,
-                             generator: Optional[torch.Generator] = None, noise: Optional[torch.Tensor] = None) -> dict:
+                             generator: Optional[torch.Generator] = None, noise: Optional[torch.Tensor] = None,
+                             keep: Optional[torch.Tensor] = None) -> dict:
     """The same rule as densify_and_prune (fit_multiview_stub.py:140-197) evaluated on the device, for
     fits at scale (config C5: millions of Gaussians), with the jitter drawn from a device generator:
     no host round trip of the parameters.  Same keep / top-k / jitter / -0.1 opacity / colour
     duplication; only the random stream differs from the stub's CPU one.  ``noise`` (>= added rows x 3,
     standard normal) replaces the generator's draw: with the stub's own draw the result is the host
-    rule's (tests/test_densify.py)."""
+    rule's (tests/test_densify.py).  ``keep``: as densify_and_prune's."""
     with torch.no_grad():
         means, scales_raw, op_raw = params["means"].detach(), params["scales_raw"].detach(), params["opacities_raw"].detach()
         key = "sh_raw" if "sh_raw" in params else "colors_raw"
         col = params[key].detach()
         op = torch.sigmoid(op_raw)
-        keep = op > prune_opacity
-        if int(keep.sum()) < 64:
-            top_keep = torch.topk(op, k=min(64, op.shape[0]), largest=True).indices
-            keep = torch.zeros_like(keep, dtype=torch.bool)
-            keep[top_keep] = True
+        if keep is not None:
+            keep = _keep_mask(keep, op)
+        else:
+            keep = op > prune_opacity
+            if int(keep.sum()) < 64:
+                top_keep = torch.topk(op, k=min(64, op.shape[0]), largest=True).indices
+                keep = torch.zeros_like(keep, dtype=torch.bool)
+                keep[top_keep] = True
         means, scales_raw, op_raw, col = means[keep], scales_raw[keep], op_raw[keep], col[keep]
         n = means.shape[0]
         room = max(0, max_gaussians - n)
@@ -273,11 +302,12 @@ def densify_and_prune_device(params: dict, max_gaussians: int, densify_ratio: fl
 
 def densify_by_gradient(params: dict, gsum: torch.Tensor, seen: torch.Tensor, grad_threshold: float, split_scale: float,
                         max_gaussians: int, prune_opacity: float, generator: Optional[torch.Generator] = None,
-                        noise: Optional[torch.Tensor] = None) -> dict:
+                        noise: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None) -> dict:
     """Adaptive density control (an extension: the stub's rule, densify_and_prune, duplicates the most opaque Gaussians)
     from the fit's density statistics (ViewShardedFitter.density_state: per Gaussian the sum over the views that saw it
     of the view loss's gradient norm w.r.t. its NDC position, and the number of those views), on the tensors' device:
-      1. prune as densify_and_prune (sigmoid(opacities_raw) > prune_opacity, else the 64 most opaque);
+      1. prune as densify_and_prune (sigmoid(opacities_raw) > prune_opacity, else the 64 most opaque; or the rows of
+         ``keep`` when given);
       2. avg = gsum / max(seen, 1); candidates: kept rows with seen > 0 and avg >= grad_threshold, at most
          max_gaussians - kept of them (each adds one row net), the largest avg first, ties to the lower index;
       3. with s = softplus(scales_raw) + 1e-3 and smax its larger screen-plane component (columns 0, 1, the two the
@@ -292,11 +322,14 @@ def densify_by_gradient(params: dict, gsum: torch.Tensor, seen: torch.Tensor, gr
         col = params[key].detach()
         dev = means.device
         op = torch.sigmoid(op_raw)
-        keep = op > prune_opacity
-        if int(keep.sum()) < 64:
-            top_keep = torch.topk(op, k=min(64, op.shape[0]), largest=True).indices
-            keep = torch.zeros_like(keep, dtype=torch.bool)
-            keep[top_keep] = True
+        if keep is not None:
+            keep = _keep_mask(keep, op)
+        else:
+            keep = op > prune_opacity
+            if int(keep.sum()) < 64:
+                top_keep = torch.topk(op, k=min(64, op.shape[0]), largest=True).indices
+                keep = torch.zeros_like(keep, dtype=torch.bool)
+                keep[top_keep] = True
         gsum, seen = gsum.to(dev), seen.to(dev)
         avg = gsum / seen.clamp_min(1.0)
         idx = torch.nonzero(keep & (seen > 0) & (avg >= grad_threshold)).flatten()
@@ -2230,19 +2263,135 @@ class ViewShardedFitter:
         return {"l1": l1, "mse": mse, "psnr": psnr, "ssim": ssim, "mean_l1": mean(l1), "mean_mse": mean(mse),
                 "mean_psnr": mean(psnr), "mean_ssim": mean(ssim)}
 
+    # ---- contribution (peak blend weight per Gaussian) ----------------------------------------------------------
+    def _contrib_native(self, m, s, c, o, gvs, peak) -> None:
+        """gr_contrib_views: the views' peak blend weights into ``peak`` through the native executor, one C call."""
+        device = m.device
+        ns = max(1, min(NUM_STREAMS, len(gvs)))
+        arr = (tr._native.GrFitTarget * len(gvs))()
+        for j, gv in enumerate(gvs):
+            arr[j].view = gv
+            arr[j].target_rgb = None
+            arr[j].target_mask = None
+            arr[j].target_depth = None
+        cfg = tr._native.GrFitConfig(NUM_STREAMS, PREP_AHEAD, PREP_GROUP, PREP_FIRST, REDUCE_BATCH, min(REDUCE_TAIL, REDUCE_BATCH))
+        if EXEC_STREAMS:  # the driver's own torch streams, as _views_native
+            side, prep = self._eval_streams(device, ns)
+            rs = (ctypes.c_void_p * max(1, ns - 1))(*[st.cuda_stream for st in side])  # (read during the call only)
+            cfg.render_streams = rs
+            cfg.prep_stream = prep.cuda_stream
+        tr._native.check(tr._native.lib().gr_contrib_views(
+            tr._native.executor(device.index or 0), ctypes.byref(cfg), len(gvs), arr, int(m.shape[0]), tr._native.ptr(m),
+            tr._native.ptr(s), tr._native.ptr(c), tr._color_dim(c), tr._native.ptr(o), tr._native.ptr(peak),
+            ctypes_stream(device)), "gr_contrib_views")
+        self._eval_keep = (m, s, c, o)  # read by the executor's streams until the caller's stream passes them
+
+    def _contrib_direct(self, m, s, c, o, gvs, peak) -> None:
+        """The Python schedule of the same calls (_eval_direct's): view j on render stream j % NUM_STREAMS,
+        forward_native (saved sums only) + contrib_view_native, every view into the one ``peak``."""
+        device = m.device
+        main = torch.cuda.current_stream(device)
+        ns = max(1, min(NUM_STREAMS, len(gvs)))
+        side, prep = self._eval_streams(device, ns)
+        streams = [main] + side
+        for st in streams[1:]:
+            st.wait_stream(main)
+        prep.wait_stream(main)
+        pins = self._plan_pins(len(gvs))
+        ahead: dict = {}
+        views = list(range(len(gvs)))
+        prepare_upto = self._prep_groups(views, ahead, lambda js: tr.prepare_views_native(
+            m, s, c, o, [gvs[q] for q in js], [pins[q] for q in js]), prep)
+        for j in views:
+            k = j % ns
+            prepare_upto(j)
+            pv = ahead.pop(j)
+            streams[k].wait_event(pv.event)
+            pv.geom.record_stream(streams[k])
+            with torch.cuda.stream(streams[k]):
+                _, _, _, rs = tr.forward_native(m, s, c, o, pv.gv, pv, images=False)
+                tr.contrib_view_native(rs, pv, peak)
+                pv = rs = None
+            prepare_upto(j + PREP_AHEAD)
+        for st in streams[1:]:
+            main.wait_stream(st)
+        main.wait_stream(prep)
+
+    def contribution_state(self, cams: Optional[list] = None) -> torch.Tensor:
+        """Per Gaussian in canonical order (as canonical_params), its peak blend weight: the maximum over the views
+        ``cams`` (default: the training cameras) and their pixels of w / (1 + W), its share of the pixel under this
+        renderer's weighted-average compositing.  Removing Gaussian i alone moves no pixel of those views by more than
+        peak[i] / (1 - peak[i]) in any channel.  (N,) float32 on the parameters' device.
+        The views are rendered as evaluate() renders them (16-pixel tiles, the 7-sigma footprint, the step's own
+        activations).  A collective: view i belongs to rank i % world, the ranks meet in one all-reduce (MAX: exact),
+        every rank returns the same tensor.  On the HIP device through gr_contrib_view (the native executor's
+        gr_contrib_views where the fit step uses it, else a Python schedule of the same calls); on other devices
+        cpu_renderer.peak_contribution.  Changes nothing of the fit."""
+        self.graph_sync()
+        cams = self.cams if cams is None else cams
+        device = self.params["means"].device
+        n = int(self.params["means"].shape[0])
+        mine = list(range(self.rank, len(cams), self.world))
+        peak = torch.zeros((n,), dtype=torch.float32, device=device)
+        with torch.no_grad():
+            if mine and n > 0:
+                m, s, c, o = (t.detach().float().contiguous() for t in self._eval_activations(device))
+                if device.type == "cuda":
+                    gvs = [self._eval_view(cams[i], device) for i in mine]
+                    if self._native_exec() and GATHER:
+                        self._contrib_native(m, s, c, o, gvs, peak)
+                    else:
+                        self._contrib_direct(m, s, c, o, gvs, peak)
+                else:
+                    from . import cpu_renderer
+                    for i in mine:
+                        peak = torch.maximum(peak, cpu_renderer.peak_contribution(m, s, o, cams[i].view, cams[i].proj,
+                                                                                  self.width, self.height))
+        if self.world > 1:
+            dist.all_reduce(peak, op=dist.ReduceOp.MAX, group=self.group)
+        if self.perm is not None:
+            canon = torch.empty_like(peak)
+            canon[self.perm] = peak
+            peak = canon
+        return peak
+
     def densify_and_prune(self, max_gaussians: int, densify_ratio: float, prune_opacity: float,
                           on_device: Optional[bool] = None, mode: str = "opacity", grad_threshold: float = 0.0002,
-                          split_scale: float = 0.01) -> None:
+                          split_scale: float = 0.01, prune_mode: str = "opacity",
+                          prune_contribution: float = 1.0 / 510.0) -> None:
         """on_device (default: N >= DEVICE_DENSIFY_MIN): the device-side rule with a device generator
         (densify_and_prune_device); otherwise the host rule with the stub's CPU random stream.
         mode "gradient" (a fitter with density_stats): densify_by_gradient on the statistics since the last call, on
         the parameters' device with its generator (densify_ratio <= 0: prune only); the same rank-0-decides flow.
-        Either mode leaves the statistics zeroed at the new size."""
+        Either mode leaves the statistics zeroed at the new size.
+        prune_mode "contribution": the rows that survive are prune_by_contribution(contribution_state(),
+        prune_contribution) instead of the opacity rule's (whichever densify mode is active; prune_opacity is then only
+        counted for the report).  The default threshold 1 / 510 bounds the change of any training pixel by half an
+        8-bit level (t / (1 - t) = 1 / 509) per removed Gaussian.  Fills self.contribution_report."""
         if mode not in ("opacity", "gradient"):
             raise ValueError(f"densify mode must be 'opacity' or 'gradient', got {mode!r}")
+        if prune_mode not in ("opacity", "contribution"):
+            raise ValueError(f"prune mode must be 'opacity' or 'contribution', got {prune_mode!r}")
         self.graph_sync()
         state = self.density_state() if mode == "gradient" else None  # (a collective: before rank 0 decides)
         n_now = int(self.params["means"].shape[0])
+        keep = None
+        if prune_mode == "contribution":
+            peak = self.contribution_state()  # (a collective too)
+            keep = prune_by_contribution(peak, prune_contribution)
+            pk = peak.float().cpu()
+            qs = torch.quantile(pk, torch.tensor([0.01, 0.1, 0.5])).tolist() if pk.numel() else [0.0] * 3
+            op_c = torch.empty_like(self.params["opacities_raw"].detach())
+            if self.perm is not None:
+                op_c[self.perm] = self.params["opacities_raw"].detach()
+            else:
+                op_c.copy_(self.params["opacities_raw"].detach())
+            by_op = torch.sigmoid(op_c) <= prune_opacity
+            self.contribution_report = {"n": n_now, "p1": qs[0], "p10": qs[1], "p50": qs[2],
+                                        "threshold": float(prune_contribution),
+                                        "at_or_below": int((peak <= prune_contribution).sum()),
+                                        "pruned": int((~keep).sum()), "opacity_would_prune": int(by_op.sum()),
+                                        "both": int((by_op & ~keep.to(by_op.device)).sum())}
         if mode == "gradient":
             on_device = True
             # what the threshold is compared with, for the caller's log: percentiles of avg over the seen Gaussians
@@ -2260,11 +2409,11 @@ class ViewShardedFitter:
             base = self.canonical_params()
             if mode == "gradient":
                 newp = densify_by_gradient(base, state[0], state[1], grad_threshold if densify_ratio > 0.0 else math.inf,
-                                           split_scale, max_gaussians, prune_opacity, self._dgen)
+                                           split_scale, max_gaussians, prune_opacity, self._dgen, keep=keep)
             elif on_device:
-                newp = densify_and_prune_device(base, max_gaussians, densify_ratio, prune_opacity, self._dgen)
+                newp = densify_and_prune_device(base, max_gaussians, densify_ratio, prune_opacity, self._dgen, keep=keep)
             else:
-                newp = densify_and_prune(base, max_gaussians, densify_ratio, prune_opacity)
+                newp = densify_and_prune(base, max_gaussians, densify_ratio, prune_opacity, keep=keep)
             perm = None
             if self.reorder and newp["means"].shape[0] >= 2:
                 perm = morton_order(newp["means"])
@@ -2339,6 +2488,14 @@ def main(argv=None) -> None:
     ap.add_argument("--prune_interval", type=int, default=80)
     ap.add_argument("--densify_ratio", type=float, default=0.15)
     ap.add_argument("--prune_opacity", type=float, default=0.05)
+    ap.add_argument("--prune_mode", choices=("opacity", "contribution"), default="opacity",
+                    help="opacity: the reference's rule (sigmoid(opacity) > --prune_opacity); contribution: keep a Gaussian "
+                         "whose peak blend weight w / (1 + W) over the training views' pixels exceeds --prune_contribution "
+                         "(what it owns of its best pixel under this renderer's weighted-average compositing)")
+    ap.add_argument("--prune_contribution", type=float, default=1.0 / 510.0,
+                    help="contribution mode: the peak blend weight t at or below which a Gaussian is pruned.  Removing one "
+                         "such Gaussian moves no training pixel by more than t / (1 - t); the default 1/510 makes that "
+                         "1/509, half an 8-bit level.  A bound per removed Gaussian, not a measured quality result")
     ap.add_argument("--densify_mode", choices=("opacity", "gradient"), default="opacity",
                     help="opacity: the reference's rule (duplicate the most opaque Gaussians); gradient: adaptive density "
                          "control from each Gaussian's accumulated screen-space positional gradient (clone small, split "
@@ -2498,7 +2655,14 @@ def main(argv=None) -> None:
                                      args.densify_ratio if (it + 1) % args.densify_interval == 0 else 0.0,
                                      args.prune_opacity, mode=args.densify_mode,
                                      grad_threshold=args.densify_grad_threshold,
-                                     split_scale=args.densify_percent_dense * extent)
+                                     split_scale=args.densify_percent_dense * extent, prune_mode=args.prune_mode,
+                                     prune_contribution=args.prune_contribution)
+            if rank == 0 and args.prune_mode == "contribution":
+                r = fitter.contribution_report
+                print(f"prune at iter {it + 1}: peak blend weight of {r['n']} Gaussians: p1={r['p1']:.3e} p10={r['p10']:.3e} "
+                      f"p50={r['p50']:.3e}, {r['at_or_below']} at or below {r['threshold']:.3e} ({r['pruned']} pruned); the "
+                      f"opacity rule ({args.prune_opacity:g}) would have pruned {r['opacity_would_prune']} ({r['both']} in "
+                      f"common); N -> {fitter.params['means'].shape[0]}")
             if rank == 0 and args.densify_mode == "gradient":
                 r = fitter.density_report
                 print(f"densify at iter {it + 1}: avg gradient over {r['seen']} of {r['n']} Gaussians seen: p50={r['p50']:.3e} "

@@ -906,6 +906,24 @@ def eval_view_native(st: RenderState, target, metrics_out) -> None:
                                  _native.ptr(ws), ws.numel(), _stream(dev)), "gr_eval_view")
 
 
+def contrib_view_native(rs: RenderState, pv: Prepared, peak) -> None:
+    """gr_contrib_view on the current stream: ``peak`` ((n,) float32 on the device, zeroed by the caller) takes, per
+    Gaussian, the maximum of its value and the Gaussian's largest blend weight w / (1 + W) over the pixels of its kept
+    pairs in this view.  ``rs``: the ``forward_native`` state of the view (its bins and saved sums; with or without
+    images, 16-pixel tiles, a whole view); ``pv``: the ``Prepared`` it was rendered from (its geom: the raster records
+    and the pairs' offsets).  Calls accumulate across views, in any order and from any streams."""
+    L = _native.lib()
+    dev = rs.saved.device
+    if pv.n != rs.n or pv.gv.width != rs.gv.width or pv.gv.height != rs.gv.height:
+        raise ValueError("prepared view does not match the render state (Gaussian count or image size)")
+    _check_operand(peak, (rs.n,), "peak", dev)
+    ws = torch.empty((int(L.gr_contrib_ws_bytes(ctypes.byref(rs.gv), rs.n, ctypes.byref(rs.plan))),), dtype=torch.uint8,
+                     device=dev)
+    _native.check(L.gr_contrib_view(ctypes.byref(rs.gv), rs.n, ctypes.byref(rs.plan), _native.ptr(pv.geom),
+                                    _native.ptr(rs.bins), _native.ptr(rs.saved), _native.ptr(peak), _native.ptr(ws),
+                                    ws.numel(), _stream(dev)), "gr_contrib_view")
+
+
 def _grad_background(st: RenderState, background: torch.Tensor, g_out: torch.Tensor) -> torch.Tensor:
     """d(out)/d(bg) = sum_p g_out * [0<=out_r<=1] / (1+W)  (torch_renderer.py:194-196)."""
     HW = st.gv.width * st.gv.height
@@ -1277,4 +1295,5 @@ __all__ = ["Camera", "get_default_device", "perspective", "look_at", "render_gau
            "make_view", "prepare_view", "prepare_native", "Prepared", "forward_native", "backward_native",
            "backward_l1_native", "backward_fit_native", "backward_fit_gather_native", "forward_l1_native", "backward_splat_native", "reduce_views_native",
            "gather_view_native", "reduce_sums_native", "density_stats_native", "camera_grads_sums_native", "eval_view_native",
+           "contrib_view_native",
            "DEFAULT_CUTOFF", "DEPTH_GRAD_CUTOFF", "DEFAULT_CORE_CUTOFF", "FIT_CUTOFF", "default_cutoff"]

@@ -507,6 +507,40 @@ gr_status gr_eval_views(gr_executor* executor, const gr_fit_config* config, int 
                         const float* colors, int color_dim, const float* opacities,
                         float* metrics /* device [num_views][GR_EVAL_METRICS] */, void* stream);
 
+/* Peak blend weight per Gaussian, for contribution-based pruning (an extension: the reference prunes by opacity).
+ * Compositing is out = clamp((bg + sum w c) / (1 + W)), so a Gaussian's share of pixel p is its blend weight
+ * b = w(p) / (1 + W(p)); removing the Gaussian moves no channel of that pixel by more than b / (1 - b).
+ *   peak[i] = max(peak[i], max_p w_i(p) / (1 + W(p)))
+ * over the in-image pixels p of every kept (Gaussian i, tile) pair of the view, core and tail lists alike;
+ * w_i(p) = o exp2(qx dx^2 + qy dy^2) from the raster record of geom at the forward's pixel centres, in plain f32
+ * whatever the view's precision mode; W(p) the weight sums in `saved`, as gr_fwd_render / gr_fwd_render_saved of the
+ * same view, plan and bins left them.  A pixel outside a Gaussian's kept tiles has w < o exp(-cutoff^2 / 2).
+ *   - the caller zeroes peak ([n] float32, device); calls accumulate across views.  A Gaussian without pairs (behind
+ *     the camera, off screen, opacity <= 0) keeps its value
+ *   - two launches: one workgroup per work item writes each pair's maximum into ws (one float per pair), then one lane
+ *     per Gaussian takes the maximum of its pairs and issues one unsigned atomic maximum on the float's bit pattern
+ *   - several streams may share one peak buffer (unlike gr_density_stats, whose float sums are read-modify-write
+ *     without atomics and depend on order): peak is only ever updated by atomic maxima of non-negative floats, which
+ *     commute and lose nothing, so the result is bit-identical for any order of views and any assignment to streams
+ *   - the view: 16-pixel tiles, whole, device_counts = 0 (tile = 32, rows > 0, device_counts = 1:
+ *     GR_ERR_INVALID_ARGUMENT); null pointers: GR_ERR_INVALID_ARGUMENT; ws shorter than gr_contrib_ws_bytes:
+ *     GR_ERR_WORKSPACE (nothing is launched on a refusal); n == 0 or a plan without pairs: no-op, nothing launched,
+ *     ws may be null
+ *   - stream-ordered, no allocation, deterministic */
+size_t gr_contrib_ws_bytes(const gr_view* v, int n, const gr_plan* plan); /* 0 for a plan without pairs */
+gr_status gr_contrib_view(const gr_view* v, int n, const gr_plan* plan, const void* geom, const void* bins,
+                          const float* saved, float* peak /* [n], device */, void* ws, size_t ws_bytes, void* stream);
+/* gr_contrib_view over several views of the same Gaussians: gr_eval_views' schedule with gr_contrib_view in place of
+ * gr_eval_view (per view gr_fwd_render keeping the saved sums only, then gr_contrib_view into the one peak buffer,
+ * view j on render stream j % num_streams).  The targets of `views` are ignored and may be NULL; config->caps must be
+ * NULL.  The caller zeroes peak.  The executor's accumulators, density statistics and camera rows are left untouched.
+ * Ordered after and before `stream` as gr_fit_views; n == 0 or num_views == 0: no-op.  Bit-identical to per-view
+ * gr_fwd_render + gr_contrib_view calls in any order. */
+gr_status gr_contrib_views(gr_executor* executor, const gr_fit_config* config, int num_views,
+                           const gr_fit_target* views, int n, const float* means, const float* scales,
+                           const float* colors, int color_dim, const float* opacities, float* peak /* [n], device */,
+                           void* stream);
+
 /* ------------------------------------------------------------------------------------------ */
 /* Legacy uint8 surface (host pointers), replaces gr::render_gaussians (renderer.h:33-39).    */
 /* Semantics of renderer_cpu.cpp: 3-sigma box, w < 1e-5 skip, uint8 round-half-up, A = 255.  */
