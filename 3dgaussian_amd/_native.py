@@ -233,6 +233,7 @@ _SIG = {
     "gr_render_u8": (ctypes.c_int, [ctypes.POINTER(GrRenderParams), ctypes.c_int, _P, _P, _P, _P, _P]),
     "gr_geom_layout": (None, [ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
     "gr_bins_layout": (None, [_VP, ctypes.c_int, _PP, ctypes.POINTER(ctypes.c_size_t)]),
+    "gr_items_layout": (None, [_VP, ctypes.c_int, _PP, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int)]),
     "gr_profile_begin": (None, []),
     "gr_profile_end": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)]),
     "gr_l1_loss_ws_bytes": (ctypes.c_size_t, []),
@@ -325,6 +326,16 @@ def bins_layout(gv: GrView, n: int, num_pairs: int):
     plan = GrPlan(int(num_pairs), 0, 0)
     lib().gr_bins_layout(ctypes.byref(gv), int(n), ctypes.byref(plan), out)
     return list(out)
+
+
+def items_layout(gv: GrView, n: int, num_pairs: int):
+    """([items int4[cap], num_items int[2], tile_item0 int[2 tiles], ticket], work-item length)
+    (gr_hip.h gr_items_layout)."""
+    out = (ctypes.c_size_t * 4)()
+    ch = ctypes.c_int(0)
+    plan = GrPlan(int(num_pairs), 0, 0)
+    lib().gr_items_layout(ctypes.byref(gv), int(n), ctypes.byref(plan), out, ctypes.byref(ch))
+    return list(out), int(ch.value)
 
 
 _EXECUTORS: dict = {}

@@ -5428,6 +5428,18 @@ void gr_bins_layout(const gr_view* v, int n, const gr_plan* plan, size_t offsets
   offsets_out[3] = off[6];
 }
 
+void gr_items_layout(const gr_view* v, int n, const gr_plan* plan, size_t offsets_out[4], int* ch_out) {
+  (void)n;
+  size_t off[8];
+  const int ch = tile_cfg(v, plan ? plan->num_pairs : 0).ch;
+  bins_fixed(vtiles_of(v), plan ? plan->num_pairs : 0, off, ch);
+  offsets_out[0] = off[3];
+  offsets_out[1] = off[4];
+  offsets_out[2] = off[5];
+  offsets_out[3] = off[7];
+  if (ch_out) *ch_out = ch;
+}
+
 size_t gr_geom_bytes(int n) {
   size_t off[GR_GEOM_PARTS];
   return geom_fixed(n, off) + align_up(scan_tmp_bytes(n > 0 ? n : 1));

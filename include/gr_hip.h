@@ -691,6 +691,18 @@ gr_status gr_fit_views_batched(int num_views, const gr_batch_view* views, int n,
 void gr_geom_layout(int n, size_t offsets_out[GR_GEOM_PARTS]);
 void gr_bins_layout(const gr_view* v, int n, const gr_plan* plan, size_t offsets_out[4]);
 
+/* Byte offsets of the work-item part of bins (same layout function as the kernels' view of it), and in *ch_out
+ * (may be NULL) the work-item length in pairs that the view and the plan's pair count give:
+ *   [0] items int4[(K + ch - 1) / ch + 2 * tiles]: (virtual tile, k0, k1, chunk index); the non-empty tiles' items
+ *       in tile order, per tile its core chunks then its tail chunks, each [k0, min(k1, k0 + ch)); then one
+ *       (2t, 0, 0, 0) item per tile t that is empty in both zones
+ *   [1] num_items int[2]: all items, the non-empty ones
+ *   [2] tile_item0 int[2 * tiles]: first item of each virtual tile's list (an empty list: where it would start)
+ *   [3] ticket int[tiles]: arrivals of a split tile's items; then, from int index (tiles + 1 rounded up to a
+ *       multiple of 32), the fan-in counters: nine ints (eight shards and a top counter), one every 32 ints.
+ *       Zeroed by the binning and left zero by every launch that uses them. */
+void gr_items_layout(const gr_view* v, int n, const gr_plan* plan, size_t offsets_out[4], int* ch_out);
+
 /* Live kernel timing with HIP events on the launch stream (bench.py).  Between begin and end,
  * the timed stages are bracketed by two events each; end() synchronises them and returns the
  * summed device time and count of [0] the forward splat kernel, [1] the backward splat kernel,

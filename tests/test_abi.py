@@ -54,6 +54,34 @@ def test_layouts_are_aligned_and_ordered(pkg):
     assert b[3] > b[2]  # pos_of after the ranges
 
 
+def test_items_layout(pkg):
+    """gr_items_layout (host-only): the work-item part of bins follows the ranges (the tickets come last, behind pos_of), in
+    order and aligned, sized by the work-item length it reports (gr_view.chunk rounded up to 64; unset, 512 to the tile size's
+    default by the pair count)."""
+    np = __import__("numpy")
+    nat = pkg._native
+    n, K = 1000, 123456
+    for W, H, tile in ((800, 800, 0), (800, 800, 32), (112, 80, 0)):
+        gv = pkg.torch_renderer.make_view(np.eye(4, dtype="float32"), np.eye(4, dtype="float32"), W, H, depth_grad=False,
+                                          tile=tile)
+        te = tile or 16
+        tiles = ((W + te - 1) // te) * ((H + te - 1) // te)
+        for chunk, want in ((0, 512), (64, 64), (100, 128), (192, 192)):
+            gv.chunk = chunk
+            off, ch = nat.items_layout(gv, n, K)
+            b = nat.bins_layout(gv, n, K)
+            assert ch == want
+            assert off == sorted(off) and all(o % 256 == 0 for o in off)
+            # in order: ranges, items, num_items, tile_item0, pos_of, ticket
+            assert b[2] + 16 * tiles <= off[0] and off[2] + 8 * tiles <= b[3] < off[3]
+            assert off[1] - off[0] >= 16 * ((K + ch - 1) // ch + 2 * tiles)
+            assert off[2] - off[1] >= 8 and off[3] - off[2] >= 8 * tiles
+            total = int(nat.lib().gr_bins_bytes(ctypes.byref(gv), n, ctypes.byref(nat.GrPlan(K, K, K))))
+            assert off[3] + 4 * (((tiles + 32) // 32) * 32 + 9 * 32) <= total
+    gv.chunk = 0
+    assert nat.items_layout(gv, n, 4 * 1024 * 1024)[1] == 2048  # large views keep the 16-pixel default
+
+
 def test_struct_sizes_match_header(pkg):
     # gr_view: 2 ints + 16 + 16 + 3 + 3 + 2 floats + 1 int, then the background_dev pointer (8-aligned);
     # gr_render_params: RenderParams' layout

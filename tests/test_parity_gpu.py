@@ -154,9 +154,10 @@ def _native_bins(pkg, scene: orc.Scene, view, proj, W, H, device, cutoff=CUTOFF)
 
 
 @pytest.mark.parametrize("case", ["f1_n300_64x48", "f2_c1_view1", "c2_100k_512", "edge_big_sigma", "hd_1920x1080",
-                                  "xl_2304x2304", "n768_whole_blocks", "n300k_512"])
+                                  "xl_2304x2304", "n768_whole_blocks", "n300k_512", "sxga_1280x1024"])
 def test_bins_bit_exact(pkg, cuda, case):
-    """hd: 8160 tiles (counting sort, 2 waves per column); xl: 20736 tiles (radix-sort fallback);
+    """hd: 8160 tiles (counting sort, 1 wave per column: two waves' cursors fit up to 8,128 tiles); sxga: 5120 tiles
+    (2 waves per column, k_tile_place<2>: 4,065 to 8,128 tiles); xl: 20736 tiles (radix-sort fallback);
     n768: N a multiple of the 256-Gaussian scan block (the padding entry opens a block of its own);
     n300k: more scan blocks than k_plan's 1024 threads (several per thread)."""
     if case.startswith("f"):
@@ -175,8 +176,8 @@ def test_bins_bit_exact(pkg, cuda, case):
         scene = orc.synthetic_scene(300_000, seed=9)
         view, proj = orc.orbit_cameras(8, 512, 512)[1]
         W = H = 512
-    elif case in ("hd_1920x1080", "xl_2304x2304"):
-        W, H = (1920, 1080) if case.startswith("hd") else (2304, 2304)
+    elif case in ("hd_1920x1080", "xl_2304x2304", "sxga_1280x1024"):
+        W, H = {"hd": (1920, 1080), "xl": (2304, 2304), "sxga": (1280, 1024)}[case.split("_")[0]]
         scene = orc.synthetic_scene(60_000, seed=6)
         view, proj = orc.orbit_cameras(8, W, H)[3]
     else:
