@@ -510,7 +510,7 @@ class ViewShardedFitter:
                  exposure_fixed: tuple = (0,)):
         # dssim_weight l > 0: a view's photometric term is (1 - l) mean|pred - tgt| + l dssim(pred, tgt)
         # (losses.dssim_loss) on the per-view autograd path; 0 (default): the L1 fit, every path as it was
-        # dssim_fused (with l > 0, the HIP render op): the fused path's D-SSIM form (_views_direct_ssim or the native
+        # dssim_fused (with l > 0, the HIP render op): the fused path's D-SSIM form (_views_scheduled or the native
         # executor: gr_bwd_fit_ssim_gather per view, no autograd and no gradient image) instead of the autograd path
         # density_stats: accumulate every Gaussian's screen-space positional gradient over the views that see it
         # (density_state; what densify_and_prune(mode="gradient") reads): on the HIP device from the fused paths only
@@ -563,6 +563,29 @@ class ViewShardedFitter:
         self.opt = torch.optim.Adam(list(self.params.values()), lr=lr)
         self.densify_seed = 1234
         self.steps_done = 0
+        # ---- what a fitter keeps between calls, made on first use (None / empty until then) ----
+        self._bg = None  # the background colour as one device tensor (_background)
+        self._side = []  # the render streams besides the caller's (_streams: grows, never shrinks)
+        self._prep = None  # the preparation stream (_streams)
+        self._bin = None  # the L1 form's binning stream (GR_BIN_STREAM)
+        self._gv = {}  # every cached gr_view, by (kind, ...) (_gr_view); a camera update drops it (_drop_views)
+        self._native_targets = None  # (key, GrFitTarget array) of the executor's last fit call; dropped with _gv
+        self._acc_kept = {}  # "direct" / "native" -> (shapes, stream accumulator sets, their pointer array) (_acc_sets)
+        self._acc_parts = None  # the accumulator sets this step's views wrote, for the parameter update to sum
+        self._acc = None  # their sum in stream order while the autograd update reads it
+        self._exec_streams = None  # the render streams' handles an executor call reads (_exec_config)
+        self._native_keep = None  # the activations the executor's / batched step's streams still read
+        self._eval_keep = None  # the same for evaluate() and contribution_state()
+        self._pins = None  # pinned (views, 3) int64 rows the preparations write their plans to (_plan_pins)
+        self._grad_keep = {}  # parameter name -> its .grad tensor on the fused path, overwritten every step
+        self._act_ws = None  # activations_native's workspace (_act_ws_for)
+        self._gs = None  # the _GraphState of the device-sized / captured step (_graph_build)
+        self._dgen = None  # the device generator of densify_and_prune's device rules
+        self._cuts_cache = {}  # band cuts by (view, bands, tile, Gaussians, re-sort epoch) (_band_cuts)
+        self._rows_cache = {}  # estimated pairs per tile row by (view, tile, Gaussians, re-sort epoch)
+        self._cam_ws = {}  # render stream -> its gr_camera_grads_sums workspace (_camera_ws)
+        self._cam_pin = None  # pinned host copy of the step's camera-gradient rows (_camera_step_fused)
+        # (density_report / contribution_report exist only once densify_and_prune has filled them)
         self.density_stats = bool(density_stats)
         self._stats = []  # one (n, 2) buffer per render stream: [sum of gradient norms, seeing views]
         if self.density_stats and dev.type == "cuda":
@@ -728,7 +751,7 @@ class ViewShardedFitter:
 
     def _camera_ws(self, k: int, n: int, device) -> torch.Tensor:
         """Render stream k's gr_camera_grads_sums workspace (reused in stream order)."""
-        ws = self.__dict__.setdefault("_cam_ws", {})
+        ws = self._cam_ws
         need = max(8, int(tr._native.lib().gr_camera_grads_ws_bytes(n, tr._native.REDUCE_MAX_VIEWS)))
         t = ws.get(k)
         if t is None or t.numel() < need or t.device != device:
@@ -753,7 +776,7 @@ class ViewShardedFitter:
         if self.world > 1:
             dist.all_reduce(tot, group=self.group)
         if device.type == "cuda":
-            pin = self.__dict__.get("_cam_pin")
+            pin = self._cam_pin
             if pin is None or pin.shape != tot.shape:
                 self._cam_pin = pin = torch.empty(tot.shape, dtype=torch.float32, pin_memory=True)
             pin.copy_(tot, non_blocking=True)
@@ -815,8 +838,7 @@ class ViewShardedFitter:
                 if i in self._cam_host:
                     self._cam_host[i] = (vnp[i], self._cam_host[i][1])
         # the gr_views that hold the matrices are rebuilt on their next use (band cuts keep their refresh points)
-        for name in ("_gv_cache", "_band_gv", "_gvd_cache", "_gvs_cache", "_native_targets", "_eval_gv"):
-            self.__dict__.pop(name, None)
+        self._drop_views()
 
     def refined_cameras(self) -> list:
         """The cameras at their current poses, in the fitter's view order."""
@@ -880,7 +902,7 @@ class ViewShardedFitter:
 
     def _background(self, device) -> torch.Tensor:
         # one persistent tensor: the renderer reads its value on the host once, not per view
-        if getattr(self, "_bg", None) is None or self._bg.device != device:
+        if self._bg is None or self._bg.device != device:
             self._bg = torch.zeros(3, device=device)
         return self._bg
 
@@ -925,7 +947,7 @@ class ViewShardedFitter:
         tile = self.views_tile()
         ty = -(-self.height // tile)
         key = (i, g, tile, int(self.params["means"].shape[0]), self.steps_done // max(1, RESORT_EVERY))
-        cache = self.__dict__.setdefault("_cuts_cache", {})
+        cache = self._cuts_cache
         if key in cache:
             return cache[key]
         if len(cache) > 64:
@@ -937,7 +959,7 @@ class ViewShardedFitter:
 
     def _row_pairs_cached(self, i: int, tile: int, ty: int) -> np.ndarray:
         key = (i, tile, int(self.params["means"].shape[0]), self.steps_done // max(1, RESORT_EVERY))
-        cache = self.__dict__.setdefault("_rows_cache", {})
+        cache = self._rows_cache
         if key not in cache:
             if len(cache) > 64:
                 cache.clear()
@@ -1047,38 +1069,72 @@ class ViewShardedFitter:
         prepare_upto(min(PREP_FIRST, PREP_AHEAD - 1) if PREP_INITIAL > 1 else 0)
         return prepare_upto
 
-    def _fit_view(self, i: int, device) -> "tr._native.GrView":
-        """The gr_view of view i for the fused path (one FIT_CUTOFF zone, no depth gradient), built once:
-        cameras and background do not change during a fit (saves the host's matrix inverse and copies
-        twice per view and step).  A band id (>= V): that view with its band of tile rows."""
-        if i >= len(self.targets):
-            b = getattr(self, "_band_gv", None)
-            if b is None:
-                self._band_gv = b = {}
-            key = (i, F32_GRADE, FIT_TILE) + self._bands[i]
-            gv = b.get(key)
-            if gv is None:
-                base, row0, rows = self._bands[i]
-                gv = b[key] = tr._native.GrView.from_buffer_copy(self._fit_view(base, device))
-                gv.row0, gv.rows = row0, rows
+    def _gr_view(self, kind: str, i, device) -> "tr._native.GrView":
+        """The one cache of gr_views, each built once: cameras and background change during a fit only through
+        _camera_update, which drops them all (_drop_views).  Building one costs the host a matrix inverse and copies.
+          fit    view i for the fused path: one FIT_CUTOFF zone, no depth gradient, FIT_TILE tiles (F32_GRADE: the
+                 f32-grade mode on 16-pixel tiles); keyed by those two switches as well
+          ssim   the same with 16-pixel tiles, the SSIM kernels' tile (the D-SSIM form without a depth term)
+          depth  view i in the default precision mode with the depth gradient's footprint (a depth term)
+          band   a band id i >= V (_bands): its view's `fit` view cut to the band's tile rows; keyed by the cut too
+          eval   the view render_gaussians_torch(..., depth_grad=False) makes for camera object i with the fitter's
+                 background (16-pixel tiles, default_cutoff(False), the default core cutoff); keyed by the object's
+                 identity, and the object is kept with the view so that the identity stays its own"""
+        if kind == "eval":
+            key = (kind, id(i), str(device))
+            hit = self._gv.get(key)
+            if hit is None:
+                hit = self._gv[key] = (tr.make_view(i.view, i.proj, self.width, self.height, self._background(device),
+                                                    depth_grad=False), i)
+            return hit[0]
+        if kind == "depth":
+            key = (kind, i)
+        elif kind == "ssim":
+            key = (kind, i, F32_GRADE)
+        else:
+            key = (kind, i, F32_GRADE, FIT_TILE) + (self._bands[i] if kind == "band" else ())
+        gv = self._gv.get(key)
+        if gv is not None:
             return gv
-        cache = getattr(self, "_gv_cache", None)
-        if cache is None:
-            self._gv_cache = cache = {}
-        gv = cache.get((i, F32_GRADE, FIT_TILE))
-        if gv is None:
-            gv = cache[(i, F32_GRADE, FIT_TILE)] = tr.make_view(*self._cam_mats(i), self.width, self.height,
-                                                      self._background(device), cutoff=tr.FIT_CUTOFF,
-                                                      core_cutoff=tr.FIT_CUTOFF, depth_grad=False,
-                                                      tile=0 if F32_GRADE else FIT_TILE)
+        if kind == "band":
+            base, row0, rows = self._bands[i]
+            gv = tr._native.GrView.from_buffer_copy(self._gr_view("fit", base, device))
+            gv.row0, gv.rows = row0, rows
+        elif kind == "depth":
+            gv = tr.make_view(*self._cam_mats(i), self.width, self.height, self._background(device), depth_grad=True)
+        else:
+            tile = {} if kind == "ssim" else {"tile": 0 if F32_GRADE else FIT_TILE}
+            gv = tr.make_view(*self._cam_mats(i), self.width, self.height, self._background(device),
+                              cutoff=tr.FIT_CUTOFF, core_cutoff=tr.FIT_CUTOFF, depth_grad=False, **tile)
             if F32_GRADE:
                 gv.no_depth_grad = 2
+        self._gv[key] = gv
         return gv
+
+    def _drop_views(self) -> None:
+        """The cameras' matrices changed: every gr_view, and the executor's target array that holds copies of them, is
+        rebuilt on its next use (band cuts keep their refresh points)."""
+        self._gv.clear()
+        self._native_targets = None
+
+    def _fit_view(self, i: int, device) -> "tr._native.GrView":
+        """The fused path's gr_view of view i, or of band id i >= V (_gr_view's `fit` / `band`)."""
+        return self._gr_view("band" if i >= len(self.targets) else "fit", i, device)
+
+    def _ssim_view(self, i: int, device) -> "tr._native.GrView":
+        """The gr_view of view i for the fused path's D-SSIM form without a depth term (_gr_view's `ssim`)."""
+        return self._gr_view("ssim", i, device)
+
+    def _step_view(self, i: int, device, depth: bool, ssim: bool = False) -> "tr._native.GrView":
+        """The gr_view the fused step renders (virtual) view i with, in every schedule."""
+        if depth:
+            return self._gr_view("depth", i, device)
+        return self._ssim_view(i, device) if ssim else self._fit_view(i, device)
 
     def _plan_pins(self, count: int) -> torch.Tensor:
         """One pinned (count, 3) int64 buffer for the views' plans, kept across steps (a pinned allocation
         per view and step costs host time on the render path)."""
-        pins = getattr(self, "_pins", None)
+        pins = self._pins
         if pins is None or pins.shape[0] < count:
             self._pins = pins = torch.zeros((max(count, 1), 3), dtype=torch.int64, pin_memory=True)
         return pins
@@ -1127,8 +1183,176 @@ class ViewShardedFitter:
             loss = loss + self.w_depth * torch.mean(torch.abs(d_pred - self.depths[i]))
         return loss
 
+    # ---- the fused path's streams, kept buffers and its one per-view schedule ------------------------------------
+    def _streams(self, device, ns: int) -> tuple:
+        """(the ns - 1 render streams besides the caller's, the preparation stream): the fitter's own, shared by the
+        fit step in every form, the native executor's calls, evaluate() and contribution_state().  The side streams
+        are made before the preparation stream, and that one at PREP_PRIORITY: creation order decides the streams'
+        hardware-queue placement.  More side streams are made only when too few exist, and none is ever dropped: a
+        call over fewer views than the fit has streams (an evaluate() of two held-out views) uses the first of them and
+        leaves the fit's streams as they are.  (Before, any call with another stream count re-created them all.)"""
+        if (self._side and self._side[0].device != device) or (self._prep is not None and self._prep.device != device):
+            self._side, self._prep = [], None
+        while len(self._side) < ns - 1:
+            self._side.append(torch.cuda.Stream(device))
+        if self._prep is None:
+            self._prep = torch.cuda.Stream(device, priority=PREP_PRIORITY)
+        return self._side[:max(0, ns - 1)], self._prep
+
+    def _acc_sets(self, owner: str, ns: int, m, s, c, o) -> tuple:
+        """(ns stream accumulator sets, each four tensors like m, s, c, o; their 4 * ns pointers as the executor takes
+        them), kept per owner ("direct": the Python and batched schedules, "native": the executor) while the shapes
+        hold: 4 x streams allocations per step were host time before the first launch.  They are written only after
+        the render streams wait for the caller's stream, i.e. after the previous step's parameter update read them."""
+        shapes = (ns,) + tuple(tuple(t.shape) for t in (m, s, c, o))
+        kept = self._acc_kept.get(owner)
+        if kept is None or kept[0] != shapes or kept[1][0][0].device != m.device:
+            acc = [tuple(torch.empty_like(t) for t in (m, s, c, o)) for _ in range(ns)]
+            self._acc_kept[owner] = kept = (shapes, acc, (ctypes.c_void_p * (4 * ns))(*[t.data_ptr() for a in acc for t in a]))
+        return kept[1], kept[2]
+
+    def _exec_config(self, device, ns: int, sized=None) -> "tr._native.GrFitConfig":
+        """The native executor's configuration of a call over ns streams: the module's schedule knobs, with `sized`
+        the device-side sizing state (capacities, observed counts, overflow word), and the fitter's own torch streams
+        (EXEC_STREAMS): the same hardware-queue placement as the Python schedule, so the two differ only in their
+        host code."""
+        cfg = tr._native.GrFitConfig(NUM_STREAMS, PREP_AHEAD, PREP_GROUP, PREP_FIRST, REDUCE_BATCH, min(REDUCE_TAIL, REDUCE_BATCH))
+        if sized is not None:
+            cfg.caps = sized.caps_arr
+            cfg.observed = sized.observed.data_ptr()
+            cfg.overflow = sized.ovf.data_ptr()
+        if EXEC_STREAMS:
+            side, prep = self._streams(device, ns)
+            self._exec_streams = rs = (ctypes.c_void_p * max(1, ns - 1))(*[st.cuda_stream for st in side])
+            cfg.render_streams = rs
+            cfg.prep_stream = prep.cuda_stream
+        return cfg
+
+    def _reg_after_exec(self, reg_fn, device):
+        """The regulariser's small kernels after the executor's call (the host starts the views' preparations first),
+        on the preparation stream behind the last preparation when the executor runs on the fitter's streams (as the
+        Python schedule does; no extra hardware queue).  Returns reg_fn()'s value, or None."""
+        if reg_fn is None:
+            return None
+        prep = self._prep if EXEC_STREAMS else None
+        if prep is None:
+            return reg_fn()
+        main = torch.cuda.current_stream(device)
+        with torch.cuda.stream(prep):
+            reg = reg_fn()
+        reg.record_stream(main)  # allocated on prep, read on main (ADVICE r04): not reused by prep early
+        main.wait_stream(prep)
+        return reg
+
+    def _preparer(self, m, s, c, o, gv_at: Callable, count: int, sized=None) -> Callable:
+        """_view_loop's preparation callable over positions 0 .. count - 1 (gv_at(q): position q's gr_view): host-sized
+        (the plans land in pinned rows the forward reads), or with `sized` (_graph_step) device-sized: capacities in,
+        the true counts to the pinned `observed` rows."""
+        if sized is None:
+            pins = self._plan_pins(count)
+            return lambda js: tr.prepare_views_native(m, s, c, o, [gv_at(q) for q in js], [pins[q] for q in js])
+        return lambda js: tr.prepare_views_sized(m, s, c, o, [tr.sized_view(gv_at(q)) for q in js],
+                                                 [sized.caps[q] for q in js], [sized.observed[q] for q in js], sized.ovf)
+
+    def _view_loop(self, device, count: int, prepare_views: Callable, body: Callable, reduce: Optional[Callable] = None,
+                   tail_fn: Optional[Callable] = None):
+        """The fused path's per-view schedule, the one every Python form runs (the L1, depth and D-SSIM fit steps,
+        evaluate(), contribution_state()) and the native executor mirrors (gr_fit_exec.cpp):
+          * the preparation groups (_prep_groups over prepare_views) run PREP_AHEAD views ahead on the preparation stream;
+          * view j runs on render stream j % ns (the caller's stream first): the stream waits for the prepared view's
+            event, its geometry is recorded on the stream, then body(j, take) runs with the stream current.  The body
+            takes the prepared view with take(j): the loop itself keeps no reference to it or to anything the body
+            makes, so each body decides when its memory returns to the allocator;
+          * with `reduce`, what the bodies return waits per stream in view order and is reduced in the batches of
+            _batch_sizes: reduce(k, batch, js, accumulate) on stream k, js the batch's positions, accumulate False
+            for a stream's first batch;
+          * tail_fn() runs on the preparation stream after the last preparation (its tensor recorded on the caller's);
+          * the caller's stream waits for every render stream, then for the preparation stream.
+        Three ordering rules carry the bit-identity with the executor and must hold for every caller:
+          1. whatever the bodies write (losses, accumulators, statistics, camera rows) is allocated on the caller's
+             stream before this is called: the render streams' first act is to wait for that stream;
+          2. kept accumulators are therefore written only after the previous parameter update read them;
+          3. a stream's reductions run in view order, and the caller sums the streams in stream order.
+        Returns tail_fn()'s value (None without one)."""
+        main = torch.cuda.current_stream(device)
+        ns = max(1, min(NUM_STREAMS, count))
+        side, prep = self._streams(device, ns)
+        streams = [main] + side
+        for st in side:
+            st.wait_stream(main)
+        prep.wait_stream(main)
+        ahead: dict = {}
+        take = ahead.pop
+        prepare_upto = self._prep_groups(range(count), ahead, prepare_views, prep)
+        pending: list = [[] for _ in streams]  # per stream: what its bodies returned, awaiting their reduction
+        pending_js: list = [[] for _ in streams]  # their positions (the camera-gradient rows)
+        started = [False] * ns
+        sizes = _batch_sizes(ns, count) if reduce is not None else None
+
+        def reduce_pending(k):
+            if pending[k]:
+                with torch.cuda.stream(streams[k]):
+                    reduce(k, pending[k], pending_js[k], started[k])
+                started[k] = True
+                pending[k] = []
+                pending_js[k] = []
+
+        for j in range(count):
+            k = j % ns
+            st = streams[k]
+            prepare_upto(j)
+            pv = ahead[j]
+            st.wait_event(pv.event)
+            pv.geom.record_stream(st)
+            pv = None
+            with torch.cuda.stream(st):
+                item = body(j, take)
+            prepare_upto(j + PREP_AHEAD)
+            if reduce is not None:
+                pending[k].append(item)
+                pending_js[k].append(j)
+                item = None
+                if len(pending[k]) >= sizes[k][0]:
+                    reduce_pending(k)
+                    if len(sizes[k]) > 1:
+                        sizes[k].pop(0)
+        if reduce is not None:
+            for k in range(ns):
+                reduce_pending(k)
+        tail = None
+        if tail_fn is not None:
+            with torch.cuda.stream(prep):
+                tail = tail_fn()
+                if isinstance(tail, torch.Tensor):
+                    tail.record_stream(main)  # allocated on the preparation stream, read on main
+        for st in side:
+            main.wait_stream(st)
+        main.wait_stream(prep)
+        return tail
+
+    def _reduce_batch(self, m, s, c, o, batch, js, k: int, acc, stats, accumulate: bool, gathered: bool = True) -> None:
+        """One reduction batch of render stream k, on the current stream: the chain rules from the views' gathered
+        sums into the stream's accumulator set (gr_reduce_sums), with density_stats the statistics beside it, with
+        refine_cameras the camera gradients after it (batch entry q is position js[q] of my_views).  gathered False
+        (the L1 form with GR_GATHER=0): the one-pass gr_reduce_views over the views' kept workspaces."""
+        if not gathered:
+            if self.refine_cameras:
+                raise ValueError("refine_cameras: the fused path's camera gradient reads the gathered sums "
+                                 "(GR_GATHER=0 has none)")
+            tr.reduce_views_native(m, s, c, o, batch, acc[k], accumulate=accumulate)
+            return
+        tr.reduce_sums_native(m, s, c, o, batch, acc[k], accumulate=accumulate)
+        if stats is not None:
+            tr.density_stats_native(m, s, o, batch, self._inv_g_scale(), stats[k])
+        if self.refine_cameras:
+            self._camera_grads_batch(m, s, c, o, batch, js, k)
+
+    def _form(self) -> str:
+        """The fused step's form: "ssim" (the D-SSIM form, with or without a depth term), "depth" or "l1"."""
+        return "ssim" if self._ssim_form() else "depth" if self._depth_grad() else "l1"
+
     def _direct(self, device) -> bool:
-        """The fused path (_views_direct, or _views_direct_depth with a depth term): HIP render op, the
+        """The fused path (_views_direct, or _views_scheduled's depth and D-SSIM forms): HIP render op, the
         view loss and its gradients in the C ABI, no autograd per view.  Needs float32 parameters and
         targets / masks / depths of exactly the image's shape (checked at construction).  A D-SSIM term
         (dssim_weight > 0) is not fused into the splat epilogues: such a fit takes the per-view autograd path, or with
@@ -1151,33 +1375,7 @@ class ViewShardedFitter:
         if self._direct(device) and self.params["means"].shape[0] > 0 and self._fused_step_ok():
             with torch.no_grad():
                 means, scales, colors, opacities, reg_t = self._activations_fused(device)
-                reg_fn = (lambda: reg_t) if reg_t is not None else None
-                reg = None
-                if self._native_exec() and GATHER:
-                    total = self._views_native(means, scales, colors, opacities, self._depth_grad(), ssim=self._ssim_form())
-                    # the regulariser's small kernels after the executor's call (the host starts the views'
-                    # preparations first), on the preparation stream behind the last preparation when the executor
-                    # runs on this driver's streams (as the Python schedule does; no extra hardware queue)
-                    rs = getattr(self, "_prep", None) if EXEC_STREAMS else None
-                    if reg_fn and rs is not None:
-                        main = torch.cuda.current_stream(device)
-                        with torch.cuda.stream(rs):
-                            reg = reg_fn()
-                        reg.record_stream(main)  # allocated on rs, read on main: not reused by rs early
-                        main.wait_stream(rs)
-                    elif reg_fn:
-                        reg = reg_fn()
-                elif self._ssim_form():
-                    reg = reg_fn() if reg_fn else None
-                    total = self._views_direct_ssim(means, scales, colors, opacities)
-                elif self._depth_grad():
-                    reg = reg_fn() if reg_fn else None
-                    total = self._views_direct_depth(means, scales, colors, opacities)
-                else:
-                    # the regulariser's small kernels run on the preparation stream once the last
-                    # preparation is enqueued: neither before the first view nor between the last
-                    # reduction and the parameter update
-                    total, reg = self._views_direct(means, scales, colors, opacities, reg_fn)
+                total, reg = self._views_fused(means, scales, colors, opacities, reg_t, self._native_exec() and GATHER)
                 loss = total / len(self.targets)
                 if reg is not None:
                     loss = loss + reg
@@ -1187,12 +1385,7 @@ class ViewShardedFitter:
             return out
         means, scales, colors, opacities = activations(self.params)
         if self._direct(device) and means.shape[0] > 0:
-            if self._ssim_form():
-                total = self._views_direct_ssim(means, scales, colors, opacities)
-            elif self._depth_grad():
-                total = self._views_direct_depth(means, scales, colors, opacities)
-            else:
-                total, _ = self._views_direct(means, scales, colors, opacities)
+            total, _ = self._views_scheduled(means, scales, colors, opacities, self._form())
             parts = self._acc_parts
             acc = []
             for q in range(4):  # in stream order
@@ -1230,9 +1423,7 @@ class ViewShardedFitter:
         ns = min(NUM_STREAMS, len(self.my_views))
         if prefetch and ns > 1:
             main = torch.cuda.current_stream(device)
-            side = getattr(self, "_side", None)
-            if side is None or len(side) != ns - 1 or side[0].device != device:
-                self._side = side = [torch.cuda.Stream(device) for _ in range(ns - 1)]
+            side, _ = self._streams(device, ns)
             for st in side:
                 st.wait_stream(main)  # the activations are produced on the main stream
             streams = [main] + side
@@ -1291,9 +1482,9 @@ class ViewShardedFitter:
         return str(NATIVE_EXEC) not in ("0", "False", "")
 
     def _views_native(self, means, scales, colors, opacities, depth: bool, sized=None, ssim: bool = False) -> torch.Tensor:
-        """_views_direct / _views_direct_depth through the native executor (gr_fit_views): one C call per
-        step; returns the sum of the view losses and leaves the stream accumulators in self._acc_parts.
-        ssim: _views_direct_ssim's form (gr_fit_views_ssim)."""
+        """_views_scheduled's forms through the native executor (gr_fit_views): one C call per step; returns the sum
+        of the view losses and leaves the stream accumulators in self._acc_parts.  ssim: the D-SSIM form
+        (gr_fit_views_ssim)."""
         device = means.device
         m, s, c, o = (t.detach().float().contiguous() for t in (means, scales, colors, opacities))
         views = self.my_views
@@ -1303,54 +1494,20 @@ class ViewShardedFitter:
         ns = max(1, min(NUM_STREAMS, len(views)))
         w_sil = self.w_sil if (self.masks is not None and self.w_sil > 0.0) else 0.0
         key = (tuple(views), depth, F32_GRADE, w_sil > 0.0, str(device), sized is not None, ssim)
-        cache = getattr(self, "_native_targets", None)
+        cache = self._native_targets
         if cache is None or cache[0] != key:
             arr = (tr._native.GrFitTarget * len(views))()
             for j, i in enumerate(views):
-                if depth:
-                    gvd = getattr(self, "_gvd_cache", None)
-                    if gvd is None:
-                        self._gvd_cache = gvd = {}
-                    if i not in gvd:
-                        gvd[i] = tr.make_view(*self._cam_mats(i), self.width, self.height, self._background(device),
-                                              depth_grad=True)
-                    arr[j].view = gvd[i] if sized is None else tr.sized_view(gvd[i])
-                    arr[j].target_depth = self.depths[i].data_ptr()
-                else:
-                    gvf = self._ssim_view(i, device) if ssim else self._fit_view(i, device)
-                    arr[j].view = gvf if sized is None else tr.sized_view(gvf)
-                    arr[j].target_depth = None
+                gv = self._step_view(i, device, depth, ssim)
+                arr[j].view = gv if sized is None else tr.sized_view(gv)
+                arr[j].target_depth = self.depths[i].data_ptr() if depth else None
                 arr[j].target_rgb = self.targets[self._vi(i)].data_ptr()
                 arr[j].target_mask = self.masks[self._vi(i)].data_ptr() if w_sil > 0.0 else None
             self._native_targets = cache = (key, arr)
-        cfg = tr._native.GrFitConfig(NUM_STREAMS, PREP_AHEAD, PREP_GROUP, PREP_FIRST, REDUCE_BATCH, min(REDUCE_TAIL, REDUCE_BATCH))
-        if sized is not None:  # device-side sizing: the capacities, the observed counts, the overflow word
-            cfg.caps = sized.caps_arr
-            cfg.observed = sized.observed.data_ptr()
-            cfg.overflow = sized.ovf.data_ptr()
-        if EXEC_STREAMS:
-            # the Python schedule's own torch streams: the same hardware-queue placement (stream creation
-            # order decides it), so the two schedules differ only in their host code
-            side = getattr(self, "_side", None)
-            if ns > 1 and (side is None or len(side) != ns - 1 or side[0].device != device):
-                self._side = side = [torch.cuda.Stream(device) for _ in range(ns - 1)]
-            prep = getattr(self, "_prep", None)
-            if prep is None or prep.device != device:
-                self._prep = prep = torch.cuda.Stream(device, priority=PREP_PRIORITY)
-            self._exec_streams = rs = (ctypes.c_void_p * max(1, ns - 1))(
-                *[st.cuda_stream for st in (side[:ns - 1] if ns > 1 else [])])
-            cfg.render_streams = rs
-            cfg.prep_stream = prep.cuda_stream
+        cfg = self._exec_config(device, ns, sized)
         losses_v = torch.empty(len(views), dtype=torch.float32, device=device)
-        # the streams' accumulators (and their pointer array) are kept across steps while the shapes hold: the
-        # executor writes them (accumulate = 0 first) only after the caller's stream, so after the previous step's
-        # parameter update read them; 4 x streams allocations per step were host time before the first launch
-        shapes = (ns,) + tuple(tuple(t.shape) for t in (m, s, c, o))
-        cached = getattr(self, "_native_acc", None)
-        if cached is None or cached[0] != shapes or cached[1][0][0].device != device:
-            acc = [tuple(torch.empty_like(t) for t in (m, s, c, o)) for _ in range(ns)]
-            self._native_acc = cached = (shapes, acc, (ctypes.c_void_p * (4 * ns))(*[t.data_ptr() for a in acc for t in a]))
-        acc, ptrs = cached[1], cached[2]
+        # (the executor writes the kept accumulators, accumulate = 0 first, only after the caller's stream)
+        acc, ptrs = self._acc_sets("native", ns, m, s, c, o)
         L = tr._native.lib()
         head = (tr._native.executor(device.index or 0), ctypes.byref(cfg), len(views), cache[1], int(m.shape[0]),
                 tr._native.ptr(m), tr._native.ptr(s), tr._native.ptr(c), tr._color_dim(c), tr._native.ptr(o),
@@ -1376,259 +1533,102 @@ class ViewShardedFitter:
         self._native_keep = (m, s, c, o)  # read by the executor's streams until the caller's stream passes them
         return losses_v.sum()
 
+    def _views_fused(self, means, scales, colors, opacities, reg_t, native: bool, sized=None) -> tuple:
+        """The fused step's views through the native executor or the Python schedule: (the sum of the view losses,
+        the regulariser reg_t after its hand-over).  The regulariser's small kernels follow the last preparation on
+        the preparation stream (_reg_after_exec; the L1 form's tail_fn: neither before the first view nor between the
+        last reduction and the parameter update); the depth and D-SSIM forms of the Python schedule take it as it is."""
+        reg_fn = (lambda: reg_t) if reg_t is not None else None
+        if native:
+            total = self._views_native(means, scales, colors, opacities, self._depth_grad(), sized=sized, ssim=self._ssim_form())
+            return total, self._reg_after_exec(reg_fn, means.device)
+        form = self._form()
+        if form != "l1":
+            return self._views_scheduled(means, scales, colors, opacities, form, sized=sized)[0], reg_t
+        return self._views_scheduled(means, scales, colors, opacities, form, reg_fn, sized)
+
     def _views_direct(self, means, scales, colors, opacities, tail_fn=None, sized=None):
-        """This rank's views without autograd: per view, gr_fwd_render_l1 (the HIP forward whose epilogue
-        evaluates the view's L1 + silhouette loss and its upstream gradients, fit_multiview_stub.py:292-299)
-        and gr_bwd_splat (the backward splat, :310); every REDUCE_BATCH views of a HIP stream,
-        gr_reduce_views adds their gradient w.r.t. the
-        activated parameters into that stream's accumulator set (in view order: deterministic).  The
-        accumulators are summed in stream order and leave in self._acc for one autograd pass through the
-        activations; returns (the sum of the view losses (device, 0-d), tail_fn() evaluated on the
-        preparation stream after the last preparation, or None)."""
+        """_views_scheduled's L1 form: (the sum of the view losses, tail_fn()'s value or None)."""
+        return self._views_scheduled(means, scales, colors, opacities, "l1", tail_fn, sized)
+
+    def _views_scheduled(self, means, scales, colors, opacities, form: str, tail_fn=None, sized=None) -> tuple:
+        """This rank's views without autograd, on the Python schedule (_view_loop).  Per view, by form:
+          l1     gr_fwd_render_l1 (the HIP forward whose epilogue evaluates the view's L1 + silhouette loss and its
+                 upstream gradients, fit_multiview_stub.py:292-299) and gr_bwd_splat (the backward splat, :310), then
+                 gr_gather_view (GATHER; else the view's workspaces wait for gr_reduce_views); band views (_vi), and
+                 the binning on a stream of its own with GR_BIN_STREAM;
+          depth  the depth term (fit_multiview_stub.py:301-305): the HIP forward in the default precision mode (f32-grade
+                 W and D, the depth-gradient footprint) keeping its saved sums, then gr_bwd_fit_gather (L1 + silhouette
+                 + depth loss gradients and the render backward up to the per-Gaussian sums);
+          ssim   the D-SSIM form (dssim_fused): gr_bwd_fit_ssim_gather in its place, whose photometric term is
+                 (1 - l) L1 + l D-SSIM; with a depth term the depth form's views, without one _ssim_view's.
+        Every reduction batch of a stream adds its views' gradient w.r.t. the activated parameters into that stream's
+        accumulator set (_reduce_batch, in view order: deterministic); the sets leave in self._acc_parts, to be summed
+        in stream order by the caller (gr_fit_param_step or torch adds).  Returns (the sum of the view losses (device,
+        0-d), tail_fn() evaluated on the preparation stream after the last preparation, or None)."""
         device = means.device
         m, s, c, o = (t.detach().float().contiguous() for t in (means, scales, colors, opacities))
         views = self.my_views
+        nv = len(views)
+        ns = max(1, min(NUM_STREAMS, nv))
         main = torch.cuda.current_stream(device)
-        ns = max(1, min(NUM_STREAMS, len(views)))
-        side = getattr(self, "_side", None)
-        if ns > 1 and (side is None or len(side) != ns - 1 or side[0].device != device):
-            self._side = side = [torch.cuda.Stream(device) for _ in range(ns - 1)]
-        streams = [main] + (side[:ns - 1] if ns > 1 else [])
-        # made on the main stream before the side streams wait for it: every stream's use is ordered
-        # after its allocation, and main waits for every stream before they are read or freed
-        losses_v = torch.empty(max(1, len(views)), dtype=torch.float32, device=device)
-        # the streams' accumulators are kept across steps while the shapes hold (written only after the side
-        # streams wait for main below, i.e. after the previous step's parameter update read them): 4 x streams
-        # allocations per step were host time before the first preparation
-        shapes = (len(streams),) + tuple(tuple(t.shape) for t in (m, s, c, o))
-        cached = getattr(self, "_direct_acc", None)
-        if cached is None or cached[0] != shapes or cached[1][0][0].device != device:
-            self._direct_acc = cached = (shapes, [tuple(torch.empty_like(t) for t in (m, s, c, o)) for _ in streams])
-        acc = cached[1]
-        stats = self._stats_bufs(len(streams), device) if self.density_stats else None
-        if self.refine_cameras:  # (made on the main stream, before the render streams wait for it)
-            self._camera_rows(len(views), device)
-        for st in streams[1:]:
-            st.wait_stream(main)
+        self._streams(device, ns)  # (made before the binning stream: creation order places them on the hardware queues)
+        # made on the main stream before the render streams wait for it (_view_loop's rule 1): every stream's use is
+        # ordered after its allocation, and main waits for every stream before they are read or freed
+        losses_v = torch.empty(max(1, nv), dtype=torch.float32, device=device)
+        acc, _ = self._acc_sets("direct", ns, m, s, c, o)
+        stats = self._stats_bufs(ns, device) if self.density_stats else None
+        if self.refine_cameras:
+            self._camera_rows(nv, device)
         w_sil = self.w_sil if (self.masks is not None and self.w_sil > 0.0) else 0.0
         g_scale = 1.0 / len(self.targets)
-        # the views' preparations (projection, culling, pair counts) run on a stream of their own,
-        # PREP_AHEAD views ahead of the view being rendered: the host's read of a view's pair count never
-        # waits behind other views' renders, the preparations run beside the splat kernels, and the host
-        # starts the first render after enqueueing a few preparations (not all of them)
-        prep = getattr(self, "_prep", None)
-        if prep is None or prep.device != device:
-            self._prep = prep = torch.cuda.Stream(device, priority=PREP_PRIORITY)
-        prep.wait_stream(main)
+        depth = form == "depth" or (form == "ssim" and self._depth_grad())
         bin_stream = None
-        if BIN_STREAM != "":
-            bin_stream = getattr(self, "_bin", None)
-            if bin_stream is None or bin_stream.device != device:
-                self._bin = bin_stream = torch.cuda.Stream(device, priority=int(BIN_STREAM))
+        if form == "l1" and BIN_STREAM != "":
+            if self._bin is None or self._bin.device != device:
+                self._bin = torch.cuda.Stream(device, priority=int(BIN_STREAM))
+            bin_stream = self._bin
             bin_stream.wait_stream(main)
-        pins = self._plan_pins(len(views))
-        ahead: dict = {}
-        if sized is None:
-            prepare_upto = self._prep_groups(views, ahead, lambda js: tr.prepare_views_native(
-                m, s, c, o, [self._fit_view(views[q], device) for q in js], [pins[q] for q in js]), prep)
-        else:  # device-side sizing (_graph_step): capacities in, true counts to the pinned `observed` rows
-            prepare_upto = self._prep_groups(views, ahead, lambda js: tr.prepare_views_sized(
-                m, s, c, o, [tr.sized_view(self._fit_view(views[q], device)) for q in js], [sized.caps[q] for q in js],
-                [sized.observed[q] for q in js], sized.ovf), prep)
-        pending: list = [[] for _ in streams]  # per stream: (render state, partials) awaiting their reduction
-        pending_js: list = [[] for _ in streams]  # their positions in `views` (the camera-gradient rows)
-        started = [False] * ns
-        sizes = _batch_sizes(ns, len(views))
 
-        def reduce_pending(k):
-            if pending[k]:
-                with torch.cuda.stream(streams[k]):
-                    if GATHER:
-                        tr.reduce_sums_native(m, s, c, o, pending[k], acc[k], accumulate=started[k])
-                        if stats is not None:
-                            tr.density_stats_native(m, s, o, pending[k], self._inv_g_scale(), stats[k])
-                        if self.refine_cameras:
-                            self._camera_grads_batch(m, s, c, o, pending[k], pending_js[k], k)
-                    else:
-                        if self.refine_cameras:
-                            raise ValueError("refine_cameras: the fused path's camera gradient reads the gathered sums "
-                                             "(GR_GATHER=0 has none)")
-                        tr.reduce_views_native(m, s, c, o, pending[k], acc[k], accumulate=started[k])
-                started[k] = True
-                pending[k] = []
-                pending_js[k] = []
+        def body_l1(j, take):
+            # one zone at the core cutoff and no depth channel: the loss reads neither depth nor the tail-only part
+            # of W's footprint (torch_renderer.FIT_CUTOFF)
+            i = self._vi(views[j])
+            pv = take(j)
+            rs, ws = tr.forward_l1_native(m, s, c, o, pv.gv, pv, self.targets[i], self.masks[i] if w_sil > 0.0 else None,
+                                          w_sil, g_scale, losses_v[j:j + 1], bin_stream=bin_stream)
+            pv = None
+            tr.backward_splat_native(rs, ws)
+            if GATHER:  # the view's sums; its bins, geom and workspace go back to the allocator on return
+                return rs.gv, tr.gather_view_native(rs, ws)
+            return rs, ws
 
-        for j, i in enumerate(views):
-            k = j % ns
-            prepare_upto(j)
-            pv = ahead.pop(j)
-            streams[k].wait_event(pv.event)
-            pv.geom.record_stream(streams[k])
-            with torch.cuda.stream(streams[k]):
-                # one zone at the core cutoff and no depth channel: the loss reads neither depth nor the
-                # tail-only part of W's footprint (torch_renderer.FIT_CUTOFF)
-                rs, ws = tr.forward_l1_native(m, s, c, o, pv.gv, pv, self.targets[self._vi(i)],
-                                              self.masks[self._vi(i)] if w_sil > 0.0 else None, w_sil, g_scale, losses_v[j:j + 1],
-                                              bin_stream=bin_stream)
-                pv = None
-                tr.backward_splat_native(rs, ws)
-                if GATHER:  # the view's sums; its bins, geom and workspace go back to the allocator here
-                    pending[k].append((rs.gv, tr.gather_view_native(rs, ws)))
-                    rs = ws = None
-            if rs is not None:
-                pending[k].append((rs, ws))
-            pending_js[k].append(j)
-            prepare_upto(j + PREP_AHEAD)
-            if len(pending[k]) >= sizes[k][0]:
-                reduce_pending(k)
-                if len(sizes[k]) > 1:
-                    sizes[k].pop(0)
-        for k in range(ns):
-            reduce_pending(k)
-        tail = None
-        if tail_fn is not None:
-            with torch.cuda.stream(prep):
-                tail = tail_fn()
-                if isinstance(tail, torch.Tensor):
-                    tail.record_stream(main)  # allocated on the preparation stream, read on main
-        for st in streams[1:]:
-            main.wait_stream(st)
-        main.wait_stream(prep)
+        def body_sums(j, take):
+            i = views[j]
+            pv = take(j)
+            _, _, _, rs = tr.forward_native(m, s, c, o, pv.gv, pv, images=False)  # the backward reads the sums
+            pv = None
+            mask = self.masks[i] if w_sil > 0.0 else None
+            if form == "ssim":
+                sums, sums3 = tr.backward_fit_ssim_gather_native(
+                    rs, self.targets[i], mask, w_sil, self.depths[i] if depth else None, self.w_depth if depth else 0.0,
+                    g_scale, self.w_dssim, losses_v[j:j + 1])
+            else:
+                sums, sums3 = tr.backward_fit_gather_native(rs, self.targets[i], mask, w_sil, self.depths[i], self.w_depth,
+                                                            g_scale, losses_v[j:j + 1])
+            return (rs.gv, sums, sums3) if sums3 is not None else (rs.gv, sums)
+
+        gathered = GATHER or form != "l1"
+        tail = self._view_loop(
+            device, nv, self._preparer(m, s, c, o, lambda q: self._step_view(views[q], device, depth, form == "ssim"), nv, sized),
+            body_l1 if form == "l1" else body_sums,
+            lambda k, batch, js, accumulate: self._reduce_batch(m, s, c, o, batch, js, k, acc, stats, accumulate, gathered),
+            tail_fn)
         if bin_stream is not None:
             main.wait_stream(bin_stream)
-        used = min(ns, len(views))
         # the streams' accumulators (summed in stream order by the caller: gr_fit_param_step or torch adds)
-        self._acc_parts = acc[:used] if used > 0 else [tuple(torch.zeros_like(t) for t in (m, s, c, o))]
-        return (losses_v[:len(views)].sum() if views else torch.zeros((), device=device)), tail
-
-    def _ssim_view(self, i: int, device) -> "tr._native.GrView":
-        """The gr_view of view i for the fused path's D-SSIM form without a depth term: _fit_view's (one FIT_CUTOFF
-        zone, no depth gradient) with 16-pixel tiles, the SSIM kernels' tile; built once."""
-        cache = self.__dict__.setdefault("_gvs_cache", {})
-        gv = cache.get((i, F32_GRADE))
-        if gv is None:
-            gv = cache[(i, F32_GRADE)] = tr.make_view(*self._cam_mats(i), self.width, self.height, self._background(device),
-                                                      cutoff=tr.FIT_CUTOFF, core_cutoff=tr.FIT_CUTOFF, depth_grad=False)
-            if F32_GRADE:
-                gv.no_depth_grad = 2
-        return gv
-
-    def _views_direct_ssim(self, means, scales, colors, opacities) -> torch.Tensor:
-        """The fused path's D-SSIM form (dssim_fused): _views_direct_depth's schedule with, per view, the HIP forward
-        keeping its saved sums (no image) and gr_bwd_fit_ssim_gather, whose photometric term is (1 - l) L1 + l D-SSIM;
-        with or without a depth term.  Returns the sum of the view losses."""
-        return self._views_direct_depth(means, scales, colors, opacities, ssim=True)
-
-    def _views_direct_depth(self, means, scales, colors, opacities, sized=None, ssim: bool = False) -> torch.Tensor:
-        """The fused path with the depth term (fit_multiview_stub.py:301-305): per view the HIP forward in the
-        default precision mode (depth output, f32-grade W and D, the depth-gradient footprint), then
-        gr_bwd_fit (L1 + silhouette + depth loss gradients and the render backward) adding the gradient into
-        the stream's accumulator set (in view order: deterministic).  Returns the sum of the view losses.
-        ssim (_views_direct_ssim): gr_bwd_fit_ssim_gather in gr_bwd_fit_gather's place, and without a depth term the
-        views of _ssim_view and no depth sums."""
-        device = means.device
-        m, s, c, o = (t.detach().float().contiguous() for t in (means, scales, colors, opacities))
-        views = self.my_views
-        main = torch.cuda.current_stream(device)
-        ns = max(1, min(NUM_STREAMS, len(views)))
-        side = getattr(self, "_side", None)
-        if ns > 1 and (side is None or len(side) != ns - 1 or side[0].device != device):
-            self._side = side = [torch.cuda.Stream(device) for _ in range(ns - 1)]
-        streams = [main] + (side[:ns - 1] if ns > 1 else [])
-        losses_v = torch.empty(max(1, len(views)), dtype=torch.float32, device=device)
-        shapes = (len(streams),) + tuple(tuple(t.shape) for t in (m, s, c, o))  # kept across steps (_views_direct)
-        cached = getattr(self, "_direct_acc", None)
-        if cached is None or cached[0] != shapes or cached[1][0][0].device != device:
-            self._direct_acc = cached = (shapes, [tuple(torch.empty_like(t) for t in (m, s, c, o)) for _ in streams])
-        acc = cached[1]
-        stats = self._stats_bufs(len(streams), device) if self.density_stats else None
-        if self.refine_cameras:  # (made on the main stream, before the render streams wait for it)
-            self._camera_rows(len(views), device)
-        for st in streams[1:]:
-            st.wait_stream(main)
-        w_sil = self.w_sil if (self.masks is not None and self.w_sil > 0.0) else 0.0
-        g_scale = 1.0 / len(self.targets)
-        prep = getattr(self, "_prep", None)
-        if prep is None or prep.device != device:
-            self._prep = prep = torch.cuda.Stream(device, priority=PREP_PRIORITY)
-        prep.wait_stream(main)
-        pins = self._plan_pins(len(views))
-        cache = getattr(self, "_gvd_cache", None)
-        if cache is None:
-            self._gvd_cache = cache = {}
-        ahead: dict = {}
-
-        depth = self._depth_grad()
-
-        def gv_of(i):
-            if ssim and not depth:
-                return self._ssim_view(i, device)
-            if i not in cache:
-                cache[i] = tr.make_view(*self._cam_mats(i), self.width, self.height, self._background(device),
-                                        depth_grad=True)
-            return cache[i]
-
-        if sized is None:
-            prepare_upto = self._prep_groups(views, ahead, lambda js: tr.prepare_views_native(
-                m, s, c, o, [gv_of(views[q]) for q in js], [pins[q] for q in js]), prep)
-        else:  # device-side sizing (_graph_step)
-            prepare_upto = self._prep_groups(views, ahead, lambda js: tr.prepare_views_sized(
-                m, s, c, o, [tr.sized_view(gv_of(views[q])) for q in js], [sized.caps[q] for q in js],
-                [sized.observed[q] for q in js], sized.ovf), prep)
-        # per view its render and the depth-loss backward up to the per-Gaussian sums (gr_bwd_fit_gather); per batch
-        # of a stream's views one chain-rule pass (gr_reduce_sums with the depth sums), as _views_direct
-        pending: list = [[] for _ in streams]
-        pending_js: list = [[] for _ in streams]  # their positions in `views` (the camera-gradient rows)
-        started = [False] * ns
-        sizes = _batch_sizes(ns, len(views))
-
-        def reduce_pending(k):
-            if pending[k]:
-                with torch.cuda.stream(streams[k]):
-                    tr.reduce_sums_native(m, s, c, o, pending[k], acc[k], accumulate=started[k])
-                    if stats is not None:
-                        tr.density_stats_native(m, s, o, pending[k], self._inv_g_scale(), stats[k])
-                    if self.refine_cameras:
-                        self._camera_grads_batch(m, s, c, o, pending[k], pending_js[k], k)
-                started[k] = True
-                pending[k] = []
-                pending_js[k] = []
-
-        for j, i in enumerate(views):
-            k = j % ns
-            prepare_upto(j)
-            pv = ahead.pop(j)
-            streams[k].wait_event(pv.event)
-            pv.geom.record_stream(streams[k])
-            with torch.cuda.stream(streams[k]):
-                _, _, _, rs = tr.forward_native(m, s, c, o, pv.gv, pv, images=False)  # the backward reads the sums
-                pv = None
-                if ssim:
-                    sums, sums3 = tr.backward_fit_ssim_gather_native(
-                        rs, self.targets[i], self.masks[i] if w_sil > 0.0 else None, w_sil,
-                        self.depths[i] if depth else None, self.w_depth if depth else 0.0, g_scale, self.w_dssim,
-                        losses_v[j:j + 1])
-                else:
-                    sums, sums3 = tr.backward_fit_gather_native(rs, self.targets[i], self.masks[i] if w_sil > 0.0 else None,
-                                                                w_sil, self.depths[i], self.w_depth, g_scale,
-                                                                losses_v[j:j + 1])
-                pending[k].append((rs.gv, sums, sums3) if sums3 is not None else (rs.gv, sums))
-                pending_js[k].append(j)
-                rs = None
-            prepare_upto(j + PREP_AHEAD)
-            if len(pending[k]) >= sizes[k][0]:
-                reduce_pending(k)
-                if len(sizes[k]) > 1:
-                    sizes[k].pop(0)
-        for k in range(ns):
-            reduce_pending(k)
-        for st in streams[1:]:
-            main.wait_stream(st)
-        main.wait_stream(prep)
-        used = min(ns, len(views))
-        # the streams' accumulators (summed in stream order by the caller: gr_fit_param_step or torch adds)
-        self._acc_parts = acc[:used] if used > 0 else [tuple(torch.zeros_like(t) for t in (m, s, c, o))]
-        return losses_v[:len(views)].sum() if views else torch.zeros((), device=device)
+        self._acc_parts = acc[:min(ns, nv)] if nv > 0 else [tuple(torch.zeros_like(t) for t in (m, s, c, o))]
+        return (losses_v[:nv].sum() if views else torch.zeros((), device=device)), tail
 
     def _fused_step_ok(self) -> bool:
         """The fused parameter update applies: plain Adam (torch.optim.Adam defaults: no weight decay, no
@@ -1693,10 +1693,8 @@ class ViewShardedFitter:
             else:
                 # the gradient tensor is kept across steps (zero_grad(set_to_none) drops p.grad each step; the
                 # kernel overwrites every element, in stream order after the previous step's readers)
-                kept = self._grad_keep.get(k) if hasattr(self, "_grad_keep") else None
+                kept = self._grad_keep.get(k)
                 if kept is None or kept.shape != p.shape or kept.device != p.device:
-                    if not hasattr(self, "_grad_keep"):
-                        self._grad_keep = {}
                     self._grad_keep[k] = kept = torch.empty_like(p)
                 grad = kept
             # p.grad is this kept tensor, overwritten in place every step (an alias, not a fresh tensor): a caller that
@@ -1831,10 +1829,8 @@ class ViewShardedFitter:
             depth = self._depth_grad()
             for j0 in range(0, len(views), tr._native.PREPARE_MAX_VIEWS):
                 js = range(j0, min(len(views), j0 + tr._native.PREPARE_MAX_VIEWS))
-                gvs = [tr.make_view(self.cams[views[q]].view, self.cams[views[q]].proj, self.width, self.height,
-                                    self._background(device), depth_grad=True) if depth else self._fit_view(views[q], device)
-                       for q in js]
-                tr.prepare_views_native(m, s, c, o, gvs, [pins[q] for q in js])
+                tr.prepare_views_native(m, s, c, o, [self._step_view(views[q], device, depth) for q in js],
+                                        [pins[q] for q in js])
             torch.cuda.synchronize(device)
             return [tuple(int(x) for x in r) for r in pins[:len(views)].tolist()]
 
@@ -1865,7 +1861,7 @@ class ViewShardedFitter:
 
     def _act_ws_for(self, device) -> torch.Tensor:
         """activations_native's workspace, kept per fitter (made outside any capture: _graph_build asks first)."""
-        ws = getattr(self, "_act_ws", None)
+        ws = self._act_ws
         if ws is None or ws.device != device:
             self._act_ws = ws = torch.zeros(int(tr._native.lib().gr_fit_activations_ws_bytes(0)), dtype=torch.uint8,
                                             device=device)
@@ -1883,28 +1879,11 @@ class ViewShardedFitter:
         """The fused step (step()'s first branch, eager) on device-sized views, for capture."""
         with torch.no_grad():
             means, scales, colors, opacities, reg_t = self._activations_fused(self.params["means"].device)
-            reg_fn = (lambda: reg_t) if reg_t is not None else None
             mode = self._graph_mode()
             if mode in ("batch", "batchgraph"):  # one launch per kernel for up to 8 views (gr_fit_views_batched), one stream
-                reg = reg_fn() if reg_fn else None
-                total = self._views_batched(means, scales, colors, opacities, gs)
-            elif mode == "exec":  # the native executor with capacities (as step()'s executor branch)
-                total = self._views_native(means, scales, colors, opacities, self._depth_grad(), sized=gs)
-                rs = getattr(self, "_prep", None) if EXEC_STREAMS else None
-                reg = None
-                if reg_fn and rs is not None:
-                    main = torch.cuda.current_stream(means.device)
-                    with torch.cuda.stream(rs):
-                        reg = reg_fn()
-                    reg.record_stream(main)
-                    main.wait_stream(rs)
-                elif reg_fn:
-                    reg = reg_fn()
-            elif self._depth_grad():
-                reg = reg_fn() if reg_fn else None
-                total = self._views_direct_depth(means, scales, colors, opacities, sized=gs)
-            else:
-                total, reg = self._views_direct(means, scales, colors, opacities, reg_fn, sized=gs)
+                total, reg = self._views_batched(means, scales, colors, opacities, gs), reg_t
+            else:  # "exec": the native executor with capacities; else the Python schedule (as step()'s fused branch)
+                total, reg = self._views_fused(means, scales, colors, opacities, reg_t, mode == "exec", sized=gs)
             loss = total / len(self.targets)
             if reg is not None:
                 loss = loss + reg
@@ -1913,7 +1892,7 @@ class ViewShardedFitter:
     def _graph_build(self, device, counts=None, old_caps=None):
         """(Re)capture the step: capacities from `counts` (or a probe), the device step counter at the updates applied
         so far (the optimizer's step count), a fresh schedule table when it runs short."""
-        gs = getattr(self, "_gs", None)
+        gs = self._gs
         if gs is None:
             gs = self._gs = _GraphState()
         gs.graph = None
@@ -1947,7 +1926,7 @@ class ViewShardedFitter:
         return gs
 
     def _graph_step(self, device) -> torch.Tensor:
-        gs = getattr(self, "_gs", None)
+        gs = self._gs
         if gs is None or gs.graph is None or gs.key != self._graph_key():
             self.graph_sync()
             counts = None
@@ -2015,19 +1994,7 @@ class ViewShardedFitter:
         bkey = (n, depth, tuple((int(cp.num_pairs), int(cp.num_core_pairs)) for cp in gs.caps), str(device))
         bw = getattr(gs, "batch_ws", None)
         if bw is None or bw[0] != bkey:
-            gvs = []
-            for i in views:
-                if depth:
-                    cam = self.cams[i]
-                    gvd = getattr(self, "_gvd_cache", None)
-                    if gvd is None:
-                        self._gvd_cache = gvd = {}
-                    if i not in gvd:
-                        gvd[i] = tr.make_view(cam.view, cam.proj, self.width, self.height, self._background(device),
-                                              depth_grad=True)
-                    gvs.append(tr.sized_view(gvd[i]))
-                else:
-                    gvs.append(tr.sized_view(self._fit_view(i, device)))
+            gvs = [tr.sized_view(self._step_view(i, device, depth)) for i in views]
             u8 = dict(dtype=torch.uint8, device=device)
             gb = int(L.gr_geom_bytes(n))
             ws = []
@@ -2046,15 +2013,11 @@ class ViewShardedFitter:
         _, gvs, ws = bw
         losses_v = torch.empty(max(1, len(views)), dtype=torch.float32, device=device)
         # the chain rules in one accumulator set, batches of up to REDUCE_BATCH views (every view is gathered before
-        # the first chain rule, so no short tail batch): the same sums in the same order as _views_direct /
-        # _views_direct_depth with GR_STREAMS=1 and GR_REDUCE_TAIL=0, so the same parameters bit for bit (one chain-rule
+        # the first chain rule, so no short tail batch): the same sums in the same order as _views_scheduled with
+        # GR_STREAMS=1 and GR_REDUCE_TAIL=0, so the same parameters bit for bit (one chain-rule
         # launch for up to 16 views, one accumulator for the update to read instead of one per stream)
         ns = 1
-        shapes = (ns,) + tuple(tuple(t.shape) for t in (m, s, c, o))
-        cached = getattr(self, "_direct_acc", None)
-        if cached is None or cached[0] != shapes or cached[1][0][0].device != device:
-            self._direct_acc = cached = (shapes, [tuple(torch.empty_like(t) for t in (m, s, c, o)) for _ in range(ns)])
-        acc = cached[1]
+        acc, _ = self._acc_sets("direct", ns, m, s, c, o)
         stream = ctypes_stream(device)
         cd = tr._color_dim(c)
         for j0 in range(0, len(views), nat.PREPARE_MAX_VIEWS):
@@ -2101,7 +2064,7 @@ class ViewShardedFitter:
         """The step goes eager while replayed steps may still be in flight (the graph's conditions changed, e.g.
         F32_GRADE toggled): settle them first (an overflowed one is redone and its loss rewritten, and the host's Adam
         step count corrected), then drop the graph, so that a later capture counts only its own replays."""
-        gs = getattr(self, "_gs", None)
+        gs = self._gs
         if gs is None or gs.graph is None:
             return
         self.graph_sync()
@@ -2112,7 +2075,7 @@ class ViewShardedFitter:
     def graph_sync(self) -> None:
         """Wait for the replayed steps and redo any that overflowed (densify, the parameters' readers and the end of a
         fit call this; a no-op without a graph)."""
-        gs = getattr(self, "_gs", None)
+        gs = self._gs
         if gs is None or gs.graph is None:
             return
         torch.cuda.synchronize(self.params["means"].device)
@@ -2120,15 +2083,8 @@ class ViewShardedFitter:
 
     # ---- evaluation (held-out view metrics) ---------------------------------------------------------------------
     def _eval_view(self, cam, device) -> "tr._native.GrView":
-        """The gr_view an evaluation renders ``cam`` with: the one render_gaussians_torch(..., depth_grad=False) makes
-        for the fitter's background (16-pixel tiles, default_cutoff(False), the default core cutoff), built once per
-        camera object (kept with it, so the key stays its own)."""
-        cache = self.__dict__.setdefault("_eval_gv", {})
-        hit = cache.get(id(cam))
-        if hit is None or hit[0] is not cam or hit[2] != str(device):
-            gv = tr.make_view(cam.view, cam.proj, self.width, self.height, self._background(device), depth_grad=False)
-            cache[id(cam)] = hit = (cam, gv, str(device))
-        return hit[1]
+        """The gr_view an evaluation renders ``cam`` with (_gr_view's `eval`)."""
+        return self._gr_view("eval", cam, device)
 
     def _eval_native_ok(self, device, targets) -> bool:
         """evaluate() through the HIP metrics kernel: the preconditions of _direct() that concern it (the HIP render
@@ -2145,69 +2101,44 @@ class ViewShardedFitter:
             return activations_native(self.params)[:4]
         return tuple(t.detach() for t in activations(self.params))
 
-    def _eval_streams(self, device, ns: int):
-        """The fit step's own render and preparation streams (made here when no step has run yet)."""
-        side = getattr(self, "_side", None)
-        if ns > 1 and (side is None or len(side) != ns - 1 or side[0].device != device):
-            self._side = side = [torch.cuda.Stream(device) for _ in range(ns - 1)]
-        prep = getattr(self, "_prep", None)
-        if prep is None or prep.device != device:
-            self._prep = prep = torch.cuda.Stream(device, priority=PREP_PRIORITY)
-        return (side[:ns - 1] if ns > 1 else []), prep
-
-    def _eval_native(self, m, s, c, o, gvs, targets, out) -> None:
-        """gr_eval_views: the views' metrics into ``out`` (len(gvs), 3) through the native executor, one C call."""
+    def _exec_views(self, fn: str, m, s, c, o, gvs, targets, out) -> None:
+        """One native executor call over views that are only rendered: gr_eval_views (the views' metrics against
+        ``targets`` into ``out`` (len(gvs), 3)) or gr_contrib_views (targets None: every view's peak blend weights into
+        the one ``out``)."""
         device = m.device
-        ns = max(1, min(NUM_STREAMS, len(gvs)))
         arr = (tr._native.GrFitTarget * len(gvs))()
-        for j, (gv, t) in enumerate(zip(gvs, targets)):
+        for j, gv in enumerate(gvs):
             arr[j].view = gv
-            arr[j].target_rgb = t.data_ptr()
+            arr[j].target_rgb = targets[j].data_ptr() if targets is not None else None
             arr[j].target_mask = None
             arr[j].target_depth = None
-        cfg = tr._native.GrFitConfig(NUM_STREAMS, PREP_AHEAD, PREP_GROUP, PREP_FIRST, REDUCE_BATCH, min(REDUCE_TAIL, REDUCE_BATCH))
-        if EXEC_STREAMS:  # the driver's own torch streams, as _views_native
-            side, prep = self._eval_streams(device, ns)
-            rs = (ctypes.c_void_p * max(1, ns - 1))(*[st.cuda_stream for st in side])  # (read during the call only)
-            cfg.render_streams = rs
-            cfg.prep_stream = prep.cuda_stream
-        tr._native.check(tr._native.lib().gr_eval_views(
+        cfg = self._exec_config(device, max(1, min(NUM_STREAMS, len(gvs))))
+        tr._native.check(getattr(tr._native.lib(), fn)(
             tr._native.executor(device.index or 0), ctypes.byref(cfg), len(gvs), arr, int(m.shape[0]), tr._native.ptr(m),
             tr._native.ptr(s), tr._native.ptr(c), tr._color_dim(c), tr._native.ptr(o), tr._native.ptr(out),
-            ctypes_stream(device)), "gr_eval_views")
+            ctypes_stream(device)), fn)
         self._eval_keep = (m, s, c, o)  # read by the executor's streams until the caller's stream passes them
 
     def _eval_direct(self, m, s, c, o, gvs, targets, out) -> None:
-        """The Python schedule of the same calls: preparations ahead on the preparation stream, view j on render
-        stream j % NUM_STREAMS: forward_native (saved sums only) + eval_view_native into ``out[j]``."""
-        device = m.device
-        main = torch.cuda.current_stream(device)
-        ns = max(1, min(NUM_STREAMS, len(gvs)))
-        side, prep = self._eval_streams(device, ns)
-        streams = [main] + side
-        for st in streams[1:]:
-            st.wait_stream(main)
-        prep.wait_stream(main)
-        pins = self._plan_pins(len(gvs))
-        ahead: dict = {}
-        views = list(range(len(gvs)))
-        prepare_upto = self._prep_groups(views, ahead, lambda js: tr.prepare_views_native(
-            m, s, c, o, [gvs[q] for q in js], [pins[q] for q in js]), prep)
-        for j in views:
-            k = j % ns
-            prepare_upto(j)
-            pv = ahead.pop(j)
-            streams[k].wait_event(pv.event)
-            pv.geom.record_stream(streams[k])
-            with torch.cuda.stream(streams[k]):
-                _, _, _, rs = tr.forward_native(m, s, c, o, pv.gv, pv, images=False)
-                pv = None
-                tr.eval_view_native(rs, targets[j], out[j])
-                rs = None
-            prepare_upto(j + PREP_AHEAD)
-        for st in streams[1:]:
-            main.wait_stream(st)
-        main.wait_stream(prep)
+        """The Python schedule of gr_eval_views' calls (_view_loop): per view forward_native (saved sums only) +
+        eval_view_native into ``out[j]``."""
+        def body(j, take):
+            pv = take(j)
+            _, _, _, rs = tr.forward_native(m, s, c, o, pv.gv, pv, images=False)
+            pv = None
+            tr.eval_view_native(rs, targets[j], out[j])
+
+        self._view_loop(m.device, len(gvs), self._preparer(m, s, c, o, gvs.__getitem__, len(gvs)), body)
+
+    def _contrib_direct(self, m, s, c, o, gvs, peak) -> None:
+        """The Python schedule of gr_contrib_views' calls (_view_loop): per view forward_native (saved sums only) +
+        contrib_view_native, every view into the one ``peak``."""
+        def body(j, take):
+            pv = take(j)
+            _, _, _, rs = tr.forward_native(m, s, c, o, pv.gv, pv, images=False)
+            tr.contrib_view_native(rs, pv, peak)
+
+        self._view_loop(m.device, len(gvs), self._preparer(m, s, c, o, gvs.__getitem__, len(gvs)), body)
 
     def evaluate(self, cams: Optional[list] = None, targets: Optional[list] = None) -> dict:
         """Per-view metrics of the current Gaussians against target images: float64 numpy arrays ``l1`` (mean|x - y|),
@@ -2241,7 +2172,7 @@ class ViewShardedFitter:
                 gvs = [self._eval_view(cams[i], device) for i in mine]
                 out = torch.empty((len(mine), tr._native.EVAL_METRICS), dtype=torch.float32, device=device)
                 if self._native_exec() and GATHER:
-                    self._eval_native(m, s, c, o, gvs, [targets[i] for i in mine], out)
+                    self._exec_views("gr_eval_views", m, s, c, o, gvs, [targets[i] for i in mine], out)
                 else:
                     self._eval_direct(m, s, c, o, gvs, [targets[i] for i in mine], out)
                 res[mine] = out
@@ -2264,59 +2195,6 @@ class ViewShardedFitter:
                 "mean_psnr": mean(psnr), "mean_ssim": mean(ssim)}
 
     # ---- contribution (peak blend weight per Gaussian) ----------------------------------------------------------
-    def _contrib_native(self, m, s, c, o, gvs, peak) -> None:
-        """gr_contrib_views: the views' peak blend weights into ``peak`` through the native executor, one C call."""
-        device = m.device
-        ns = max(1, min(NUM_STREAMS, len(gvs)))
-        arr = (tr._native.GrFitTarget * len(gvs))()
-        for j, gv in enumerate(gvs):
-            arr[j].view = gv
-            arr[j].target_rgb = None
-            arr[j].target_mask = None
-            arr[j].target_depth = None
-        cfg = tr._native.GrFitConfig(NUM_STREAMS, PREP_AHEAD, PREP_GROUP, PREP_FIRST, REDUCE_BATCH, min(REDUCE_TAIL, REDUCE_BATCH))
-        if EXEC_STREAMS:  # the driver's own torch streams, as _views_native
-            side, prep = self._eval_streams(device, ns)
-            rs = (ctypes.c_void_p * max(1, ns - 1))(*[st.cuda_stream for st in side])  # (read during the call only)
-            cfg.render_streams = rs
-            cfg.prep_stream = prep.cuda_stream
-        tr._native.check(tr._native.lib().gr_contrib_views(
-            tr._native.executor(device.index or 0), ctypes.byref(cfg), len(gvs), arr, int(m.shape[0]), tr._native.ptr(m),
-            tr._native.ptr(s), tr._native.ptr(c), tr._color_dim(c), tr._native.ptr(o), tr._native.ptr(peak),
-            ctypes_stream(device)), "gr_contrib_views")
-        self._eval_keep = (m, s, c, o)  # read by the executor's streams until the caller's stream passes them
-
-    def _contrib_direct(self, m, s, c, o, gvs, peak) -> None:
-        """The Python schedule of the same calls (_eval_direct's): view j on render stream j % NUM_STREAMS,
-        forward_native (saved sums only) + contrib_view_native, every view into the one ``peak``."""
-        device = m.device
-        main = torch.cuda.current_stream(device)
-        ns = max(1, min(NUM_STREAMS, len(gvs)))
-        side, prep = self._eval_streams(device, ns)
-        streams = [main] + side
-        for st in streams[1:]:
-            st.wait_stream(main)
-        prep.wait_stream(main)
-        pins = self._plan_pins(len(gvs))
-        ahead: dict = {}
-        views = list(range(len(gvs)))
-        prepare_upto = self._prep_groups(views, ahead, lambda js: tr.prepare_views_native(
-            m, s, c, o, [gvs[q] for q in js], [pins[q] for q in js]), prep)
-        for j in views:
-            k = j % ns
-            prepare_upto(j)
-            pv = ahead.pop(j)
-            streams[k].wait_event(pv.event)
-            pv.geom.record_stream(streams[k])
-            with torch.cuda.stream(streams[k]):
-                _, _, _, rs = tr.forward_native(m, s, c, o, pv.gv, pv, images=False)
-                tr.contrib_view_native(rs, pv, peak)
-                pv = rs = None
-            prepare_upto(j + PREP_AHEAD)
-        for st in streams[1:]:
-            main.wait_stream(st)
-        main.wait_stream(prep)
-
     def contribution_state(self, cams: Optional[list] = None) -> torch.Tensor:
         """Per Gaussian in canonical order (as canonical_params), its peak blend weight: the maximum over the views
         ``cams`` (default: the training cameras) and their pixels of w / (1 + W), its share of the pixel under this
@@ -2339,7 +2217,7 @@ class ViewShardedFitter:
                 if device.type == "cuda":
                     gvs = [self._eval_view(cams[i], device) for i in mine]
                     if self._native_exec() and GATHER:
-                        self._contrib_native(m, s, c, o, gvs, peak)
+                        self._exec_views("gr_contrib_views", m, s, c, o, gvs, None, peak)
                     else:
                         self._contrib_direct(m, s, c, o, gvs, peak)
                 else:
@@ -2402,7 +2280,7 @@ class ViewShardedFitter:
                                    "over": int((avg >= grad_threshold).sum())}
         if on_device is None:
             on_device = self.params["means"].device.type == "cuda" and n_now >= DEVICE_DENSIFY_MIN
-        if on_device and getattr(self, "_dgen", None) is None:
+        if on_device and self._dgen is None:
             self._dgen = torch.Generator(device=self.params["means"].device).manual_seed(self.densify_seed)
 
         def decide():

@@ -29,28 +29,52 @@ def setup(fm, cuda):
     return cams, targets, masks, depths
 
 
-def _one_step(fm, cuda, setup, lam, fused, direct=True, native=None, depth=False):
-    """(loss, gradients, updated parameters, view_loss calls, (_direct, _graph_ok)) of a fresh fitter's first step;
-    masks on and no depth term, or with `depth` a depth term and no masks."""
+# 11 views of 64x48, 300 Gaussians, on 4 streams in reduction batches of 2 with a tail of 1 (a stream of three views
+# reduces three times, the last a short tail) and preparation groups of 1, then 2, three views ahead (the groups run
+# out mid-step), for two steps: the batch and tail bookkeeping of the Python schedule's loop
+SMALL_BATCHES = dict(NUM_STREAMS=4, REDUCE_BATCH=2, REDUCE_TAIL=1, PREP_GROUP=2, PREP_FIRST=1, PREP_AHEAD=3)
+
+
+@pytest.fixture(scope="module")
+def setup_small(fm, cuda):
+    w, h, views = 64, 48, 11
+    cams = fm.orbit_cameras(views, w, h, cuda)
+    g = torch.Generator(device=cuda).manual_seed(9)
+    targets = [torch.rand((h, w, 3), generator=g, device=cuda) for _ in cams]
+    masks = [(t.mean(dim=2) > 0.5).float() for t in targets]
+    return cams, targets, masks, None
+
+
+def _one_step(fm, cuda, setup, lam, fused, direct=True, native=None, depth=False, knobs=None, steps=1, n=N):
+    """(loss, gradients, updated parameters, view_loss calls, (_direct, _graph_ok)) of a fresh fitter's first step (of
+    its last of `steps`); masks on and no depth term, or with `depth` a depth term and no masks.  knobs: module
+    switches of the schedule set for the run."""
     bench = importlib.import_module("bench")
     cams, targets, masks, depths = setup
+    h, w = targets[0].shape[:2]
     saved = fm.DIRECT_BACKWARD, fm.NATIVE_EXEC
+    saved_knobs = {k: getattr(fm, k) for k in (knobs or {})}
     fm.DIRECT_BACKWARD = direct
     if native is not None:
         fm.NATIVE_EXEC = native
     try:
-        f = fm.ViewShardedFitter(bench.synthetic_params(N, cuda), cams, targets, W, H, masks=None if depth else masks,
+        for k, v in (knobs or {}).items():
+            setattr(fm, k, v)
+        f = fm.ViewShardedFitter(bench.synthetic_params(n, cuda), cams, targets, w, h, masks=None if depth else masks,
                                  depths=depths if depth else None, dssim_weight=lam, dssim_fused=fused)
         calls = []
         inner = f.view_loss
         f.view_loss = lambda *a, **kw: (calls.append(a[0]), inner(*a, **kw))[1]
         flags = f._direct(cuda), f._graph_ok(cuda)
-        loss = f.step().detach().clone()
+        for _ in range(steps):
+            loss = f.step().detach().clone()
         torch.cuda.synchronize()
         grads = {k: v.grad.detach().clone() for k, v in f.params.items()}
         params = {k: v.detach().clone() for k, v in f.params.items()}
     finally:
         fm.DIRECT_BACKWARD, fm.NATIVE_EXEC = saved
+        for k, v in saved_knobs.items():
+            setattr(fm, k, v)
     return loss, grads, params, calls, flags
 
 
@@ -79,11 +103,15 @@ def test_step_matches_autograd_path(fm, cuda, setup):
     assert ok
 
 
-@pytest.mark.parametrize("depth", [False, True], ids=["masks", "depth"])
-def test_executor_matches_python_schedule(fm, cuda, setup, depth):
+@pytest.mark.parametrize("depth", [False, True, "small-batches"], ids=["masks", "depth", "small-batches"])
+def test_executor_matches_python_schedule(fm, cuda, setup, setup_small, depth):
     """The native executor's D-SSIM form against the Python schedule, bit for bit and run to run; with masks, and
-    with a depth term and no masks."""
-    runs = [_one_step(fm, cuda, setup, LAM, True, native=nv, depth=depth) for nv in ("1", "1", "0", "0")]
+    with a depth term and no masks; and with masks at SMALL_BATCHES' knobs over two steps."""
+    if depth == "small-batches":
+        runs = [_one_step(fm, cuda, setup_small, LAM, True, native=nv, knobs=SMALL_BATCHES, steps=2, n=300)
+                for nv in ("1", "1", "0", "0")]
+    else:
+        runs = [_one_step(fm, cuda, setup, LAM, True, native=nv, depth=depth) for nv in ("1", "1", "0", "0")]
     for r in runs:
         assert r[3] == [] and r[4][0]
     ref = runs[0]

@@ -1,5 +1,5 @@
 """GPU: the native fit executor (gr_fit_views, 3dgaussian_amd/csrc/gr_fit_exec.cpp) runs the Python
-driver's per-view schedule (fit_multiview._views_direct / _views_direct_depth: streams, preparation
+driver's per-view schedule (fit_multiview._view_loop under _views_scheduled: streams, preparation
 groups, reduction batches) and gives bit-identical losses and parameters after a fit step."""
 from __future__ import annotations
 
@@ -12,12 +12,20 @@ import torch
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("streams", [1, 4])
-@pytest.mark.parametrize("depth", [False, True])
-def test_native_executor_matches_python_schedule(cuda, streams, depth):
+# 11 views on 4 streams in reduction batches of 2 with a tail of 1 (a stream of three views reduces three times, the
+# last a short tail) and preparation groups of 1, then 2, three views ahead (the groups run out mid-step): the batch
+# and tail bookkeeping of the Python schedule's loop, which the default knobs (one batch per stream) barely touch
+SMALL_BATCHES = dict(REDUCE_BATCH=2, REDUCE_TAIL=1, PREP_GROUP=2, PREP_FIRST=1, PREP_AHEAD=3)
+
+
+@pytest.mark.parametrize("depth,streams,knobs", [
+    pytest.param(False, 1, None, id="False-1"), pytest.param(False, 4, None, id="False-4"),
+    pytest.param(True, 1, None, id="True-1"), pytest.param(True, 4, None, id="True-4"),
+    pytest.param(False, 4, SMALL_BATCHES, id="small-batches")])
+def test_native_executor_matches_python_schedule(cuda, streams, depth, knobs):
     fm = importlib.import_module("3dgaussian_amd.fit_multiview")
     bench = importlib.import_module("bench")
-    W, H, V = 256, 192, 11
+    (W, H, N), V = ((256, 192, 50_000) if knobs is None else (64, 48, 300)), 11
     cams = fm.orbit_cameras(V, W, H, cuda)
     g = torch.Generator(device=cuda).manual_seed(21)
     targets = [torch.rand((H, W, 3), generator=g, device=cuda) for _ in range(V)]
@@ -25,21 +33,61 @@ def test_native_executor_matches_python_schedule(cuda, streams, depth):
     depths = [torch.rand((H, W), generator=g, device=cuda) for _ in range(V)] if depth else None
     res = {}
     saved = fm.NATIVE_EXEC, fm.NUM_STREAMS, fm.GRAPH_MODE
+    saved_knobs = {k: getattr(fm, k) for k in (knobs or {})}
     try:
+        for k, v in (knobs or {}).items():
+            setattr(fm, k, v)
         for native in (False, True):
             # the eager schedules every step (not the default's batched steps for views this small)
             fm.NATIVE_EXEC, fm.NUM_STREAMS, fm.GRAPH_MODE = ("1" if native else "0"), streams, "0"
-            f = fm.ViewShardedFitter(bench.synthetic_params(50_000, cuda), cams, targets, W, H, masks=masks, depths=depths)
+            f = fm.ViewShardedFitter(bench.synthetic_params(N, cuda), cams, targets, W, H, masks=masks, depths=depths)
             losses = [float(f.step()) for _ in range(2)]
             res[native] = (losses, {k: v.detach().clone() for k, v in f.params.items()})
     finally:
         fm.NATIVE_EXEC, fm.NUM_STREAMS, fm.GRAPH_MODE = saved
+        for k, v in saved_knobs.items():
+            setattr(fm, k, v)
     assert res[True][0] == res[False][0]
     # the default ("auto") takes the native executor for views this small
     f = fm.ViewShardedFitter(bench.synthetic_params(1000, cuda), cams, targets, W, H)
     assert fm.NATIVE_EXEC != "auto" or f._native_exec()
     for k in res[False][1]:
         assert torch.equal(res[True][1][k], res[False][1][k]), k
+
+
+@pytest.mark.parametrize("native", ["0", "1"], ids=["python", "executor"])
+def test_calls_over_fewer_views_keep_the_fit_streams(cuda, native):
+    """evaluate() over two held-out views and contribution_state() over one, between two steps of a fit on 4 streams:
+    the fit's render streams are the same objects afterwards (the stream helper only ever adds streams), and the
+    parameters equal bit for bit those of a fit that stepped twice with nothing in between."""
+    fm = importlib.import_module("3dgaussian_amd.fit_multiview")
+    bench = importlib.import_module("bench")
+    W, H, V = 64, 48, 11
+    cams = fm.orbit_cameras(V + 2, W, H, cuda)
+    g = torch.Generator(device=cuda).manual_seed(21)
+    targets = [torch.rand((H, W, 3), generator=g, device=cuda) for _ in range(V + 2)]
+    saved = fm.NATIVE_EXEC, fm.NUM_STREAMS, fm.GRAPH_MODE
+    res = {}
+    try:
+        fm.NATIVE_EXEC, fm.NUM_STREAMS, fm.GRAPH_MODE = native, 4, "0"
+        for between in (False, True):
+            f = fm.ViewShardedFitter(bench.synthetic_params(300, cuda), cams[:V], targets[:V], W, H)
+            f.step()
+            streams = list(f._side) + [f._prep]
+            assert len(f._side) == 3
+            if between:
+                ev = f.evaluate(cams[V:], targets[V:])
+                assert ev["l1"].shape == (2,)
+                assert f.contribution_state(cams[V:V + 1]).shape == (300,)
+            f.step()
+            torch.cuda.synchronize()
+            after = list(f._side) + [f._prep]
+            assert len(after) == len(streams) and all(a is b for a, b in zip(after, streams))
+            res[between] = {k: v.detach().clone() for k, v in f.params.items()}
+    finally:
+        fm.NATIVE_EXEC, fm.NUM_STREAMS, fm.GRAPH_MODE = saved
+    for k in res[False]:
+        assert torch.equal(res[True][k], res[False][k]), k
 
 
 def test_native_executor_at_c4_size(cuda):
