@@ -43,6 +43,7 @@
 #include <atomic>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/gr_hip.h"
@@ -913,8 +914,14 @@ __global__ __launch_bounds__(256) void k_emit_zones(ViewK v, int n, const int4* 
 // A kernel's blocks for several views of the same image size in ONE launch: block b belongs to the view whose block
 // range [first[v], first[v + 1]) holds it and runs exactly as block b - first[v] of that view's own launch (a per-view
 // grid of gx x (count / gx) blocks), with that view's arguments.  Small views (C2, C3: ~300 work items per splat, a
-// few hundred blocks per binning kernel) leave most CUs idle per launch; eight views per launch fill them.  The kernel
-// bodies take blockIdx / gridDim as parameters (shadowing the builtins), so the single-view launch is the same code.
+// few hundred blocks per binning kernel) leave most CUs idle per launch; eight views per launch fill them.
+// Each such kernel x states its parameters once, as struct k_x_args, and both of its forms take that struct: the
+// one-view kernel k_x(k_x_args) and the batched k_x_views(VBatch<k_x_args>), which looks its block's view up
+// (vbatch_block).  Both call k_x_run(args, VBlock), the one place that expands the struct into k_x_body's
+// positional __restrict__ parameters; the body takes blockIdx / gridDim as parameters (shadowing the builtins), so the
+// two forms run the same code.  (k_fwd32_l1 and k_bwd32 still have the older arrangement, a positional one-view kernel
+// and a batched kernel that each call the body: see the note above k_fwd32_l1.)  On the host one builder per kernel (emit_offsets_args(ViewCtx) ...) fills the struct
+// for the one-view entry points and for gr_fit_views_batched alike.
 constexpr int GR_BATCH_MAX = 8;
 struct BI {
   int x, y;
@@ -931,6 +938,20 @@ __device__ __forceinline__ int vbatch_view(const VBatch<A>& B, int b) {
   int v = 0;
   while (v + 1 < B.nv && b >= B.first[v + 1]) ++v;
   return v;
+}
+// A block's place in a launch: its index and the grid, as its kernel body sees them.
+struct VBlock {
+  int view;
+  BI block, grid;
+};
+__device__ __forceinline__ VBlock own_block() {  // a one-view launch
+  return {0, BI{(int)blockIdx.x, (int)blockIdx.y}, BI{(int)gridDim.x, (int)gridDim.y}};
+}
+template <class A>
+__device__ __forceinline__ VBlock vbatch_block(const VBatch<A>& B) {  // a batched launch: the view's own grid
+  const int vb = vbatch_view(B, (int)blockIdx.x);
+  const int lb = (int)blockIdx.x - B.first[vb], gx = B.gx[vb];
+  return {vb, BI{lb % gx, lb / gx}, BI{gx, (B.first[vb + 1] - B.first[vb]) / gx}};
 }
 
 constexpr int EWIN_BLK = 4096;  // pairs staged in LDS per block
@@ -989,12 +1010,6 @@ __device__ __forceinline__ void k_emit_offsets_body(ViewK v, int n, const int4* 
     ids[k] = sI[e];
   }
 }
-__global__ __launch_bounds__(256) void k_emit_offsets(ViewK v, int n, const int4* __restrict__ rect, const Cnt2* __restrict__ counts,
-                                                      const unsigned long long* __restrict__ bsum, Cnt2* __restrict__ offsets,
-                                                      const float4* __restrict__ rec, uint16_t* __restrict__ keys,
-                                                      int* __restrict__ ids, int* __restrict__ fan) {
-  k_emit_offsets_body(v, n, rect, counts, bsum, offsets, rec, keys, ids, fan, BI{(int)blockIdx.x, (int)blockIdx.y}, BI{(int)gridDim.x, (int)gridDim.y});
-}
 struct k_emit_offsets_args {
   ViewK v;
   int n;
@@ -1007,11 +1022,15 @@ struct k_emit_offsets_args {
   int* ids;
   int* fan;
 };
+__device__ __forceinline__ void k_emit_offsets_run(const k_emit_offsets_args& a, const VBlock& b) {
+  k_emit_offsets_body(a.v, a.n, a.rect, a.counts, a.bsum, a.offsets, a.rec, a.keys, a.ids, a.fan, b.block, b.grid);
+}
+__global__ __launch_bounds__(256) void k_emit_offsets(k_emit_offsets_args a) {
+  k_emit_offsets_run(a, own_block());
+}
 __global__ __launch_bounds__(256) void k_emit_offsets_views(VBatch<k_emit_offsets_args> B) {
-  const int vb = vbatch_view(B, (int)blockIdx.x);
-  const k_emit_offsets_args& a = B.a[vb];
-  const int lb = (int)blockIdx.x - B.first[vb], gx = B.gx[vb];
-  k_emit_offsets_body(a.v, a.n, a.rect, a.counts, a.bsum, a.offsets, a.rec, a.keys, a.ids, a.fan, BI{lb % gx, lb / gx}, BI{gx, (B.first[vb + 1] - B.first[vb]) / gx});
+  const VBlock b = vbatch_block(B);
+  k_emit_offsets_run(B.a[b.view], b);
 }
 
 
@@ -1318,18 +1337,19 @@ __device__ __forceinline__ void k_tile_count_body(TZones Z, int tiles, const BI 
   __syncthreads();
   for (int t = threadIdx.x; t < tiles; t += 256) zz.M[(size_t)c * tiles + t] = hist[t];
 }
-__global__ __launch_bounds__(256) void k_tile_count(TZones Z, int tiles) {
-  k_tile_count_body(Z, tiles, BI{(int)blockIdx.x, (int)blockIdx.y}, BI{(int)gridDim.x, (int)gridDim.y});
-}
 struct k_tile_count_args {
   TZones Z;
   int tiles;
 };
+__device__ __forceinline__ void k_tile_count_run(const k_tile_count_args& a, const VBlock& b) {
+  k_tile_count_body(a.Z, a.tiles, b.block, b.grid);
+}
+__global__ __launch_bounds__(256) void k_tile_count(k_tile_count_args a) {
+  k_tile_count_run(a, own_block());
+}
 __global__ __launch_bounds__(256) void k_tile_count_views(VBatch<k_tile_count_args> B) {
-  const int vb = vbatch_view(B, (int)blockIdx.x);
-  const k_tile_count_args& a = B.a[vb];
-  const int lb = (int)blockIdx.x - B.first[vb], gx = B.gx[vb];
-  k_tile_count_body(a.Z, a.tiles, BI{lb % gx, lb / gx}, BI{gx, (B.first[vb + 1] - B.first[vb]) / gx});
+  const VBlock b = vbatch_block(B);
+  k_tile_count_run(B.a[b.view], b);
 }
 
 
@@ -1425,11 +1445,6 @@ __device__ __forceinline__ void k_tile_colscan_body(TZones Z, int tiles, int2* _
   work_items_zones<true, GR_CS_THREADS>(tiles, z1.zbase, z0.K > 0 ? z0.T : nullptr, z1.K > 0 ? z1.T : nullptr,
                                   ranges, items, num_items, tile_item0, ticket, Z.ch);
 }
-__global__ __launch_bounds__(GR_CS_THREADS) void k_tile_colscan(TZones Z, int tiles, int2* __restrict__ ranges,
-                                                             int4* __restrict__ items, int* __restrict__ num_items,
-                                                             int* __restrict__ tile_item0, int* __restrict__ ticket) {
-  k_tile_colscan_body(Z, tiles, ranges, items, num_items, tile_item0, ticket, BI{(int)blockIdx.x, (int)blockIdx.y}, BI{(int)gridDim.x, (int)gridDim.y});
-}
 struct k_tile_colscan_args {
   TZones Z;
   int tiles;
@@ -1439,11 +1454,15 @@ struct k_tile_colscan_args {
   int* tile_item0;
   int* ticket;
 };
+__device__ __forceinline__ void k_tile_colscan_run(const k_tile_colscan_args& a, const VBlock& b) {
+  k_tile_colscan_body(a.Z, a.tiles, a.ranges, a.items, a.num_items, a.tile_item0, a.ticket, b.block, b.grid);
+}
+__global__ __launch_bounds__(GR_CS_THREADS) void k_tile_colscan(k_tile_colscan_args a) {
+  k_tile_colscan_run(a, own_block());
+}
 __global__ __launch_bounds__(GR_CS_THREADS) void k_tile_colscan_views(VBatch<k_tile_colscan_args> B) {
-  const int vb = vbatch_view(B, (int)blockIdx.x);
-  const k_tile_colscan_args& a = B.a[vb];
-  const int lb = (int)blockIdx.x - B.first[vb], gx = B.gx[vb];
-  k_tile_colscan_body(a.Z, a.tiles, a.ranges, a.items, a.num_items, a.tile_item0, a.ticket, BI{lb % gx, lb / gx}, BI{gx, (B.first[vb + 1] - B.first[vb]) / gx});
+  const VBlock b = vbatch_block(B);
+  k_tile_colscan_run(B.a[b.view], b);
 }
 
 
@@ -1657,12 +1676,6 @@ __device__ __forceinline__ void k_tile_place_body(TZones Z, int tiles, int bits,
     }
   }
 }
-template <int WAVES>
-__global__ __launch_bounds__(64 * WAVES, GR_PLACE_WAVES) void k_tile_place(TZones Z, int tiles, int bits,
-                                                                    const int2* __restrict__ ranges,
-                                                                    int* __restrict__ pairs_out, int* __restrict__ pos_of) {
-  k_tile_place_body<WAVES>(Z, tiles, bits, ranges, pairs_out, pos_of, BI{(int)blockIdx.x, (int)blockIdx.y}, BI{(int)gridDim.x, (int)gridDim.y});
-}
 struct k_tile_place_args {
   TZones Z;
   int tiles;
@@ -1672,11 +1685,17 @@ struct k_tile_place_args {
   int* pos_of;
 };
 template <int WAVES>
+__device__ __forceinline__ void k_tile_place_run(const k_tile_place_args& a, const VBlock& b) {
+  k_tile_place_body<WAVES>(a.Z, a.tiles, a.bits, a.ranges, a.pairs_out, a.pos_of, b.block, b.grid);
+}
+template <int WAVES>
+__global__ __launch_bounds__(64 * WAVES, GR_PLACE_WAVES) void k_tile_place(k_tile_place_args a) {
+  k_tile_place_run<WAVES>(a, own_block());
+}
+template <int WAVES>
 __global__ __launch_bounds__(64 * WAVES, GR_PLACE_WAVES) void k_tile_place_views(VBatch<k_tile_place_args> B) {
-  const int vb = vbatch_view(B, (int)blockIdx.x);
-  const k_tile_place_args& a = B.a[vb];
-  const int lb = (int)blockIdx.x - B.first[vb], gx = B.gx[vb];
-  k_tile_place_body<WAVES>(a.Z, a.tiles, a.bits, a.ranges, a.pairs_out, a.pos_of, BI{lb % gx, lb / gx}, BI{gx, (B.first[vb + 1] - B.first[vb]) / gx});
+  const VBlock b = vbatch_block(B);
+  k_tile_place_run<WAVES>(B.a[b.view], b);
 }
 
 
@@ -2258,11 +2277,6 @@ __device__ __forceinline__ void k_depth_tile_max_body(ViewK v, const float4* __r
   __syncthreads();
   if (tid == 0) dscal[0] = fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3]));
 }
-__global__ __launch_bounds__(256) void k_depth_tile_max(ViewK v, const float4* __restrict__ saved4,
-                                                        const float* __restrict__ savedD, float* __restrict__ tile_aux,
-                                                        float* __restrict__ dscal, int* __restrict__ ticket) {
-  k_depth_tile_max_body(v, saved4, savedD, tile_aux, dscal, ticket, BI{(int)blockIdx.x, (int)blockIdx.y}, BI{(int)gridDim.x, (int)gridDim.y});
-}
 struct k_depth_tile_max_args {
   ViewK v;
   const float4* saved4;
@@ -2271,11 +2285,15 @@ struct k_depth_tile_max_args {
   float* dscal;
   int* ticket;
 };
+__device__ __forceinline__ void k_depth_tile_max_run(const k_depth_tile_max_args& a, const VBlock& b) {
+  k_depth_tile_max_body(a.v, a.saved4, a.savedD, a.tile_aux, a.dscal, a.ticket, b.block, b.grid);
+}
+__global__ __launch_bounds__(256) void k_depth_tile_max(k_depth_tile_max_args a) {
+  k_depth_tile_max_run(a, own_block());
+}
 __global__ __launch_bounds__(256) void k_depth_tile_max_views(VBatch<k_depth_tile_max_args> B) {
-  const int vb = vbatch_view(B, (int)blockIdx.x);
-  const k_depth_tile_max_args& a = B.a[vb];
-  const int lb = (int)blockIdx.x - B.first[vb], gx = B.gx[vb];
-  k_depth_tile_max_body(a.v, a.saved4, a.savedD, a.tile_aux, a.dscal, a.ticket, BI{lb % gx, lb / gx}, BI{gx, (B.first[vb + 1] - B.first[vb]) / gx});
+  const VBlock b = vbatch_block(B);
+  k_depth_tile_max_run(B.a[b.view], b);
 }
 
 
@@ -2324,13 +2342,6 @@ __device__ __forceinline__ void k_depth_tile_sums_body(ViewK v, const float4* __
   if (!arrive_last_tile(ticket, tiles, tile, &last)) return;
   depth_final(tile_loss, tile_aux, tiles, HW, w_depth, g_scale, dscal, r);
 }
-__global__ __launch_bounds__(256) void k_depth_tile_sums(ViewK v, const float4* __restrict__ saved4,
-                                                         const float* __restrict__ savedD, const float* __restrict__ t_depth,
-                                                         float* __restrict__ dscal, float* __restrict__ tile_loss,
-                                                         float* __restrict__ tile_aux, int64_t HW, float w_depth,
-                                                         float g_scale, int* __restrict__ ticket) {
-  k_depth_tile_sums_body(v, saved4, savedD, t_depth, dscal, tile_loss, tile_aux, HW, w_depth, g_scale, ticket, BI{(int)blockIdx.x, (int)blockIdx.y}, BI{(int)gridDim.x, (int)gridDim.y});
-}
 struct k_depth_tile_sums_args {
   ViewK v;
   const float4* saved4;
@@ -2344,11 +2355,15 @@ struct k_depth_tile_sums_args {
   float g_scale;
   int* ticket;
 };
+__device__ __forceinline__ void k_depth_tile_sums_run(const k_depth_tile_sums_args& a, const VBlock& b) {
+  k_depth_tile_sums_body(a.v, a.saved4, a.savedD, a.t_depth, a.dscal, a.tile_loss, a.tile_aux, a.HW, a.w_depth, a.g_scale, a.ticket, b.block, b.grid);
+}
+__global__ __launch_bounds__(256) void k_depth_tile_sums(k_depth_tile_sums_args a) {
+  k_depth_tile_sums_run(a, own_block());
+}
 __global__ __launch_bounds__(256) void k_depth_tile_sums_views(VBatch<k_depth_tile_sums_args> B) {
-  const int vb = vbatch_view(B, (int)blockIdx.x);
-  const k_depth_tile_sums_args& a = B.a[vb];
-  const int lb = (int)blockIdx.x - B.first[vb], gx = B.gx[vb];
-  k_depth_tile_sums_body(a.v, a.saved4, a.savedD, a.t_depth, a.dscal, a.tile_loss, a.tile_aux, a.HW, a.w_depth, a.g_scale, a.ticket, BI{lb % gx, lb / gx}, BI{gx, (B.first[vb + 1] - B.first[vb]) / gx});
+  const VBlock b = vbatch_block(B);
+  k_depth_tile_sums_run(B.a[b.view], b);
 }
 
 
@@ -2466,13 +2481,6 @@ __device__ __forceinline__ void k_pixel_grads_body(ViewK v, const float4* __rest
                             l1.loss_out, reinterpret_cast<double (*)[256]>(&sU[0][0]));
   }
 }
-__global__ __launch_bounds__(256) void k_pixel_grads(ViewK v, const float4* __restrict__ saved4,
-                                                     const float* __restrict__ savedD, const float* __restrict__ g_rgb,
-                                                     const float* __restrict__ g_alpha, const float* __restrict__ g_depth,
-                                                     uint4* __restrict__ UF, int pieces, L1Args l1, bool depth,
-                                                     int* __restrict__ ticket) {
-  k_pixel_grads_body(v, saved4, savedD, g_rgb, g_alpha, g_depth, UF, pieces, l1, depth, ticket, BI{(int)blockIdx.x, (int)blockIdx.y}, BI{(int)gridDim.x, (int)gridDim.y});
-}
 struct k_pixel_grads_args {
   ViewK v;
   const float4* saved4;
@@ -2486,11 +2494,15 @@ struct k_pixel_grads_args {
   bool depth;
   int* ticket;
 };
+__device__ __forceinline__ void k_pixel_grads_run(const k_pixel_grads_args& a, const VBlock& b) {
+  k_pixel_grads_body(a.v, a.saved4, a.savedD, a.g_rgb, a.g_alpha, a.g_depth, a.UF, a.pieces, a.l1, a.depth, a.ticket, b.block, b.grid);
+}
+__global__ __launch_bounds__(256) void k_pixel_grads(k_pixel_grads_args a) {
+  k_pixel_grads_run(a, own_block());
+}
 __global__ __launch_bounds__(256) void k_pixel_grads_views(VBatch<k_pixel_grads_args> B) {
-  const int vb = vbatch_view(B, (int)blockIdx.x);
-  const k_pixel_grads_args& a = B.a[vb];
-  const int lb = (int)blockIdx.x - B.first[vb], gx = B.gx[vb];
-  k_pixel_grads_body(a.v, a.saved4, a.savedD, a.g_rgb, a.g_alpha, a.g_depth, a.UF, a.pieces, a.l1, a.depth, a.ticket, BI{lb % gx, lb / gx}, BI{gx, (B.first[vb + 1] - B.first[vb]) / gx});
+  const VBlock b = vbatch_block(B);
+  k_pixel_grads_run(B.a[b.view], b);
 }
 
 
@@ -2614,18 +2626,6 @@ __device__ __forceinline__ void k_raster_fwd_mfma_body(ViewK v, int n, const int
                             reinterpret_cast<double (*)[256]>(smem));
   }
 }
-template <int MODE>
-__global__ __launch_bounds__(256, MODE >= 3 ? GR_FWD_WAVES3 : GR_FWD_WAVES) void k_raster_fwd_mfma(ViewK v, int n, const int4* __restrict__ items,
-                                                         const int* __restrict__ num_items, const int2* __restrict__ ranges,
-                                                         const int* __restrict__ pairs, const float4* __restrict__ rec,
-                                                         float* __restrict__ fwd_part, float* __restrict__ out_rgb,
-                                                         float* __restrict__ out_alpha, float* __restrict__ out_depth,
-                                                         float4* __restrict__ saved4, float* __restrict__ savedD,
-                                                         L1Args l1, uint4* __restrict__ UF, const int* __restrict__ f16_sa,
-                                                         const int* __restrict__ tile_item0, int* __restrict__ ticket,
-                                                         int ch) {
-  k_raster_fwd_mfma_body<MODE>(v, n, items, num_items, ranges, pairs, rec, fwd_part, out_rgb, out_alpha, out_depth, saved4, savedD, l1, UF, f16_sa, tile_item0, ticket, ch, BI{(int)blockIdx.x, (int)blockIdx.y}, BI{(int)gridDim.x, (int)gridDim.y});
-}
 struct k_raster_fwd_mfma_args {
   ViewK v;
   int n;
@@ -2648,11 +2648,17 @@ struct k_raster_fwd_mfma_args {
   int ch;
 };
 template <int MODE>
+__device__ __forceinline__ void k_raster_fwd_mfma_run(const k_raster_fwd_mfma_args& a, const VBlock& b) {
+  k_raster_fwd_mfma_body<MODE>(a.v, a.n, a.items, a.num_items, a.ranges, a.pairs, a.rec, a.fwd_part, a.out_rgb, a.out_alpha, a.out_depth, a.saved4, a.savedD, a.l1, a.UF, a.f16_sa, a.tile_item0, a.ticket, a.ch, b.block, b.grid);
+}
+template <int MODE>
+__global__ __launch_bounds__(256, MODE >= 3 ? GR_FWD_WAVES3 : GR_FWD_WAVES) void k_raster_fwd_mfma(k_raster_fwd_mfma_args a) {
+  k_raster_fwd_mfma_run<MODE>(a, own_block());
+}
+template <int MODE>
 __global__ __launch_bounds__(256, MODE >= 3 ? GR_FWD_WAVES3 : GR_FWD_WAVES) void k_raster_fwd_mfma_views(VBatch<k_raster_fwd_mfma_args> B) {
-  const int vb = vbatch_view(B, (int)blockIdx.x);
-  const k_raster_fwd_mfma_args& a = B.a[vb];
-  const int lb = (int)blockIdx.x - B.first[vb], gx = B.gx[vb];
-  k_raster_fwd_mfma_body<MODE>(a.v, a.n, a.items, a.num_items, a.ranges, a.pairs, a.rec, a.fwd_part, a.out_rgb, a.out_alpha, a.out_depth, a.saved4, a.savedD, a.l1, a.UF, a.f16_sa, a.tile_item0, a.ticket, a.ch, BI{lb % gx, lb / gx}, BI{gx, (B.first[vb + 1] - B.first[vb]) / gx});
+  const VBlock b = vbatch_block(B);
+  k_raster_fwd_mfma_run<MODE>(B.a[b.view], b);
 }
 
 
@@ -2987,13 +2993,6 @@ __device__ __forceinline__ void k_raster_bwd_bf16_body(ViewK v, int n, const int
   else
     bwd_item_bf16<false, true, PIECES>(n, k0, k1, tid, wave, tx, ty, pairs, rec, partials, sA, sB, &sZ[0][0], sUF, depth3);
 }
-template <bool DEPTH, int PIECES>
-__global__ __launch_bounds__(256, DEPTH ? GR_BF16_WAVES : GR_BF16_WAVES_ND) void k_raster_bwd_bf16(ViewK v, int n, const int4* __restrict__ items,
-                                                           const int* __restrict__ num_items, const int* __restrict__ pairs,
-                                                           const float4* __restrict__ rec, const uint4* __restrict__ UF,
-                                                           float* __restrict__ partials, float* __restrict__ depth3) {
-  k_raster_bwd_bf16_body<DEPTH, PIECES>(v, n, items, num_items, pairs, rec, UF, partials, depth3, BI{(int)blockIdx.x, (int)blockIdx.y}, BI{(int)gridDim.x, (int)gridDim.y});
-}
 struct k_raster_bwd_bf16_args {
   ViewK v;
   int n;
@@ -3006,11 +3005,17 @@ struct k_raster_bwd_bf16_args {
   float* depth3;
 };
 template <bool DEPTH, int PIECES>
+__device__ __forceinline__ void k_raster_bwd_bf16_run(const k_raster_bwd_bf16_args& a, const VBlock& b) {
+  k_raster_bwd_bf16_body<DEPTH, PIECES>(a.v, a.n, a.items, a.num_items, a.pairs, a.rec, a.UF, a.partials, a.depth3, b.block, b.grid);
+}
+template <bool DEPTH, int PIECES>
+__global__ __launch_bounds__(256, DEPTH ? GR_BF16_WAVES : GR_BF16_WAVES_ND) void k_raster_bwd_bf16(k_raster_bwd_bf16_args a) {
+  k_raster_bwd_bf16_run<DEPTH, PIECES>(a, own_block());
+}
+template <bool DEPTH, int PIECES>
 __global__ __launch_bounds__(256, DEPTH ? GR_BF16_WAVES : GR_BF16_WAVES_ND) void k_raster_bwd_bf16_views(VBatch<k_raster_bwd_bf16_args> B) {
-  const int vb = vbatch_view(B, (int)blockIdx.x);
-  const k_raster_bwd_bf16_args& a = B.a[vb];
-  const int lb = (int)blockIdx.x - B.first[vb], gx = B.gx[vb];
-  k_raster_bwd_bf16_body<DEPTH, PIECES>(a.v, a.n, a.items, a.num_items, a.pairs, a.rec, a.UF, a.partials, a.depth3, BI{lb % gx, lb / gx}, BI{gx, (B.first[vb + 1] - B.first[vb]) / gx});
+  const VBlock b = vbatch_block(B);
+  k_raster_bwd_bf16_run<DEPTH, PIECES>(B.a[b.view], b);
 }
 
 
@@ -3279,16 +3284,6 @@ __device__ __forceinline__ void k_fwd32_l1_body(ViewK v, int n, const int4* __re
     tile_loss_total<true>(l1.tile_loss, tiles, l1.n1, l1.n2, l1.w_sil, 0, 0.0f, l1.loss_out,
                           reinterpret_cast<double (*)[256]>(smem));
 }
-__global__ __launch_bounds__(256, GR_FWD32_WAVES) void k_fwd32_l1(ViewK v, int n, const int4* __restrict__ items,
-                                                                 const int* __restrict__ num_items,
-                                                                 const int2* __restrict__ ranges, const int* __restrict__ pairs,
-                                                                 const float4* __restrict__ rec, float* __restrict__ fwd_part,
-                                                                 float* __restrict__ out_rgb, float* __restrict__ out_alpha,
-                                                                 L1Args l1, uint4* __restrict__ UF, const int* __restrict__ f16_sa,
-                                                                 const int* __restrict__ tile_item0, int* __restrict__ ticket,
-                                                                 int ch) {
-  k_fwd32_l1_body(v, n, items, num_items, ranges, pairs, rec, fwd_part, out_rgb, out_alpha, l1, UF, f16_sa, tile_item0, ticket, ch, BI{(int)blockIdx.x, (int)blockIdx.y}, BI{(int)gridDim.x, (int)gridDim.y});
-}
 struct k_fwd32_l1_args {
   ViewK v;
   int n;
@@ -3307,6 +3302,22 @@ struct k_fwd32_l1_args {
   int* ticket;
   int ch;
 };
+// k_fwd32_l1 and k_bwd32 keep their positional one-view form and their own batched call.  With struct arguments (the
+// k_x_run arrangement of the other kernels) their schedules shift by a few instructions and the C4-size fit step stops
+// being deterministic from run to run: equal losses, different means (test_fit_step_is_deterministic_at_c4_size; the
+// symptom profiles/r06_determinism.txt traced to the f16 split's inline-asm v_fma_mix, which the hazard recognizer does
+// not see).  The cause of this instance was not found (profiles/launch_args_refactor.txt), so the two kernels'
+// code is left exactly as it was; the host still fills their k_x_args with the shared builders.
+__global__ __launch_bounds__(256, GR_FWD32_WAVES) void k_fwd32_l1(ViewK v, int n, const int4* __restrict__ items,
+                                                                 const int* __restrict__ num_items,
+                                                                 const int2* __restrict__ ranges, const int* __restrict__ pairs,
+                                                                 const float4* __restrict__ rec, float* __restrict__ fwd_part,
+                                                                 float* __restrict__ out_rgb, float* __restrict__ out_alpha,
+                                                                 L1Args l1, uint4* __restrict__ UF, const int* __restrict__ f16_sa,
+                                                                 const int* __restrict__ tile_item0, int* __restrict__ ticket,
+                                                                 int ch) {
+  k_fwd32_l1_body(v, n, items, num_items, ranges, pairs, rec, fwd_part, out_rgb, out_alpha, l1, UF, f16_sa, tile_item0, ticket, ch, BI{(int)blockIdx.x, (int)blockIdx.y}, BI{(int)gridDim.x, (int)gridDim.y});
+}
 __global__ __launch_bounds__(256, GR_FWD32_WAVES) void k_fwd32_l1_views(VBatch<k_fwd32_l1_args> B) {
   const int vb = vbatch_view(B, (int)blockIdx.x);
   const k_fwd32_l1_args& a = B.a[vb];
@@ -3514,12 +3525,6 @@ __device__ __forceinline__ void k_bwd32_body(ViewK v, int n, const int4* __restr
     }
   }
 }
-__global__ __launch_bounds__(256, GR_BWD32_WAVES) void k_bwd32(ViewK v, int n, const int4* __restrict__ items,
-                                                              const int* __restrict__ num_items, const int* __restrict__ pairs,
-                                                              const float4* __restrict__ rec, const uint4* __restrict__ UF,
-                                                              float* __restrict__ partials) {
-  k_bwd32_body(v, n, items, num_items, pairs, rec, UF, partials, BI{(int)blockIdx.x, (int)blockIdx.y}, BI{(int)gridDim.x, (int)gridDim.y});
-}
 struct k_bwd32_args {
   ViewK v;
   int n;
@@ -3530,6 +3535,13 @@ struct k_bwd32_args {
   const uint4* UF;
   float* partials;
 };
+// (positional one-view form kept: see k_fwd32_l1)
+__global__ __launch_bounds__(256, GR_BWD32_WAVES) void k_bwd32(ViewK v, int n, const int4* __restrict__ items,
+                                                              const int* __restrict__ num_items, const int* __restrict__ pairs,
+                                                              const float4* __restrict__ rec, const uint4* __restrict__ UF,
+                                                              float* __restrict__ partials) {
+  k_bwd32_body(v, n, items, num_items, pairs, rec, UF, partials, BI{(int)blockIdx.x, (int)blockIdx.y}, BI{(int)gridDim.x, (int)gridDim.y});
+}
 __global__ __launch_bounds__(256, GR_BWD32_WAVES) void k_bwd32_views(VBatch<k_bwd32_args> B) {
   const int vb = vbatch_view(B, (int)blockIdx.x);
   const k_bwd32_args& a = B.a[vb];
@@ -3926,12 +3938,6 @@ __device__ __forceinline__ void k_gather_view_body(int n, const Cnt2* __restrict
     sums[4 * (size_t)i + q4] = o;
   }
 }
-template <bool DEPTH>
-__global__ __launch_bounds__(256) void k_gather_view(int n, const Cnt2* __restrict__ offsets, const int* __restrict__ pos_of,
-                                                     const float4* __restrict__ rows, float2* __restrict__ sums,
-                                                     const float* __restrict__ depth3, float* __restrict__ sums3) {
-  k_gather_view_body<DEPTH>(n, offsets, pos_of, rows, sums, depth3, sums3, BI{(int)blockIdx.x, (int)blockIdx.y}, BI{(int)gridDim.x, (int)gridDim.y});
-}
 struct k_gather_view_args {
   int n;
   const Cnt2* offsets;
@@ -3942,11 +3948,17 @@ struct k_gather_view_args {
   float* sums3;
 };
 template <bool DEPTH>
+__device__ __forceinline__ void k_gather_view_run(const k_gather_view_args& a, const VBlock& b) {
+  k_gather_view_body<DEPTH>(a.n, a.offsets, a.pos_of, a.rows, a.sums, a.depth3, a.sums3, b.block, b.grid);
+}
+template <bool DEPTH>
+__global__ __launch_bounds__(256) void k_gather_view(k_gather_view_args a) {
+  k_gather_view_run<DEPTH>(a, own_block());
+}
+template <bool DEPTH>
 __global__ __launch_bounds__(256) void k_gather_view_views(VBatch<k_gather_view_args> B) {
-  const int vb = vbatch_view(B, (int)blockIdx.x);
-  const k_gather_view_args& a = B.a[vb];
-  const int lb = (int)blockIdx.x - B.first[vb], gx = B.gx[vb];
-  k_gather_view_body<DEPTH>(a.n, a.offsets, a.pos_of, a.rows, a.sums, a.depth3, a.sums3, BI{lb % gx, lb / gx}, BI{gx, (B.first[vb + 1] - B.first[vb]) / gx});
+  const VBlock b = vbatch_block(B);
+  k_gather_view_run<DEPTH>(B.a[b.view], b);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -5373,6 +5385,23 @@ gr_status check_view(const gr_view* v) {
   return GR_OK;
 }
 
+// The colour layouts: (N,3) RGB or SH coefficients (N,4,3) / (N,16,3).  with_color_dim calls f with a checked
+// color_dim as a compile-time constant (the CD of the kernels templated on it).
+gr_status check_color_dim(int color_dim) {
+  if (color_dim != 3 && color_dim != 12 && color_dim != 48)
+    return set_error(GR_ERR_INVALID_ARGUMENT, "colors must be (N,3) or SH coeffs (N,4,3) / (N,16,3)");
+  return GR_OK;
+}
+template <class F>
+void with_color_dim(int color_dim, F f) {
+  if (color_dim == 3)
+    f(std::integral_constant<int, 3>{});
+  else if (color_dim == 12)
+    f(std::integral_constant<int, 12>{});
+  else
+    f(std::integral_constant<int, 48>{});
+}
+
 }  // namespace
 
 // ================================================================================================
@@ -5601,8 +5630,7 @@ gr_status gr_fwd_prepare_async(const gr_view* v, int n, const float* means, cons
   if (st != GR_OK) return st;
   if (v->device_counts) return set_error(GR_ERR_INVALID_ARGUMENT, "device_counts views are prepared by gr_fwd_prepare_views_sized");
   if (n < 0) return set_error(GR_ERR_INVALID_ARGUMENT, "n must be >= 0");
-  if (color_dim != 3 && color_dim != 12 && color_dim != 48)
-    return set_error(GR_ERR_INVALID_ARGUMENT, "colors must be (N,3) or SH coeffs (N,4,3) / (N,16,3)");
+  if ((st = check_color_dim(color_dim)) != GR_OK) return st;
   if (!plan) return set_error(GR_ERR_INVALID_ARGUMENT, "plan is null");
   if (n == 0) {
     plan->num_pairs = 0;
@@ -5615,12 +5643,9 @@ gr_status gr_fwd_prepare_async(const gr_view* v, int n, const float* means, cons
   hipStream_t s = (hipStream_t)stream;
   const ViewK vk = make_viewk(v);
   Geom g = geom_view(geom, n);
-  if (color_dim == 3)
-    hipLaunchKernelGGL(k_preprocess<3>, dim3(blocks_for(n + 1)), dim3(256), 0, s, vk, n, means, scales, colors, opacities, g);
-  else if (color_dim == 12)
-    hipLaunchKernelGGL(k_preprocess<12>, dim3(blocks_for(n + 1)), dim3(256), 0, s, vk, n, means, scales, colors, opacities, g);
-  else
-    hipLaunchKernelGGL(k_preprocess<48>, dim3(blocks_for(n + 1)), dim3(256), 0, s, vk, n, means, scales, colors, opacities, g);
+  with_color_dim(color_dim, [&](auto cd) {
+    hipLaunchKernelGGL(k_preprocess<cd()>, dim3(blocks_for(n + 1)), dim3(256), 0, s, vk, n, means, scales, colors, opacities, g);
+  });
   GR_HIP_TRY(hipGetLastError());
   // a plan in pinned (device-mapped) host memory is written by k_plan itself; pageable memory gets a copy
   gr_plan* mapped = nullptr;
@@ -5665,8 +5690,7 @@ static gr_status prepare_views_impl(int num_views, const gr_view* views, int n, 
   }
   if (caps && !ovf) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_fwd_prepare_views_sized: overflow is null");
   if (n < 0) return set_error(GR_ERR_INVALID_ARGUMENT, "n must be >= 0");
-  if (color_dim != 3 && color_dim != 12 && color_dim != 48)
-    return set_error(GR_ERR_INVALID_ARGUMENT, "colors must be (N,3) or SH coeffs (N,4,3) / (N,16,3)");
+  if (gr_status st = check_color_dim(color_dim); st != GR_OK) return st;
   if (n == 0) {
     if (plans)
       for (int k = 0; k < num_views; ++k)
@@ -5698,12 +5722,9 @@ static gr_status prepare_views_impl(int num_views, const gr_view* views, int n, 
   // rows of views: at least ~1024 blocks (4 per CU) when the views allow, each view still run by one row alone
   const dim3 pgrid(blocks, std::max(1, std::min(num_views, (1024 + blocks - 1) / blocks)));
   for (int rep = 0; rep < GR_DEBUG_PREP_REPS; ++rep) {  // > 1: timing experiments only (idempotent repeats)
-  if (color_dim == 3)
-    hipLaunchKernelGGL(k_preprocess_views<3>, pgrid, dim3(256), 0, s, B, n, means, scales, colors, opacities);
-  else if (color_dim == 12)
-    hipLaunchKernelGGL(k_preprocess_views<12>, pgrid, dim3(256), 0, s, B, n, means, scales, colors, opacities);
-  else
-    hipLaunchKernelGGL(k_preprocess_views<48>, pgrid, dim3(256), 0, s, B, n, means, scales, colors, opacities);
+  with_color_dim(color_dim, [&](auto cd) {
+    hipLaunchKernelGGL(k_preprocess_views<cd()>, pgrid, dim3(256), 0, s, B, n, means, scales, colors, opacities);
+  });
   GR_HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(k_plan_views, dim3(num_views), dim3(PLAN_THREADS), 0, s, B, n, hp);
   GR_HIP_TRY(hipGetLastError());
@@ -5773,69 +5794,209 @@ static BwdWs bwd_ws(const gr_view* v, int n, const gr_plan* plan, void* ws) {
   return w;
 }
 
+// ---- One view, resolved: its kernel block, tile geometry and workspaces, built once per entry point (once per view
+// of gr_fit_views_batched) after the entry point's own argument checks.  A workspace the caller does not have (null)
+// leaves its member zeroed; only the members of the workspaces passed may be read.
+struct ViewCtx {
+  const gr_view* view;
+  const gr_plan* plan;
+  int n;
+  ViewK vk;
+  TileCfg tc;
+  int tiles;    // screen tiles (the binning's virtual tiles: 2 x tiles)
+  int64_t cap;  // capacity of the work-item list = the splats' grid
+  size_t HW;
+  Geom g;
+  Bins b;
+  Scratch sc;
+  BwdWs w;
+  int64_t K() const { return plan->num_pairs; }
+  float* depth3() const { return w.partials + 8 * (size_t)plan->num_slots; }  // the ninth partial of each row
+};
+static ViewCtx view_ctx(const gr_view* v, int n, const gr_plan* plan, const void* geom, const void* bins, void* scratch,
+                        const void* ws) {
+  ViewCtx c{};
+  c.view = v;
+  c.plan = plan;
+  c.n = n;
+  c.vk = make_viewk(v);
+  c.tc = tile_cfg(v, plan->num_pairs);
+  c.tiles = c.vk.tiles_x * c.vk.tiles_y;
+  c.cap = item_cap(2 * c.tiles, plan->num_pairs, c.tc.ch);
+  c.HW = (size_t)v->width * v->height;
+  if (geom) c.g = geom_view((void*)geom, n);
+  if (bins) c.b = bins_view((void*)bins, 2 * c.tiles, plan->num_pairs, c.tc.ch);
+  if (scratch) c.sc = scratch_view(scratch, 2 * c.tiles, plan->num_pairs, c.tc.ch, c.tc.part_floats);
+  if (ws) c.w = bwd_ws(v, n, plan, (void*)ws);
+  return c;
+}
+
+// The counting sort's two regions (core pairs [0, Kc), tail pairs [Kc, K)), their columns, and M / S / T carved out of
+// the scratch's sort_tmp (tile_sort_tmp_bytes).  Device-side sizing (gr_view.device_counts): K and the columns are the
+// regions' capacities (the grid); the true counts are read on the device (kdev).
+static TZones tile_zones(const ViewCtx& c) {
+  const int64_t Kc = c.plan->num_core_pairs, Kr[2] = {Kc, c.K() - Kc};
+  TZones Z;
+  Z.cw = col_width(c.K(), c.tiles);
+  Z.ch = c.tc.ch;
+  Z.kdev = c.view->device_counts ? (const unsigned long long*)(c.g.offsets + c.n) : nullptr;
+  const size_t cells = (size_t)c.tiles * cols_of(c.K(), Z.cw);
+  char* q = (char*)c.sc.sort_tmp;
+  for (int z = 0; z < 2; ++z) {
+    TZone& zz = Z.z[z];
+    zz.K = Kr[z];
+    zz.cols = cols_of(Kr[z], Z.cw);
+    zz.zbase = z == 0 ? 0 : (int)Kc;
+    zz.keys = (const uint16_t*)c.sc.keys_in + (z == 0 ? 0 : Kc);
+    zz.ids = c.sc.ids_in + (z == 0 ? 0 : Kc);
+    zz.M = (int*)q;
+    q += align_up(cells * sizeof(int));
+    zz.S = (int*)q;
+    q += align_up(cells * sizeof(int));
+    zz.T = (int*)q;
+    q += align_up((size_t)c.tiles * sizeof(int));
+  }
+  return Z;
+}
+
+// The fit loss of a view (mean |out - t| + w_sil mean |alpha - m|, with t_depth the depth term): its targets and
+// weights, the per-tile sums in the backward workspace and the element counts of the means.
+static L1Args fit_l1_args(const ViewCtx& c, const float* t_rgb, const float* t_mask, float w_sil, float g_scale,
+                          float* loss_out, const float* t_depth = nullptr, float w_depth = 0.0f) {
+  L1Args l1{t_rgb, t_mask, w_sil, g_scale, c.w.tile_loss};
+  l1.loss_out = loss_out;
+  l1.n1 = (int64_t)(3 * c.HW);
+  l1.n2 = (int64_t)(t_mask ? c.HW : 0);
+  if (t_depth) {
+    l1.t_depth = t_depth;
+    l1.w_depth = w_depth;
+    l1.dscal = c.w.dscal;
+  }
+  return l1;
+}
+
+// ---- One builder per kernel with a batched form: its k_x_args from the resolved view, for the one-view launch
+// (launch_one) and for gr_fit_views_batched (vb_add) alike.
+static k_emit_offsets_args emit_offsets_args(const ViewCtx& c) {
+  return {c.vk, c.n, (const int4*)c.g.rect, (const Cnt2*)c.g.counts, (const unsigned long long*)c.g.total,
+          (Cnt2*)c.g.offsets, (const float4*)c.g.rec, (uint16_t*)c.sc.keys_in, c.sc.ids_in,
+          c.b.ticket + fan_offset(c.tiles)};
+}
+static k_tile_count_args tile_count_args(const ViewCtx& c, const TZones& Z) { return {Z, c.tiles}; }
+static k_tile_colscan_args tile_colscan_args(const ViewCtx& c, const TZones& Z) {
+  return {Z, c.tiles, c.b.ranges, c.b.items, c.b.num_items, c.b.tile_item0, c.b.ticket};
+}
+static k_tile_place_args tile_place_args(const ViewCtx& c, const TZones& Z) {
+  return {Z, c.tiles, bits_for((uint32_t)c.tiles), (const int2*)c.b.ranges, c.b.pairs, c.b.pos_of};
+}
+// `saved`: the pixel sums ([HW] float4, then [HW] depth sums) or null; the outputs and UF may be null (L1Args::t_rgb
+// null: no fit loss)
+static k_raster_fwd_mfma_args fwd_mfma_args(const ViewCtx& c, float* out_rgb, float* out_alpha, float* out_depth,
+                                            float* saved, const L1Args& l1, uint4* UF) {
+  return {c.vk, c.n, (const int4*)c.b.items, (const int*)c.b.num_items, (const int2*)c.b.ranges, (const int*)c.b.pairs,
+          (const float4*)c.g.rec, c.sc.fwd_part, out_rgb, out_alpha, out_depth, (float4*)saved,
+          saved ? saved + 4 * c.HW : nullptr, l1, UF, (const int*)(c.n > 0 && c.K() > 0 ? c.g.f16_sa : nullptr),
+          (const int*)c.b.tile_item0, c.b.ticket, c.tc.ch};
+}
+static k_fwd32_l1_args fwd32_args(const ViewCtx& c, float* out_rgb, float* out_alpha, const L1Args& l1, uint4* UF) {
+  return {c.vk, c.n, (const int4*)c.b.items, (const int*)c.b.num_items, (const int2*)c.b.ranges, (const int*)c.b.pairs,
+          (const float4*)c.g.rec, c.sc.fwd_part, out_rgb, out_alpha, l1, UF,
+          (const int*)(c.n > 0 && c.K() > 0 ? c.g.f16_sa : nullptr), (const int*)c.b.tile_item0, c.b.ticket, c.tc.ch};
+}
+static k_raster_bwd_bf16_args bwd_bf16_args(const ViewCtx& c, float* depth3) {
+  return {c.vk, c.n, (const int4*)c.b.items, (const int*)c.b.num_items, (const int*)c.b.pairs, (const float4*)c.g.rec,
+          (const uint4*)c.w.UF, c.w.partials, depth3};
+}
+static k_bwd32_args bwd32_args(const ViewCtx& c) {
+  return {c.vk, c.n, (const int4*)c.b.items, (const int*)c.b.num_items, (const int*)c.b.pairs, (const float4*)c.g.rec,
+          (const uint4*)c.w.UF, c.w.partials};
+}
+static k_depth_tile_max_args depth_tile_max_args(const ViewCtx& c, const float* saved) {
+  return {c.vk, (const float4*)saved, saved + 4 * c.HW, c.w.tile_aux, c.w.dscal, c.b.ticket};
+}
+static k_depth_tile_sums_args depth_tile_sums_args(const ViewCtx& c, const float* saved, const float* t_depth,
+                                                   float w_depth, float g_scale) {
+  return {c.vk, (const float4*)saved, saved + 4 * c.HW, t_depth, c.w.dscal, c.w.tile_loss, c.w.tile_aux, (int64_t)c.HW,
+          w_depth, g_scale, c.b.ticket};
+}
+static k_pixel_grads_args pixel_grads_args(const ViewCtx& c, const float* saved, const float* g_rgb, const float* g_alpha,
+                                           const float* g_depth, int pieces, const L1Args& l1, bool depth) {
+  return {c.vk, (const float4*)saved, saved + 4 * c.HW, g_rgb, g_alpha, g_depth, c.w.UF, pieces, l1, depth, c.b.ticket};
+}
+// depth: the tail pairs and the depth sums too (k_gather_view<true>), into sums3
+static k_gather_view_args gather_args(const ViewCtx& c, float* sums, float* sums3, bool depth) {
+  return {c.n, (const Cnt2*)c.g.offsets, (const int*)c.b.pos_of, (const float4*)c.w.partials, (float2*)sums,
+          depth ? (const float*)c.depth3() : nullptr, depth ? sums3 : nullptr};
+}
+// k_tile_place's instance for a view's tile count (tsort_waves), in both forms, with its block size and LDS bytes.
+struct TilePlace {
+  void (*one)(k_tile_place_args);
+  void (*views)(VBatch<k_tile_place_args>);
+  int threads;
+  size_t lds;
+};
+static TilePlace tile_place_of(int tiles) {
+  const int waves = tsort_waves(tiles);
+  const size_t lds = (size_t)tiles * sizeof(int) * waves;
+  if (waves == 8) return {k_tile_place<8>, k_tile_place_views<8>, 512, lds};
+  if (waves == 4) return {k_tile_place<4>, k_tile_place_views<4>, 256, lds};
+  if (waves == 2) return {k_tile_place<2>, k_tile_place_views<2>, 128, lds};
+  return {k_tile_place<1>, k_tile_place_views<1>, 64, lds};
+}
+
+// The two launches: one view's own grid with its arguments, or the views collected in a VBatch (vb_add: `blocks` of
+// each view, as a grid of gx x (blocks / gx)).
+template <class A>
+static void launch_one(void (*kern)(A), dim3 grid, int threads, size_t lds, hipStream_t s, const A& a) {
+  hipLaunchKernelGGL(kern, grid, dim3(threads), lds, s, a);
+}
+template <class A>
+static void vb_add(VBatch<A>& B, const A& a, int blocks, int gx = 0) {
+  B.a[B.nv] = a;
+  B.gx[B.nv] = gx > 0 ? gx : (blocks > 0 ? blocks : 1);
+  B.first[B.nv + 1] = B.first[B.nv] + (blocks > 0 ? blocks : 0);
+  ++B.nv;
+}
+template <class A>
+static VBatch<A> vb_new() {
+  static_assert(sizeof(VBatch<A>) <= 4096, "batched kernel arguments exceed 4 KiB");
+  VBatch<A> B;
+  B.nv = 0;
+  B.first[0] = 0;
+  return B;
+}
+#define GR_VB_LAUNCH(kern, B, threads, lds, s)                                                   \
+  do {                                                                                           \
+    if ((B).first[(B).nv] > 0) {                                                                 \
+      hipLaunchKernelGGL(kern, dim3((unsigned)(B).first[(B).nv]), dim3(threads), lds, s, (B));   \
+      GR_HIP_TRY(hipGetLastError());                                                             \
+    }                                                                                            \
+  } while (0)
+
 // The view's binning (pair emission, the stable counting sort by tile, work items): gr_fwd_bin, or the
 // first half of fwd_impl when the view is not already binned.
-static gr_status bin_impl(const gr_view* v, int n, const gr_plan* plan, const void* geom, const Bins& b,
-                          const Scratch& sc, const ViewK& vk, hipStream_t s) {
-  const int64_t num_pairs = plan->num_pairs;
-  const int tiles = vk.tiles_x * vk.tiles_y, vtiles = 2 * tiles;
+static gr_status bin_impl(const ViewCtx& c, hipStream_t s) {
+  const gr_view* v = c.view;
+  const int n = c.n, tiles = c.tiles, vtiles = 2 * tiles;
+  const int64_t num_pairs = c.K();
+  const Bins& b = c.b;
+  const Scratch& sc = c.sc;
   prof_mark(PROF_BINNING, s);
   if (n > 0 && num_pairs > 0) {
-    Geom g = geom_view((void*)geom, n);
-    const Cnt2* cnt = (const Cnt2*)g.counts;
-    const Cnt2* offs = (const Cnt2*)g.offsets;
+    const Geom& g = c.g;
     if (short_keys(vtiles)) {
       // counting sort of each region (core pairs [0, Kc), tail pairs [Kc, K)) on 16-bit tile keys, columns of G
       // Gaussians: emission + per-column counts + offsets, the column scan, the placement + work items
-      const int64_t Kc = plan->num_core_pairs, Kr[2] = {Kc, num_pairs - Kc};
-      const int cw = col_width(num_pairs, tiles);
-      const size_t cells = (size_t)tiles * cols_of(num_pairs, cw);
-      const int waves = tsort_waves(tiles);
-      TZones Z;
-      Z.cw = cw;
-      Z.ch = tile_cfg(v, num_pairs).ch;
-      // device-side sizing: Kr are the regions' capacities (columns = grid); the true counts are read on the device
-      Z.kdev = v->device_counts ? (const unsigned long long*)(g.offsets + n) : nullptr;
-      char* q = (char*)sc.sort_tmp;
-      for (int z = 0; z < 2; ++z) {
-        TZone& zz = Z.z[z];
-        zz.K = Kr[z];
-        zz.cols = cols_of(Kr[z], cw);
-        zz.zbase = z == 0 ? 0 : (int)Kc;
-        zz.keys = (const uint16_t*)sc.keys_in + (z == 0 ? 0 : Kc);
-        zz.ids = sc.ids_in + (z == 0 ? 0 : Kc);
-        zz.M = (int*)q;
-        q += align_up(cells * sizeof(int));
-        zz.S = (int*)q;
-        q += align_up(cells * sizeof(int));
-        zz.T = (int*)q;
-        q += align_up((size_t)tiles * sizeof(int));
-      }
-      int* fan = b.ticket + fan_offset(tiles);
-      hipLaunchKernelGGL(k_emit_offsets, dim3(blocks_for(n)), dim3(256), 0, s, vk, n, (const int4*)g.rect, cnt,
-                         (const unsigned long long*)g.total, (Cnt2*)g.offsets, (const float4*)g.rec,
-                         (uint16_t*)sc.keys_in, sc.ids_in, fan);
+      const TZones Z = tile_zones(c);
+      launch_one(k_emit_offsets, dim3(blocks_for(n)), 256, 0, s, emit_offsets_args(c));
       GR_HIP_TRY(hipGetLastError());
       const int blocks = Z.z[0].cols + Z.z[1].cols;
-      hipLaunchKernelGGL(k_tile_count, dim3(blocks), dim3(256), (size_t)tiles * sizeof(int), s, Z, tiles);
+      launch_one(k_tile_count, dim3(blocks), 256, (size_t)tiles * sizeof(int), s, tile_count_args(c, Z));
       GR_HIP_TRY(hipGetLastError());
-      hipLaunchKernelGGL(k_tile_colscan, dim3((tiles + CS_T - 1) / CS_T, 2), dim3(CS_T * CS_G), 0, s, Z, tiles, b.ranges,
-                         b.items, b.num_items, b.tile_item0, b.ticket);
+      launch_one(k_tile_colscan, dim3((tiles + CS_T - 1) / CS_T, 2), CS_T * CS_G, 0, s, tile_colscan_args(c, Z));
       GR_HIP_TRY(hipGetLastError());
-      const size_t lds = (size_t)tiles * sizeof(int) * waves;
-      const int bits = bits_for((uint32_t)tiles);
-      if (waves == 8)
-        hipLaunchKernelGGL(k_tile_place<8>, dim3(blocks), dim3(512), lds, s, Z, tiles, bits, (const int2*)b.ranges, b.pairs,
-                           b.pos_of);
-      else if (waves == 4)
-        hipLaunchKernelGGL(k_tile_place<4>, dim3(blocks), dim3(256), lds, s, Z, tiles, bits, (const int2*)b.ranges, b.pairs,
-                           b.pos_of);
-      else if (waves == 2)
-        hipLaunchKernelGGL(k_tile_place<2>, dim3(blocks), dim3(128), lds, s, Z, tiles, bits, (const int2*)b.ranges, b.pairs,
-                           b.pos_of);
-      else
-        hipLaunchKernelGGL(k_tile_place<1>, dim3(blocks), dim3(64), lds, s, Z, tiles, bits, (const int2*)b.ranges, b.pairs,
-                           b.pos_of);
+      const TilePlace place = tile_place_of(tiles);
+      launch_one(place.one, dim3(blocks), place.threads, place.lds, s, tile_place_args(c, Z));
       GR_HIP_TRY(hipGetLastError());
     } else {
       if (v->device_counts)
@@ -5845,8 +6006,8 @@ static gr_status bin_impl(const gr_view* v, int n, const gr_plan* plan, const vo
       hipLaunchKernelGGL(k_offsets, dim3(blocks_for(n)), dim3(256), 0, s, n, (const unsigned long long*)g.counts,
                          (const unsigned long long*)g.total, g.offsets);
       GR_HIP_TRY(hipGetLastError());
-      hipLaunchKernelGGL((k_emit_zones<uint32_t, true>), dim3(blocks_for(n)), dim3(256), 0, s, vk, n,
-                         (const int4*)g.rect, cnt, offs, (const float4*)g.rec, sc.keys_in, sc.ids_in);
+      hipLaunchKernelGGL((k_emit_zones<uint32_t, true>), dim3(blocks_for(n)), dim3(256), 0, s, c.vk, n,
+                         (const int4*)g.rect, (const Cnt2*)g.counts, (const Cnt2*)g.offsets, (const float4*)g.rec, sc.keys_in, sc.ids_in);
       GR_HIP_TRY(hipGetLastError());
       hipLaunchKernelGGL(k_pair_values, dim3(blocks_for(num_pairs)), dim3(256), 0, s, num_pairs, (const int*)sc.ids_in,
                          sc.pairs_in);
@@ -5862,14 +6023,14 @@ static gr_status bin_impl(const gr_view* v, int n, const gr_plan* plan, const vo
                          b.pairs, b.pos_of);
       GR_HIP_TRY(hipGetLastError());
       hipLaunchKernelGGL(k_work_items, dim3(1), dim3(WI_THREADS), 0, s, vtiles, (const int2*)b.ranges, b.items, b.num_items,
-                         b.tile_item0, b.ticket, tile_cfg(v, num_pairs).ch);
+                         b.tile_item0, b.ticket, c.tc.ch);
     }
   } else {
     // no pair: the Gaussians' offsets (written by the emission otherwise) are all zero
-    if (n > 0) GR_HIP_TRY(hipMemsetAsync(geom_view((void*)geom, n).offsets, 0, (size_t)n * sizeof(unsigned long long), s));
+    if (n > 0) GR_HIP_TRY(hipMemsetAsync(c.g.offsets, 0, (size_t)n * sizeof(unsigned long long), s));
     GR_HIP_TRY(hipMemsetAsync(b.ranges, 0, sizeof(int2) * vtiles, s));
     hipLaunchKernelGGL(k_work_items, dim3(1), dim3(WI_THREADS), 0, s, vtiles, (const int2*)b.ranges, b.items, b.num_items,
-                       b.tile_item0, b.ticket, tile_cfg(v, num_pairs).ch);
+                       b.tile_item0, b.ticket, c.tc.ch);
   }
   GR_HIP_TRY(hipGetLastError());
   prof_mark(PROF_BINNING, s);
@@ -5890,44 +6051,29 @@ static gr_status fwd_impl(const gr_view* v, int n, const gr_plan* plan, const vo
   if (l1 && (!ws || ws_bytes < gr_bwd_bytes(v, n, plan) || !l1_loss_out))
     return set_error(GR_ERR_WORKSPACE, "gr_fwd_render_l1: backward workspace too small (or null loss)");
   if (n > 0 && (!geom || !bins)) return set_error(GR_ERR_INVALID_ARGUMENT, "null workspace");
-  const int64_t num_pairs = plan->num_pairs;
   if (bins_bytes < gr_bins_bytes(v, n, plan)) return set_error(GR_ERR_WORKSPACE, "bins workspace too small");
   if (scratch_bytes < gr_fwd_scratch_bytes(v, n, plan) || !scratch)
     return set_error(GR_ERR_WORKSPACE, "forward scratch workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  const ViewK vk = make_viewk(v);
-  const int tiles = vk.tiles_x * vk.tiles_y, vtiles = 2 * tiles;
-  const TileCfg tc = tile_cfg(v, num_pairs);
+  const ViewCtx c = view_ctx(v, n, plan, geom, bins, scratch, l1 ? ws : nullptr);
   if (v->rows > 0 && !l1)
     return set_error(GR_ERR_INVALID_ARGUMENT, "a band of tile rows (gr_view.rows): gr_fwd_render_l1 only (the fit loss)");
-  if (tc.T == T32 && (!l1 || v->no_depth_grad != 1))
+  if (c.tc.T == T32 && (!l1 || v->no_depth_grad != 1))
     return set_error(GR_ERR_INVALID_ARGUMENT, "32-pixel tiles (gr_view.tile = 32): gr_fwd_render_l1 with no_depth_grad = 1 only");
-  if (tc.T == T32 && vk.core != vk.cutoff)
+  if (c.tc.T == T32 && c.vk.core != c.vk.cutoff)
     return set_error(GR_ERR_INVALID_ARGUMENT, "32-pixel tiles (gr_view.tile = 32): one-zone footprint only (core_cutoff <= 0 or >= cutoff)");
-  Bins b = bins_view(bins, vtiles, num_pairs, tc.ch);
-  Scratch sc = scratch_view(scratch, vtiles, num_pairs, tc.ch, tc.part_floats);
   if (!v->binned) {
     for (int rep = 0; rep < GR_DEBUG_BIN_REPS; ++rep) {  // > 1: timing experiments only (idempotent repeats)
-      st = bin_impl(v, n, plan, geom, b, sc, vk, s);
+      st = bin_impl(c, s);
       if (st != GR_OK) return st;
     }
   }
-  Geom g = geom_view((void*)geom, n > 0 ? n : 1);
-  const size_t HW = (size_t)v->width * v->height;
-  const int64_t cap = item_cap(vtiles, num_pairs, tc.ch);
   L1Args la{nullptr, nullptr, 0.f, 0.f, nullptr};
-  uint4* UF = nullptr;
   if (l1) {
-    const BwdWs w = bwd_ws(v, n, plan, ws);
-    la = *l1;
-    la.tile_loss = w.tile_loss;
-    la.loss_out = l1_loss_out;
-    la.n1 = (int64_t)(3 * HW);
-    la.n2 = (int64_t)(l1->t_mask ? HW : 0);
-    UF = w.UF;
+    la = fit_l1_args(c, l1->t_rgb, l1->t_mask, l1->w_sil, l1->g_scale, l1_loss_out);
+    la.pieces = l1->pieces;
   }
-  float4* saved4 = saved ? (float4*)saved : nullptr;
-  float* savedD = saved ? saved + 4 * HW : nullptr;
+  uint4* UF = l1 ? c.w.UF : nullptr;
   if (!(GR_DEBUG_SKIP & 1)) {
     // every tile has a work item (an empty tile its one empty item): the splat writes every output pixel, finishes
     // the tiles split over several items (the last item to arrive) and, with the fit loss, the view loss (the last
@@ -5935,20 +6081,16 @@ static gr_status fwd_impl(const gr_view* v, int n, const gr_plan* plan, const vo
     prof_mark(PROF_RASTER_FWD, s);
     // no_depth_grad: 0 default (f32-grade W / D), 1 two-piece splits, 2 f32-grade without a depth gradient
     const bool f32g = v->no_depth_grad != 1;
-    if (tc.T == T32)
-      hipLaunchKernelGGL(k_fwd32_l1, dim3((unsigned)cap), dim3(256), 0, s, vk, n, (const int4*)b.items, (const int*)b.num_items,
-                         (const int2*)b.ranges, (const int*)b.pairs, (const float4*)g.rec, sc.fwd_part, out_rgb, out_alpha, la,
-                         UF, (const int*)(n > 0 && num_pairs > 0 ? g.f16_sa : nullptr), (const int*)b.tile_item0, b.ticket,
-                         tc.ch);
-    else
-    hipLaunchKernelGGL(l1 ? (f32g ? k_raster_fwd_mfma<5> : k_raster_fwd_mfma<4>)
-                          : (f32g ? k_raster_fwd_mfma<1>
-                                  : (out_depth || depth_sums ? k_raster_fwd_mfma<2> : k_raster_fwd_mfma<3>)),
-                       dim3((unsigned)cap), dim3(256), 0, s, vk, n, (const int4*)b.items,
-                       (const int*)b.num_items, (const int2*)b.ranges, (const int*)b.pairs, (const float4*)g.rec,
-                       sc.fwd_part, out_rgb, out_alpha, out_depth, saved4, savedD, la, UF,
-                       (const int*)(n > 0 && num_pairs > 0 ? g.f16_sa : nullptr), (const int*)b.tile_item0, b.ticket,
-                       tc.ch);
+    if (c.tc.T == T32) {
+      const k_fwd32_l1_args a = fwd32_args(c, out_rgb, out_alpha, la, UF);  // (its one-view form is positional)
+      hipLaunchKernelGGL(k_fwd32_l1, dim3((unsigned)c.cap), dim3(256), 0, s, a.v, a.n, a.items, a.num_items, a.ranges,
+                         a.pairs, a.rec, a.fwd_part, a.out_rgb, a.out_alpha, a.l1, a.UF, a.f16_sa, a.tile_item0, a.ticket,
+                         a.ch);
+    } else
+      launch_one(l1 ? (f32g ? k_raster_fwd_mfma<5> : k_raster_fwd_mfma<4>)
+                    : (f32g ? k_raster_fwd_mfma<1>
+                            : (out_depth || depth_sums ? k_raster_fwd_mfma<2> : k_raster_fwd_mfma<3>)),
+                 dim3((unsigned)c.cap), 256, 0, s, fwd_mfma_args(c, out_rgb, out_alpha, out_depth, saved, la, UF));
     GR_HIP_TRY(hipGetLastError());
     prof_mark(PROF_RASTER_FWD, s);
   }
@@ -5992,11 +6134,7 @@ gr_status gr_fwd_bin(const gr_view* v, int n, const gr_plan* plan, const void* g
   if (bins_bytes < gr_bins_bytes(v, n, plan)) return set_error(GR_ERR_WORKSPACE, "bins workspace too small");
   if (scratch_bytes < gr_fwd_scratch_bytes(v, n, plan) || !scratch)
     return set_error(GR_ERR_WORKSPACE, "forward scratch workspace too small");
-  const ViewK vk = make_viewk(v);
-  const int vtiles = 2 * vk.tiles_x * vk.tiles_y;
-  const TileCfg tc = tile_cfg(v, plan->num_pairs);
-  return bin_impl(v, n, plan, geom, bins_view(bins, vtiles, plan->num_pairs, tc.ch),
-                  scratch_view(scratch, vtiles, plan->num_pairs, tc.ch, tc.part_floats), vk, (hipStream_t)stream);
+  return bin_impl(view_ctx(v, n, plan, geom, bins, scratch, nullptr), (hipStream_t)stream);
 }
 
 gr_status gr_fwd_render_l1(const gr_view* v, int n, const gr_plan* plan, const void* geom, void* bins, size_t bins_bytes,
@@ -6037,8 +6175,7 @@ static gr_status bwd_impl(const gr_view* v, int n, const gr_plan* plan, const fl
   if (v->rows > 0)
     return set_error(GR_ERR_INVALID_ARGUMENT, "a band of tile rows (gr_view.rows): the fused fit path only (gr_bwd_splat)");
   if (!plan) return set_error(GR_ERR_INVALID_ARGUMENT, "plan is null");
-  if (color_dim != 3 && color_dim != 12 && color_dim != 48)
-    return set_error(GR_ERR_INVALID_ARGUMENT, "colors must be (N,3) or SH coeffs (N,4,3) / (N,16,3)");
+  if ((st = check_color_dim(color_dim)) != GR_OK) return st;
   if (n == 0) return GR_OK;
   const bool gather_only = g_sums != nullptr;  // gr_bwd_fit_gather: the per-Gaussian sums to the caller, no chain rule
   if ((!g_rgb && !t_rgb) || !saved || !geom || !bins ||
@@ -6053,34 +6190,25 @@ static gr_status bwd_impl(const gr_view* v, int n, const gr_plan* plan, const fl
   if ((num_pairs > 0 || t_rgb) && (!ws || ws_bytes < ws_need))
     return set_error(GR_ERR_WORKSPACE, "backward workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  const ViewK vk = make_viewk(v);
-  const int tiles = vk.tiles_x * vk.tiles_y;
-  Geom g = geom_view((void*)geom, n);
-  Bins b = bins_view((void*)bins, 2 * tiles, num_pairs, tile_cfg(v, num_pairs).ch);
-  const size_t HW = (size_t)v->width * v->height;
-  const BwdWs w = bwd_ws(v, n, plan, ws);
+  const ViewCtx c = view_ctx(v, n, plan, geom, bins, nullptr, ws);
+  const ViewK& vk = c.vk;
+  const int tiles = c.tiles;
+  const Geom& g = c.g;
+  const Bins& b = c.b;
+  const size_t HW = c.HW;
+  const BwdWs& w = c.w;
   float* partials = w.partials;
   uint4* UF = w.UF;
-  float* tile_loss = w.tile_loss;
   const bool dfit = t_rgb && t_depth;  // fused depth loss (gr_bwd_fit)
-  L1Args l1{t_rgb, t_mask, w_sil, g_scale, t_rgb ? tile_loss : nullptr};
-  if (t_rgb) {  // the view loss: written by k_pixel_grads' last tile
-    l1.loss_out = loss_out;
-    l1.n1 = (int64_t)(3 * HW);
-    l1.n2 = (int64_t)(t_mask ? HW : 0);
-  }
+  // the view loss: written by k_pixel_grads' last tile
+  L1Args l1 = t_rgb ? fit_l1_args(c, t_rgb, t_mask, w_sil, g_scale, loss_out, t_depth, w_depth)
+                    : L1Args{t_rgb, t_mask, w_sil, g_scale, nullptr};
   // the arrival tickets of the one-launch reductions below: the bins' (zeroed by the work-item builder, left zero
   // by every kernel that takes one)
   int* ticket = b.ticket;
   if (dfit) {
-    l1.t_depth = t_depth;
-    l1.w_depth = w_depth;
-    l1.dscal = w.dscal;
-    const float4* s4 = (const float4*)saved;
-    const float* sD = saved + 4 * HW;
-    hipLaunchKernelGGL(k_depth_tile_max, dim3(tiles), dim3(256), 0, s, vk, s4, sD, w.tile_aux, w.dscal, ticket);
-    hipLaunchKernelGGL(k_depth_tile_sums, dim3(tiles), dim3(256), 0, s, vk, s4, sD, t_depth, w.dscal, tile_loss, w.tile_aux,
-                       (int64_t)HW, w_depth, g_scale, ticket);
+    launch_one(k_depth_tile_max, dim3(tiles), 256, 0, s, depth_tile_max_args(c, saved));
+    launch_one(k_depth_tile_sums, dim3(tiles), 256, 0, s, depth_tile_sums_args(c, saved, t_depth, w_depth, g_scale));
     GR_HIP_TRY(hipGetLastError());
   }
   const bool depth = g_depth != nullptr || dfit;  // an upstream depth gradient reaches the splat
@@ -6099,17 +6227,14 @@ static gr_status bwd_impl(const gr_view* v, int n, const gr_plan* plan, const fl
                        (const float*)maps, (const float*)partial, UF, pieces, l1, depth, ticket);
     GR_HIP_TRY(hipGetLastError());
   } else if (num_pairs > 0 || t_rgb) {
-    hipLaunchKernelGGL(k_pixel_grads, dim3(tiles), dim3(256), 0, s, vk, (const float4*)saved, saved + 4 * HW, g_rgb,
-                       g_alpha, g_depth, UF, pieces, l1, depth, ticket);
+    launch_one(k_pixel_grads, dim3(tiles), 256, 0, s,
+               pixel_grads_args(c, saved, g_rgb, g_alpha, g_depth, pieces, l1, depth));
     GR_HIP_TRY(hipGetLastError());
   }
   if (num_pairs > 0) {
-    const int64_t cap = item_cap(2 * tiles, num_pairs, tile_cfg(v, num_pairs).ch);
     prof_mark(PROF_RASTER_BWD, s);
     auto kern = depth ? k_raster_bwd_bf16<true, 3> : (pieces == 2 ? k_raster_bwd_bf16<false, 2> : k_raster_bwd_bf16<false, 3>);
-    hipLaunchKernelGGL(kern, dim3((unsigned)cap), dim3(256), 0, s, vk, n, (const int4*)b.items, (const int*)b.num_items,
-                       (const int*)b.pairs, (const float4*)g.rec, (const uint4*)UF, partials,
-                       partials + 8 * (size_t)plan->num_slots);
+    launch_one(kern, dim3((unsigned)c.cap), 256, 0, s, bwd_bf16_args(c, c.depth3()));
     GR_HIP_TRY(hipGetLastError());
     prof_mark(PROF_RASTER_BWD, s);
   }
@@ -6118,16 +6243,10 @@ static gr_status bwd_impl(const gr_view* v, int n, const gr_plan* plan, const fl
     // 32-byte rows: the lean gather into per-Gaussian sums (with a depth gradient also the tail pairs and
     // the depth sums), then the chain rule of that one view (the two stages of gr_gather_view +
     // gr_reduce_sums; k_reduce_bwd's one pass needs 117 VGPRs for the chain rule while it gathers)
-    float* depth3 = partials + 8 * (size_t)plan->num_slots;
     float* sums = gather_only ? g_sums : w.sums;
     float* sums3 = gather_only ? g_sums3 : w.sums3;
-    if (depth)
-      hipLaunchKernelGGL(k_gather_view<true>, dim3((n + 63) / 64), dim3(256), 0, s, n, (const Cnt2*)g.offsets,
-                         (const int*)b.pos_of, (const float4*)partials, (float2*)sums, (const float*)depth3, sums3);
-    else
-      hipLaunchKernelGGL(k_gather_view<false>, dim3((n + 63) / 64), dim3(256), 0, s, n, (const Cnt2*)g.offsets,
-                         (const int*)b.pos_of, (const float4*)partials, (float2*)sums, (const float*)nullptr,
-                         (float*)nullptr);
+    launch_one(depth ? k_gather_view<true> : k_gather_view<false>, dim3((n + 63) / 64), 256, 0, s,
+               gather_args(c, sums, sums3, depth));
     if (gather_only) {
       if (!depth && sums3) GR_HIP_TRY(hipMemsetAsync(sums3, 0, (size_t)n * sizeof(float), s));
       GR_HIP_TRY(hipGetLastError());
@@ -6141,15 +6260,10 @@ static gr_status bwd_impl(const gr_view* v, int n, const gr_plan* plan, const fl
     B.r[0].sums3 = depth ? w.sums3 : nullptr;
     const int gpb = 64 * (4 / reduce_sums_crw(1, color_dim));
     const dim3 grid((n + gpb - 1) / gpb), block(256);
-    if (color_dim == 3)
-      hipLaunchKernelGGL(k_reduce_sums<3>, grid, block, 0, s, B, n, means, scales, colors, opacities, d_means, d_scales,
+    with_color_dim(color_dim, [&](auto cd) {
+      hipLaunchKernelGGL(k_reduce_sums<cd()>, grid, block, 0, s, B, n, means, scales, colors, opacities, d_means, d_scales,
                          d_colors, d_opacities, accumulate, sum_index);
-    else if (color_dim == 12)
-      hipLaunchKernelGGL(k_reduce_sums<12>, grid, block, 0, s, B, n, means, scales, colors, opacities, d_means, d_scales,
-                         d_colors, d_opacities, accumulate, sum_index);
-    else
-      hipLaunchKernelGGL(k_reduce_sums<48>, grid, block, 0, s, B, n, means, scales, colors, opacities, d_means, d_scales,
-                         d_colors, d_opacities, accumulate, sum_index);
+    });
   } else if (gather_only) {  // no pair: every sum is zero
     GR_HIP_TRY(hipMemsetAsync(g_sums, 0, gr_view_sums_floats(n) * sizeof(float), s));
     if (g_sums3) GR_HIP_TRY(hipMemsetAsync(g_sums3, 0, (size_t)n * sizeof(float), s));
@@ -6163,12 +6277,9 @@ static gr_status bwd_impl(const gr_view* v, int n, const gr_plan* plan, const fl
                          (const Cnt2*)g.counts, (const Cnt2*)g.offsets, (const int*)b.pos_of, (const float*)partials,
                          d_means, d_scales, d_colors, d_opacities, depth ? 1 : 0, accumulate);
     };
-    if (color_dim == 3)
-      row8 ? launch(k_reduce_bwd<3, true>) : launch(k_reduce_bwd<3, false>);
-    else if (color_dim == 12)
-      row8 ? launch(k_reduce_bwd<12, true>) : launch(k_reduce_bwd<12, false>);
-    else
-      row8 ? launch(k_reduce_bwd<48, true>) : launch(k_reduce_bwd<48, false>);
+    with_color_dim(color_dim, [&](auto cd) {
+      row8 ? launch(k_reduce_bwd<cd(), true>) : launch(k_reduce_bwd<cd(), false>);
+    });
   }
   GR_HIP_TRY(hipGetLastError());
   prof_mark(PROF_REDUCE, s);
@@ -6260,34 +6371,8 @@ gr_status gr_bwd_l1(const gr_view* v, int n, const gr_plan* plan, const float* m
                   accumulate, ws, ws_bytes, stream);
 }
 
-}  // extern "C" (the batching helpers are templates)
-
-// ---- gr_fit_views_batched: the fused fit path's per-view chain for several views, one launch per kernel -----------
-template <class A>
-static void vb_add(VBatch<A>& B, const A& a, int blocks, int gx = 0) {
-  B.a[B.nv] = a;
-  B.gx[B.nv] = gx > 0 ? gx : (blocks > 0 ? blocks : 1);
-  B.first[B.nv + 1] = B.first[B.nv] + (blocks > 0 ? blocks : 0);
-  ++B.nv;
-}
-template <class A>
-static VBatch<A> vb_new() {
-  static_assert(sizeof(VBatch<A>) <= 4096, "batched kernel arguments exceed 4 KiB");
-  VBatch<A> B;
-  B.nv = 0;
-  B.first[0] = 0;
-  return B;
-}
-#define GR_VB_LAUNCH(kern, B, threads, lds, s)                                                   \
-  do {                                                                                           \
-    if ((B).first[(B).nv] > 0) {                                                                 \
-      hipLaunchKernelGGL(kern, dim3((unsigned)(B).first[(B).nv]), dim3(threads), lds, s, (B));   \
-      GR_HIP_TRY(hipGetLastError());                                                             \
-    }                                                                                            \
-  } while (0)
-
-extern "C" {
-
+// gr_fit_views_batched: the fused fit path's per-view chain for several views, one launch per kernel (vb_add of the
+// one-view chain's own argument builders)
 gr_status gr_fit_views_batched(int num_views, const gr_batch_view* bv, int n, float w_sil, float w_depth,
                                           float g_scale, void* stream) {
   if (num_views < 1 || num_views > GR_BATCH_MAX_VIEWS || !bv)
@@ -6323,58 +6408,28 @@ gr_status gr_fit_views_batched(int num_views, const gr_batch_view* bv, int n, fl
       return set_error(GR_ERR_INVALID_ARGUMENT, "gr_fit_views_batched: a band of tile rows needs the L1 path (no depth loss)");
   hipStream_t s = (hipStream_t)stream;
   const int tiles = vtiles_of(&v0) / 2;
-  const size_t HW = (size_t)v0.width * v0.height;
-  const int waves = tsort_waves(tiles), bits = bits_for((uint32_t)tiles);
+  ViewCtx ctx[GR_BATCH_MAX];
+  for (int j = 0; j < num_views; ++j)
+    ctx[j] = view_ctx(&bv[j].view, n, &bv[j].plan, bv[j].geom, bv[j].bins, bv[j].scratch, bv[j].ws);
   auto Be = vb_new<k_emit_offsets_args>();
   auto Bc = vb_new<k_tile_count_args>();
   auto Bs = vb_new<k_tile_colscan_args>();
   auto Bp = vb_new<k_tile_place_args>();
   for (int j = 0; j < num_views; ++j) {  // the binning (bin_impl's counting-sort path, per view)
-    const gr_batch_view& b = bv[j];
-    const ViewK vk = make_viewk(&b.view);
-    const TileCfg tc = tile_cfg(&b.view, b.plan.num_pairs);
-    const Bins bn = bins_view(b.bins, 2 * tiles, b.plan.num_pairs, tc.ch);
-    const Scratch sc = scratch_view(b.scratch, 2 * tiles, b.plan.num_pairs, tc.ch, tc.part_floats);
-    Geom g = geom_view((void*)b.geom, n);
-    const int64_t K = b.plan.num_pairs, Kc = b.plan.num_core_pairs, Kr[2] = {Kc, K - Kc};
-    TZones Z;
-    Z.cw = col_width(K, tiles);
-    Z.ch = tc.ch;
-    Z.kdev = b.view.device_counts ? (const unsigned long long*)(g.offsets + n) : nullptr;
-    const size_t cells = (size_t)tiles * cols_of(K, Z.cw);
-    char* q = (char*)sc.sort_tmp;
-    for (int z = 0; z < 2; ++z) {
-      TZone& zz = Z.z[z];
-      zz.K = Kr[z];
-      zz.cols = cols_of(Kr[z], Z.cw);
-      zz.zbase = z == 0 ? 0 : (int)Kc;
-      zz.keys = (const uint16_t*)sc.keys_in + (z == 0 ? 0 : Kc);
-      zz.ids = sc.ids_in + (z == 0 ? 0 : Kc);
-      zz.M = (int*)q;
-      q += align_up(cells * sizeof(int));
-      zz.S = (int*)q;
-      q += align_up(cells * sizeof(int));
-      zz.T = (int*)q;
-      q += align_up((size_t)tiles * sizeof(int));
-    }
+    const ViewCtx& c = ctx[j];
+    const TZones Z = tile_zones(c);
     const int cols = Z.z[0].cols + Z.z[1].cols;
-    vb_add(Be, k_emit_offsets_args{vk, n, (const int4*)g.rect, (const Cnt2*)g.counts, (const unsigned long long*)g.total,
-                                   (Cnt2*)g.offsets, (const float4*)g.rec, (uint16_t*)sc.keys_in, sc.ids_in,
-                                   bn.ticket + fan_offset(tiles)},
-           blocks_for(n));
-    vb_add(Bc, k_tile_count_args{Z, tiles}, cols);
+    vb_add(Be, emit_offsets_args(c), blocks_for(n));
+    vb_add(Bc, tile_count_args(c, Z), cols);
     const int gxs = (tiles + CS_T - 1) / CS_T;
-    vb_add(Bs, k_tile_colscan_args{Z, tiles, bn.ranges, bn.items, bn.num_items, bn.tile_item0, bn.ticket}, 2 * gxs, gxs);
-    vb_add(Bp, k_tile_place_args{Z, tiles, bits, (const int2*)bn.ranges, bn.pairs, bn.pos_of}, cols);
+    vb_add(Bs, tile_colscan_args(c, Z), 2 * gxs, gxs);
+    vb_add(Bp, tile_place_args(c, Z), cols);
   }
   GR_VB_LAUNCH(k_emit_offsets_views, Be, 256, 0, s);
   GR_VB_LAUNCH(k_tile_count_views, Bc, 256, (size_t)tiles * sizeof(int), s);
   GR_VB_LAUNCH(k_tile_colscan_views, Bs, CS_T * CS_G, 0, s);
-  const size_t lds = (size_t)tiles * sizeof(int) * waves;
-  if (waves == 8) GR_VB_LAUNCH(k_tile_place_views<8>, Bp, 512, lds, s);
-  else if (waves == 4) GR_VB_LAUNCH(k_tile_place_views<4>, Bp, 256, lds, s);
-  else if (waves == 2) GR_VB_LAUNCH(k_tile_place_views<2>, Bp, 128, lds, s);
-  else GR_VB_LAUNCH(k_tile_place_views<1>, Bp, 64, lds, s);
+  const TilePlace place = tile_place_of(tiles);
+  GR_VB_LAUNCH(place.views, Bp, place.threads, place.lds, s);
 
   auto Bg = vb_new<k_gather_view_args>();
   if (!depth) {  // the fused fit path: forward with the L1 epilogue, backward splat, gather
@@ -6384,39 +6439,18 @@ gr_status gr_fit_views_batched(int num_views, const gr_batch_view* bv, int n, fl
     auto Bb16 = vb_new<k_raster_bwd_bf16_args>();
     for (int j = 0; j < num_views; ++j) {
       const gr_batch_view& b = bv[j];
-      const ViewK vk = make_viewk(&b.view);
-      const TileCfg tc = tile_cfg(&b.view, b.plan.num_pairs);
-      const Bins bn = bins_view(b.bins, 2 * tiles, b.plan.num_pairs, tc.ch);
-      const Scratch sc = scratch_view(b.scratch, 2 * tiles, b.plan.num_pairs, tc.ch, tc.part_floats);
-      const Geom g = geom_view((void*)b.geom, n);
-      const BwdWs w = bwd_ws(&b.view, n, &b.plan, b.ws);
-      L1Args la{b.target_rgb, b.target_mask, w_sil, g_scale, w.tile_loss};
+      const ViewCtx& c = ctx[j];
+      L1Args la = fit_l1_args(c, b.target_rgb, b.target_mask, w_sil, g_scale, b.loss);
       la.pieces = 2;
-      la.loss_out = b.loss;
-      la.n1 = (int64_t)(3 * HW);
-      la.n2 = (int64_t)(b.target_mask ? HW : 0);
-      const int cap = (int)item_cap(2 * tiles, b.plan.num_pairs, tc.ch);
-      if (tc.T == T32) {
-        vb_add(Bf, k_fwd32_l1_args{vk, n, (const int4*)bn.items, (const int*)bn.num_items, (const int2*)bn.ranges,
-                                   (const int*)bn.pairs, (const float4*)g.rec, sc.fwd_part, nullptr, nullptr, la, w.UF,
-                                   (const int*)g.f16_sa, (const int*)bn.tile_item0, bn.ticket, tc.ch},
-               cap);
-        vb_add(Bb, k_bwd32_args{vk, n, (const int4*)bn.items, (const int*)bn.num_items, (const int*)bn.pairs,
-                                (const float4*)g.rec, (const uint4*)w.UF, w.partials},
-               cap);
+      const int cap = (int)c.cap;
+      if (c.tc.T == T32) {
+        vb_add(Bf, fwd32_args(c, nullptr, nullptr, la, c.w.UF), cap);
+        vb_add(Bb, bwd32_args(c), cap);
       } else {
-        vb_add(Bf16, k_raster_fwd_mfma_args{vk, n, (const int4*)bn.items, (const int*)bn.num_items, (const int2*)bn.ranges,
-                                            (const int*)bn.pairs, (const float4*)g.rec, sc.fwd_part, nullptr, nullptr,
-                                            nullptr, nullptr, nullptr, la, w.UF, (const int*)g.f16_sa,
-                                            (const int*)bn.tile_item0, bn.ticket, tc.ch},
-               cap);
-        vb_add(Bb16, k_raster_bwd_bf16_args{vk, n, (const int4*)bn.items, (const int*)bn.num_items, (const int*)bn.pairs,
-                                            (const float4*)g.rec, (const uint4*)w.UF, w.partials, nullptr},
-               cap);
+        vb_add(Bf16, fwd_mfma_args(c, nullptr, nullptr, nullptr, nullptr, la, c.w.UF), cap);
+        vb_add(Bb16, bwd_bf16_args(c, nullptr), cap);
       }
-      vb_add(Bg, k_gather_view_args{n, (const Cnt2*)g.offsets, (const int*)bn.pos_of, (const float4*)w.partials,
-                                    (float2*)b.sums, nullptr, nullptr},
-             (n + 63) / 64);
+      vb_add(Bg, gather_args(c, b.sums, nullptr, false), (n + 63) / 64);
     }
     GR_VB_LAUNCH(k_fwd32_l1_views, Bf, 256, 0, s);
     GR_VB_LAUNCH(k_raster_fwd_mfma_views<4>, Bf16, 256, 0, s);
@@ -6434,40 +6468,16 @@ gr_status gr_fit_views_batched(int num_views, const gr_batch_view* bv, int n, fl
   auto Bb = vb_new<k_raster_bwd_bf16_args>();
   for (int j = 0; j < num_views; ++j) {
     const gr_batch_view& b = bv[j];
-    const ViewK vk = make_viewk(&b.view);
-    const TileCfg tc = tile_cfg(&b.view, b.plan.num_pairs);
-    const Bins bn = bins_view(b.bins, 2 * tiles, b.plan.num_pairs, tc.ch);
-    const Scratch sc = scratch_view(b.scratch, 2 * tiles, b.plan.num_pairs, tc.ch, tc.part_floats);
-    const Geom g = geom_view((void*)b.geom, n);
-    const BwdWs w = bwd_ws(&b.view, n, &b.plan, b.ws);
-    float4* s4 = (float4*)b.saved;
-    float* sD = b.saved + 4 * HW;
-    const int cap = (int)item_cap(2 * tiles, b.plan.num_pairs, tc.ch);
-    L1Args none{nullptr, nullptr, 0.f, 0.f, nullptr};
-    vb_add(Bf, k_raster_fwd_mfma_args{vk, n, (const int4*)bn.items, (const int*)bn.num_items, (const int2*)bn.ranges,
-                                      (const int*)bn.pairs, (const float4*)g.rec, sc.fwd_part, nullptr, nullptr, nullptr,
-                                      s4, sD, none, nullptr, (const int*)g.f16_sa, (const int*)bn.tile_item0, bn.ticket,
-                                      tc.ch},
-           cap);
-    vb_add(Bm, k_depth_tile_max_args{vk, s4, sD, w.tile_aux, w.dscal, bn.ticket}, tiles);
-    vb_add(Bd, k_depth_tile_sums_args{vk, s4, sD, b.target_depth, w.dscal, w.tile_loss, w.tile_aux, (int64_t)HW, w_depth,
-                                      g_scale, bn.ticket},
-           tiles);
-    L1Args l1{b.target_rgb, b.target_mask, w_sil, g_scale, w.tile_loss};
-    l1.loss_out = b.loss;
-    l1.n1 = (int64_t)(3 * HW);
-    l1.n2 = (int64_t)(b.target_mask ? HW : 0);
-    l1.t_depth = b.target_depth;
-    l1.w_depth = w_depth;
-    l1.dscal = w.dscal;
-    vb_add(Bu, k_pixel_grads_args{vk, s4, sD, nullptr, nullptr, nullptr, w.UF, 3, l1, true, bn.ticket}, tiles);
-    vb_add(Bb, k_raster_bwd_bf16_args{vk, n, (const int4*)bn.items, (const int*)bn.num_items, (const int*)bn.pairs,
-                                      (const float4*)g.rec, (const uint4*)w.UF, w.partials,
-                                      w.partials + 8 * (size_t)b.plan.num_slots},
-           cap);
-    vb_add(Bg, k_gather_view_args{n, (const Cnt2*)g.offsets, (const int*)bn.pos_of, (const float4*)w.partials,
-                                  (float2*)b.sums, (const float*)(w.partials + 8 * (size_t)b.plan.num_slots), b.sums3},
-           (n + 63) / 64);
+    const ViewCtx& c = ctx[j];
+    const int cap = (int)c.cap;
+    const L1Args none{nullptr, nullptr, 0.f, 0.f, nullptr};
+    vb_add(Bf, fwd_mfma_args(c, nullptr, nullptr, nullptr, b.saved, none, nullptr), cap);
+    vb_add(Bm, depth_tile_max_args(c, b.saved), tiles);
+    vb_add(Bd, depth_tile_sums_args(c, b.saved, b.target_depth, w_depth, g_scale), tiles);
+    const L1Args l1 = fit_l1_args(c, b.target_rgb, b.target_mask, w_sil, g_scale, b.loss, b.target_depth, w_depth);
+    vb_add(Bu, pixel_grads_args(c, b.saved, nullptr, nullptr, nullptr, 3, l1, true), tiles);
+    vb_add(Bb, bwd_bf16_args(c, c.depth3()), cap);
+    vb_add(Bg, gather_args(c, b.sums, b.sums3, true), (n + 63) / 64);
   }
   GR_VB_LAUNCH(k_raster_fwd_mfma_views<1>, Bf, 256, 0, s);
   GR_VB_LAUNCH(k_depth_tile_max_views, Bm, 256, 0, s);
@@ -6490,24 +6500,18 @@ gr_status gr_bwd_splat(const gr_view* v, int n, const gr_plan* plan, const void*
   if (!geom || !bins) return set_error(GR_ERR_INVALID_ARGUMENT, "null pointer");
   if (!ws || ws_bytes < gr_bwd_bytes(v, n, plan)) return set_error(GR_ERR_WORKSPACE, "backward workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  const ViewK vk = make_viewk(v);
-  const int tiles = vk.tiles_x * vk.tiles_y;
-  const Geom g = geom_view((void*)geom, n);
-  const TileCfg tc = tile_cfg(v, plan->num_pairs);
-  if (tc.T == T32 && v->no_depth_grad != 1)
+  const ViewCtx c = view_ctx(v, n, plan, geom, bins, nullptr, ws);
+  if (c.tc.T == T32 && v->no_depth_grad != 1)
     return set_error(GR_ERR_INVALID_ARGUMENT, "32-pixel tiles (gr_view.tile = 32): no_depth_grad = 1 only");
-  const Bins b = bins_view((void*)bins, 2 * tiles, plan->num_pairs, tc.ch);
-  const BwdWs w = bwd_ws(v, n, plan, ws);
-  const int64_t cap = item_cap(2 * tiles, plan->num_pairs, tc.ch);
   if (GR_DEBUG_SKIP & 2) return GR_OK;
   prof_mark(PROF_RASTER_BWD, s);
-  if (tc.T == T32)
-    hipLaunchKernelGGL(k_bwd32, dim3((unsigned)cap), dim3(256), 0, s, vk, n, (const int4*)b.items,
-                       (const int*)b.num_items, (const int*)b.pairs, (const float4*)g.rec, (const uint4*)w.UF, w.partials);
-  else
-  hipLaunchKernelGGL((v->no_depth_grad == 1 ? k_raster_bwd_bf16<false, 2> : k_raster_bwd_bf16<false, 3>), dim3((unsigned)cap),
-                     dim3(256), 0, s, vk, n, (const int4*)b.items, (const int*)b.num_items, (const int*)b.pairs,
-                     (const float4*)g.rec, (const uint4*)w.UF, w.partials, (float*)nullptr);
+  if (c.tc.T == T32) {
+    const k_bwd32_args a = bwd32_args(c);  // (its one-view form is positional)
+    hipLaunchKernelGGL(k_bwd32, dim3((unsigned)c.cap), dim3(256), 0, s, a.v, a.n, a.items, a.num_items, a.pairs, a.rec,
+                       a.UF, a.partials);
+  } else
+    launch_one(v->no_depth_grad == 1 ? k_raster_bwd_bf16<false, 2> : k_raster_bwd_bf16<false, 3>, dim3((unsigned)c.cap),
+               256, 0, s, bwd_bf16_args(c, nullptr));
   GR_HIP_TRY(hipGetLastError());
   prof_mark(PROF_RASTER_BWD, s);
   return GR_OK;
@@ -6518,8 +6522,7 @@ gr_status gr_reduce_views(int num_views, const gr_reduce_view* views, int n, con
                           float* d_colors, float* d_opacities, int accumulate, void* stream) {
   if (num_views < 0 || num_views > GR_REDUCE_MAX_VIEWS)
     return set_error(GR_ERR_INVALID_ARGUMENT, "gr_reduce_views: num_views must be in [0, GR_REDUCE_MAX_VIEWS]");
-  if (color_dim != 3 && color_dim != 12 && color_dim != 48)
-    return set_error(GR_ERR_INVALID_ARGUMENT, "colors must be (N,3) or SH coeffs (N,4,3) / (N,16,3)");
+  if (gr_status st = check_color_dim(color_dim); st != GR_OK) return st;
   if (n < 0) return set_error(GR_ERR_INVALID_ARGUMENT, "n must be >= 0");
   if (n == 0) return GR_OK;
   if (!means || !scales || !colors || !opacities || !d_means || !d_scales || !d_colors || !d_opacities ||
@@ -6536,26 +6539,19 @@ gr_status gr_reduce_views(int num_views, const gr_reduce_view* views, int n, con
     if (rv.plan.num_pairs < 0) return set_error(GR_ERR_OVERFLOW, "pair count overflows int32");
     if (!rv.geom || (rv.plan.num_pairs > 0 && (!rv.bins || !rv.ws)))
       return set_error(GR_ERR_INVALID_ARGUMENT, "gr_reduce_views: null workspace");
-    const ViewK vk = make_viewk(&rv.view);
-    const Geom g = geom_view((void*)rv.geom, n);
-    const Bins b = bins_view((void*)rv.bins, 2 * vk.tiles_x * vk.tiles_y, rv.plan.num_pairs, tile_cfg(&rv.view, rv.plan.num_pairs).ch);
-    B.r[k].v = vk;
-    B.r[k].offsets = (const Cnt2*)g.offsets;
-    B.r[k].pos_of = rv.plan.num_pairs > 0 ? (const int*)b.pos_of : nullptr;
+    const ViewCtx c = view_ctx(&rv.view, n, &rv.plan, rv.geom, rv.bins, nullptr, nullptr);
+    B.r[k].v = c.vk;
+    B.r[k].offsets = (const Cnt2*)c.g.offsets;
+    B.r[k].pos_of = rv.plan.num_pairs > 0 ? (const int*)c.b.pos_of : nullptr;
     B.r[k].rows = (const float4*)rv.ws;
   }
   hipStream_t s = (hipStream_t)stream;
   prof_mark(PROF_REDUCE, s);
   const dim3 grid((n + RG - 1) / RG), block(4 * RG);
-  if (color_dim == 3)
-    hipLaunchKernelGGL(k_reduce_views<3>, grid, block, 0, s, B, n, means, scales, colors, opacities, d_means, d_scales,
+  with_color_dim(color_dim, [&](auto cd) {
+    hipLaunchKernelGGL(k_reduce_views<cd()>, grid, block, 0, s, B, n, means, scales, colors, opacities, d_means, d_scales,
                        d_colors, d_opacities, accumulate);
-  else if (color_dim == 12)
-    hipLaunchKernelGGL(k_reduce_views<12>, grid, block, 0, s, B, n, means, scales, colors, opacities, d_means, d_scales,
-                       d_colors, d_opacities, accumulate);
-  else
-    hipLaunchKernelGGL(k_reduce_views<48>, grid, block, 0, s, B, n, means, scales, colors, opacities, d_means, d_scales,
-                       d_colors, d_opacities, accumulate);
+  });
   GR_HIP_TRY(hipGetLastError());
   prof_mark(PROF_REDUCE, s);
   return GR_OK;
@@ -6580,13 +6576,10 @@ gr_status gr_gather_view(const gr_view* v, int n, const gr_plan* plan, const voi
     GR_HIP_TRY(hipMemsetAsync(sums, 0, gr_view_sums_floats(n) * sizeof(float), s));
     return GR_OK;
   }
-  const ViewK vk = make_viewk(v);
-  const Geom g = geom_view((void*)geom, n);
-  const Bins b = bins_view((void*)bins, 2 * vk.tiles_x * vk.tiles_y, plan->num_pairs, tile_cfg(v, plan->num_pairs).ch);
+  const ViewCtx c = view_ctx(v, n, plan, geom, bins, nullptr, ws);
   if (GR_DEBUG_SKIP & 4) return GR_OK;
   prof_mark(PROF_REDUCE, s);
-  hipLaunchKernelGGL(k_gather_view<false>, dim3((n + 63) / 64), dim3(256), 0, s, n, (const Cnt2*)g.offsets,
-                     (const int*)b.pos_of, (const float4*)ws, (float2*)sums, (const float*)nullptr, (float*)nullptr);
+  launch_one(k_gather_view<false>, dim3((n + 63) / 64), 256, 0, s, gather_args(c, sums, nullptr, false));
   GR_HIP_TRY(hipGetLastError());
   prof_mark(PROF_REDUCE, s);
   return GR_OK;
@@ -6597,8 +6590,7 @@ gr_status gr_reduce_sums(int num_views, const gr_sums_view* views, int n, const 
                          float* d_colors, float* d_opacities, int accumulate, void* stream) {
   if (num_views < 0 || num_views > GR_REDUCE_MAX_VIEWS)
     return set_error(GR_ERR_INVALID_ARGUMENT, "gr_reduce_sums: num_views must be in [0, GR_REDUCE_MAX_VIEWS]");
-  if (color_dim != 3 && color_dim != 12 && color_dim != 48)
-    return set_error(GR_ERR_INVALID_ARGUMENT, "colors must be (N,3) or SH coeffs (N,4,3) / (N,16,3)");
+  if (gr_status st = check_color_dim(color_dim); st != GR_OK) return st;
   if (n < 0) return set_error(GR_ERR_INVALID_ARGUMENT, "n must be >= 0");
   if (n == 0) return GR_OK;
   if (!means || !scales || !colors || !opacities || !d_means || !d_scales || !d_colors || !d_opacities ||
@@ -6619,15 +6611,10 @@ gr_status gr_reduce_sums(int num_views, const gr_sums_view* views, int n, const 
   prof_mark(PROF_REDUCE, s);
   const int gpb = 64 * (4 / reduce_sums_crw(num_views, color_dim));
   const dim3 grid((n + gpb - 1) / gpb), block(256);
-  if (color_dim == 3)
-    hipLaunchKernelGGL(k_reduce_sums<3>, grid, block, 0, s, B, n, means, scales, colors, opacities, d_means, d_scales,
+  with_color_dim(color_dim, [&](auto cd) {
+    hipLaunchKernelGGL(k_reduce_sums<cd()>, grid, block, 0, s, B, n, means, scales, colors, opacities, d_means, d_scales,
                        d_colors, d_opacities, accumulate, (const int*)nullptr);
-  else if (color_dim == 12)
-    hipLaunchKernelGGL(k_reduce_sums<12>, grid, block, 0, s, B, n, means, scales, colors, opacities, d_means, d_scales,
-                       d_colors, d_opacities, accumulate, (const int*)nullptr);
-  else
-    hipLaunchKernelGGL(k_reduce_sums<48>, grid, block, 0, s, B, n, means, scales, colors, opacities, d_means, d_scales,
-                       d_colors, d_opacities, accumulate, (const int*)nullptr);
+  });
   GR_HIP_TRY(hipGetLastError());
   prof_mark(PROF_REDUCE, s);
   return GR_OK;
@@ -6670,8 +6657,7 @@ gr_status gr_camera_grads_sums(int num_views, const gr_sums_view* views, int n, 
                                void* ws, size_t ws_bytes, void* stream) {
   if (num_views < 1 || num_views > GR_REDUCE_MAX_VIEWS)
     return set_error(GR_ERR_INVALID_ARGUMENT, "gr_camera_grads_sums: num_views must be in [1, GR_REDUCE_MAX_VIEWS]");
-  if (color_dim != 3 && color_dim != 12 && color_dim != 48)
-    return set_error(GR_ERR_INVALID_ARGUMENT, "colors must be (N,3) or SH coeffs (N,4,3) / (N,16,3)");
+  if (gr_status st = check_color_dim(color_dim); st != GR_OK) return st;
   if (n < 0) return set_error(GR_ERR_INVALID_ARGUMENT, "n must be >= 0");
   if (!d_camera) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_camera_grads_sums: null output rows");
   for (int k = 0; k < num_views; ++k)
@@ -6700,12 +6686,9 @@ gr_status gr_camera_grads_sums(int num_views, const gr_sums_view* views, int n, 
     return set_error(GR_ERR_WORKSPACE, "gr_camera_grads_sums: workspace too small");
   const int blocks = blocks_for(n);
   double* part = (double*)ws;
-  if (color_dim == 3)
-    hipLaunchKernelGGL(k_camera_grad_views<3>, dim3(blocks), dim3(256), 0, s, B, n, means, scales, colors, opacities, part);
-  else if (color_dim == 12)
-    hipLaunchKernelGGL(k_camera_grad_views<12>, dim3(blocks), dim3(256), 0, s, B, n, means, scales, colors, opacities, part);
-  else
-    hipLaunchKernelGGL(k_camera_grad_views<48>, dim3(blocks), dim3(256), 0, s, B, n, means, scales, colors, opacities, part);
+  with_color_dim(color_dim, [&](auto cd) {
+    hipLaunchKernelGGL(k_camera_grad_views<cd()>, dim3(blocks), dim3(256), 0, s, B, n, means, scales, colors, opacities, part);
+  });
   GR_HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(k_camera_final_views, dim3(CAM_GRADS, num_views), dim3(64), 0, s, (const double*)part, blocks, rows);
   GR_HIP_TRY(hipGetLastError());
@@ -6719,8 +6702,7 @@ gr_status gr_bwd_camera(const gr_view* v, int n, const gr_plan* plan, const floa
   if (st != GR_OK) return st;
   if (!plan || !d_camera) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_bwd_camera: null plan or output");
   if (plan->num_pairs < 0) return set_error(GR_ERR_OVERFLOW, "pair count overflows int32");
-  if (color_dim != 3 && color_dim != 12 && color_dim != 48)
-    return set_error(GR_ERR_INVALID_ARGUMENT, "colors must be (N,3) or SH coeffs (N,4,3) / (N,16,3)");
+  if ((st = check_color_dim(color_dim)) != GR_OK) return st;
   if (n < 0) return set_error(GR_ERR_INVALID_ARGUMENT, "n must be >= 0");
   if (depth && v->no_depth_grad)
     return set_error(GR_ERR_INVALID_ARGUMENT, "gr_bwd_camera: depth sums of a view rendered with no_depth_grad");
@@ -6736,15 +6718,10 @@ gr_status gr_bwd_camera(const gr_view* v, int n, const gr_plan* plan, const floa
   const int blocks = blocks_for(n);
   const float4* sums = (const float4*)w.sums;
   const float* sums3 = depth ? (const float*)w.sums3 : nullptr;
-  if (color_dim == 3)
-    hipLaunchKernelGGL(k_camera_grad<3>, dim3(blocks), dim3(256), 0, s, vk, n, means, scales, colors, opacities, sums, sums3,
+  with_color_dim(color_dim, [&](auto cd) {
+    hipLaunchKernelGGL(k_camera_grad<cd()>, dim3(blocks), dim3(256), 0, s, vk, n, means, scales, colors, opacities, sums, sums3,
                        w.cam_part);
-  else if (color_dim == 12)
-    hipLaunchKernelGGL(k_camera_grad<12>, dim3(blocks), dim3(256), 0, s, vk, n, means, scales, colors, opacities, sums, sums3,
-                       w.cam_part);
-  else
-    hipLaunchKernelGGL(k_camera_grad<48>, dim3(blocks), dim3(256), 0, s, vk, n, means, scales, colors, opacities, sums, sums3,
-                       w.cam_part);
+  });
   GR_HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(k_camera_final, dim3(CAM_GRADS), dim3(64), 0, s, (const double*)w.cam_part, blocks, d_camera);
   GR_HIP_TRY(hipGetLastError());
@@ -7147,17 +7124,13 @@ gr_status gr_contrib_view(const gr_view* v, int n, const gr_plan* plan, const vo
   if (!ws) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_contrib_view: null pointer");
   if (ws_bytes < gr_contrib_ws_bytes(v, n, plan)) return set_error(GR_ERR_WORKSPACE, "gr_contrib_view: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  const ViewK vk = make_viewk(v);
-  const int vtiles = 2 * vk.tiles_x * vk.tiles_y;
-  const TileCfg tc = tile_cfg(v, plan->num_pairs);
-  const Geom g = geom_view((void*)geom, n);
-  const Bins b = bins_view((void*)bins, vtiles, plan->num_pairs, tc.ch);
-  hipLaunchKernelGGL(k_contrib_view, dim3((unsigned)item_cap(vtiles, plan->num_pairs, tc.ch)), dim3(256), 0, s, vk,
-                     (const int4*)b.items, (const int*)b.num_items, (const int*)b.pairs, (const float4*)g.rec,
-                     (const float4*)saved, (float*)ws);
+  const ViewCtx c = view_ctx(v, n, plan, geom, bins, nullptr, nullptr);
+  hipLaunchKernelGGL(k_contrib_view, dim3((unsigned)c.cap), dim3(256), 0, s, c.vk, (const int4*)c.b.items,
+                     (const int*)c.b.num_items, (const int*)c.b.pairs, (const float4*)c.g.rec, (const float4*)saved,
+                     (float*)ws);
   GR_HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_contrib_gather, dim3(blocks_for(n)), dim3(256), 0, s, n, (const Cnt2*)g.offsets, (const int*)b.pos_of,
-                     (const float*)ws, (unsigned*)peak);
+  hipLaunchKernelGGL(k_contrib_gather, dim3(blocks_for(n)), dim3(256), 0, s, n, (const Cnt2*)c.g.offsets,
+                     (const int*)c.b.pos_of, (const float*)ws, (unsigned*)peak);
   GR_HIP_TRY(hipGetLastError());
   return GR_OK;
 }
