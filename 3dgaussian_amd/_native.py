@@ -230,6 +230,10 @@ _SIG = {
     "gr_contrib_view": (ctypes.c_int, [_VP, ctypes.c_int, _PP, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "gr_contrib_views": (ctypes.c_int, [_P, ctypes.POINTER(GrFitConfig), ctypes.c_int, ctypes.POINTER(GrFitTarget),
                                         ctypes.c_int, _P, _P, _P, ctypes.c_int, _P, _P, _P]),
+    "gr_error_ws_bytes": (ctypes.c_size_t, [_VP, ctypes.c_int, _PP]),
+    "gr_error_view": (ctypes.c_int, [_VP, ctypes.c_int, _PP, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "gr_error_views": (ctypes.c_int, [_P, ctypes.POINTER(GrFitConfig), ctypes.c_int, ctypes.POINTER(GrFitTarget),
+                                      ctypes.c_int, _P, _P, _P, ctypes.c_int, _P, _P, _P]),
     "gr_render_u8": (ctypes.c_int, [ctypes.POINTER(GrRenderParams), ctypes.c_int, _P, _P, _P, _P, _P]),
     "gr_geom_layout": (None, [ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
     "gr_bins_layout": (None, [_VP, ctypes.c_int, _PP, ctypes.POINTER(ctypes.c_size_t)]),

@@ -229,3 +229,44 @@ def peak_contribution(means, scales, opacities, view, proj, width: int, height: 
             w = ov[a:b, None, None] * ey[:, :, None] * ex[:, None, :]
             peak[a:b] = (w * r[None]).flatten(1).max(dim=1).values
     return peak
+
+
+def blend_error(means, scales, colors, opacities, view, proj, width: int, height: int, target, background,
+                exposure=None) -> torch.Tensor:
+    """Per Gaussian, its share of one view's L1 error: ``err[i] = sum_p b_i(p) e(p)`` over all pixels, with
+    ``b_i = w_i / (1 + W)`` the render's blend weights and ``e(p) = mean_k |x_k(p) - target_k(p)|`` the pixel's colour
+    error, ``x = clamp((bg + sum w c) / (1 + W))`` the rendered colour (``exposure``, a (3, 4) matrix E: E (x, 1) in
+    its place, as the fit's photometric term compares it).  The blend weights and the background's ``1 / (1 + W)`` sum
+    to one, so ``sum_i err[i] + sum_p e / (1 + W) = sum_p e``: the error partitioned among the Gaussians and the
+    background.  The dense definition (every Gaussian at every pixel, no gradient); (N,) in the tensors' dtype;
+    chunked over the Gaussians, one contraction of ey, e / (1 + W) and ex per chunk."""
+    with torch.no_grad():
+        means, scales, colors, opacities = means.detach(), scales.detach(), colors.detach(), opacities.detach()
+        view = view.to(dtype=means.dtype, device=means.device)
+        proj = proj.to(dtype=means.dtype, device=means.device)
+        px, py, valid, za = _project(means, view, proj, width, height)
+        col = _colors(colors, means, view).clamp(0.0, 1.0)
+        fx, fy = proj[0, 0].abs(), proj[1, 1].abs()
+        sx = (scales[:, 0].abs() * 0.5 * width * fx / za).clamp_min(1.0)
+        sy = (scales[:, 1].abs() * 0.5 * height * fy / za).clamp_min(1.0)
+        ov = opacities.clamp_min(0.0) * valid.to(opacities.dtype)
+        n = means.shape[0]
+        acc = torch.zeros((height, 4 * width), dtype=means.dtype, device=means.device)
+        for a, b in _chunks(n, width, height):
+            _, _, ex, ey = _factors(px[a:b], py[a:b], sx[a:b], sy[a:b], width, height)
+            v = torch.cat([torch.ones_like(za[a:b, None]), col[a:b]], dim=1)  # (G, 4)
+            acc += ey.t() @ ((ov[a:b, None] * v)[:, :, None] * ex[:, None, :]).reshape(b - a, 4 * width)
+        acc = acc.view(height, 4, width).permute(1, 0, 2)
+        Wt, C = acc[0], acc[1:4].permute(1, 2, 0)
+        bg = torch.as_tensor(background, dtype=means.dtype, device=means.device)
+        x = ((bg.view(1, 1, 3) + C) / (1.0 + Wt)[..., None]).clamp(0.0, 1.0)
+        if exposure is not None:
+            E = exposure.to(dtype=means.dtype, device=means.device)
+            x = x[..., 0:1] * E[:, 0] + x[..., 1:2] * E[:, 1] + x[..., 2:3] * E[:, 2] + E[:, 3]
+        e = (x - target.to(dtype=means.dtype, device=means.device)).abs().sum(-1) / 3.0
+        m = e / (1.0 + Wt)  # (H, W)
+        err = torch.zeros((n,), dtype=means.dtype, device=means.device)
+        for a, b in _chunks(n, width, height):
+            _, _, ex, ey = _factors(px[a:b], py[a:b], sx[a:b], sy[a:b], width, height)
+            err[a:b] = ov[a:b] * torch.einsum("gy,yx,gx->g", ey, m, ex)
+    return err

@@ -18,6 +18,7 @@
 // gr_eval_views is the same schedule without a backward: per view gr_fwd_render (saved sums only) and gr_eval_view, with a
 // partial-sum workspace per render stream; it writes nothing but those workspaces and the caller's metrics.
 // gr_contrib_views is gr_eval_views with gr_contrib_view in place of gr_eval_view: every view into the caller's one peak buffer.
+// gr_error_views is gr_contrib_views with gr_error_view against views[j].target_rgb: every view into the caller's one err buffer.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -85,6 +86,7 @@ struct StreamWs {  // one render stream's buffers
   Buf bins, scratch, ws, saved;
   Buf eval;                      // gr_eval_views: the view metrics' partial sums
   Buf contrib;                   // gr_contrib_views: the pairs' peak blend weights
+  Buf error;                     // gr_error_views: the pairs' blend-weighted error sums
   Buf cam;                       // gr_executor_camera_grads: a batch's camera-gradient partials
   std::vector<Buf> sums, sums3;  // one per view of a reduction batch (sums3: the depth-loss path's depth sums)
 };
@@ -126,12 +128,12 @@ static gr_status fit_views_on_device(gr_executor* ex, const gr_fit_config* cfg, 
                                      int n, const float* means, const float* scales, const float* colors, int color_dim,
                                      const float* opacities, float w_sil, float w_depth, float g_scale, float w_dssim,
                                      float* losses, float* const* acc, void* stream, float* metrics = nullptr,
-                                     float* peak = nullptr);
+                                     float* peak = nullptr, float* err = nullptr);
 static gr_status enqueue_views(gr_executor* ex, const gr_fit_config* cfg, int num_views, const gr_fit_target* views, int n,
                                const float* means, const float* scales, const float* colors, int color_dim,
                                const float* opacities, float w_sil, float w_depth, float g_scale, float w_dssim, float* losses,
                                float* const* acc, const Sched& sc, const std::vector<hipStream_t>& st, hipStream_t prep,
-                               bool depth, int nslots, int& ngroups, float* metrics, float* peak);
+                               bool depth, int nslots, int& ngroups, float* metrics, float* peak, float* err);
 
 extern "C" {
 
@@ -170,6 +172,7 @@ void gr_executor_destroy(gr_executor* ex) {
     w.saved.release();
     w.eval.release();
     w.contrib.release();
+    w.error.release();
     w.cam.release();
     for (auto& b : w.sums) b.release();
     for (auto& b : w.sums3) b.release();
@@ -292,15 +295,40 @@ gr_status gr_contrib_views(gr_executor* ex, const gr_fit_config* cfg, int num_vi
   return st;
 }
 
+gr_status gr_error_views(gr_executor* ex, const gr_fit_config* cfg, int num_views, const gr_fit_target* views, int n,
+                         const float* means, const float* scales, const float* colors, int color_dim,
+                         const float* opacities, float* err, void* stream) {
+  if (!ex || !cfg || (num_views > 0 && (!views || !err)))
+    return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, "gr_error_views: null argument");
+  if (cfg->num_streams < 1 || cfg->prep_ahead < 1 || cfg->prep_group < 1 || cfg->prep_group > GR_PREPARE_MAX_VIEWS ||
+      cfg->prep_first < 1 || cfg->prep_first > GR_PREPARE_MAX_VIEWS)
+    return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, "gr_error_views: configuration out of range");
+  if (cfg->caps) return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, "gr_error_views: device-side sizing (caps) is not supported");
+  if (num_views <= 0 || n <= 0) return GR_OK;
+  for (int j = 0; j < num_views; ++j)
+    if (!views[j].target_rgb) return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, "gr_error_views: null target");
+  gr_fit_config c = *cfg;  // no reductions: the batch settings are ignored
+  c.reduce_batch = 1;
+  c.reduce_tail = 0;
+  int prev_dev = 0;
+  GR_EXEC_TRY(hipGetDevice(&prev_dev));
+  GR_EXEC_TRY(hipSetDevice(ex->device));
+  const gr_status st = fit_views_on_device(ex, &c, num_views, views, n, means, scales, colors, color_dim, opacities, 0.0f, 0.0f,
+                                           1.0f, 0.0f, nullptr, nullptr, stream, nullptr, nullptr, err);
+  (void)hipSetDevice(prev_dev);
+  return st;
+}
+
 }  // extern "C"
 
 static gr_status fit_views_on_device(gr_executor* ex, const gr_fit_config* cfg, int num_views, const gr_fit_target* views,
                                      int n, const float* means, const float* scales, const float* colors, int color_dim,
                                      const float* opacities, float w_sil, float w_depth, float g_scale, float w_dssim,
-                                     float* losses, float* const* acc, void* stream, float* metrics, float* peak) {
+                                     float* losses, float* const* acc, void* stream, float* metrics, float* peak,
+                                     float* err) {
   // metrics: gr_eval_views' form (no losses, accumulators or statistics: per view the render and gr_eval_view);
-  // peak: gr_contrib_views' (the same with gr_contrib_view)
-  const bool fwd_only = metrics || peak;
+  // peak: gr_contrib_views' (the same with gr_contrib_view); err: gr_error_views' (with gr_error_view)
+  const bool fwd_only = metrics || peak || err;
   const bool depth = !fwd_only && views[0].target_depth != nullptr;
   const Sched sc = schedule(num_views, *cfg);
   const int ns = sc.ns;
@@ -377,7 +405,8 @@ static gr_status fit_views_on_device(gr_executor* ex, const gr_fit_config* cfg, 
       (void)hipStreamSynchronize(prep);
   };
   const gr_status status = enqueue_views(ex, cfg, num_views, views, n, means, scales, colors, color_dim, opacities, w_sil,
-                                         w_depth, g_scale, w_dssim, losses, acc, sc, st, prep, depth, nslots, ngroups, metrics, peak);
+                                         w_depth, g_scale, w_dssim, losses, acc, sc, st, prep, depth, nslots, ngroups, metrics, peak,
+                                         err);
   join();
   return status;
 }
@@ -386,8 +415,8 @@ static gr_status enqueue_views(gr_executor* ex, const gr_fit_config* cfg, int nu
                                const float* means, const float* scales, const float* colors, int color_dim,
                                const float* opacities, float w_sil, float w_depth, float g_scale, float w_dssim, float* losses,
                                float* const* acc, const Sched& sc, const std::vector<hipStream_t>& st, hipStream_t prep,
-                               bool depth, int nslots, int& ngroups, float* metrics, float* peak) {
-  const bool fwd_only = metrics || peak;  // gr_eval_views / gr_contrib_views: no backward, no reductions
+                               bool depth, int nslots, int& ngroups, float* metrics, float* peak, float* err) {
+  const bool fwd_only = metrics || peak || err;  // gr_eval_views / gr_contrib_views / gr_error_views: no backward, no reductions
   const int ns = sc.ns;
   const bool sized = cfg->caps != nullptr;  // device-side sizing: the plans are capacities, nothing to wait for
   const size_t geom_bytes = gr_geom_bytes(n);
@@ -503,6 +532,14 @@ static gr_status enqueue_views(gr_executor* ex, const gr_fit_config* cfg, int nu
       GR_EXEC_CALL(gr_fwd_render(&v, n, &plan, geom[j], bins, W.bins.cap, scratch, W.scratch.cap, nullptr, nullptr,
                                  nullptr, (float*)W.saved.p, s));
       GR_EXEC_CALL(gr_contrib_view(&v, n, &plan, geom[j], bins, (const float*)W.saved.p, peak, W.contrib.p, W.contrib.cap, s));
+    } else if (err) {
+      // gr_error_views: the saved sums only, then the view's blend-weighted error into the one buffer (atomic maxima)
+      GR_EXEC_TRY(W.saved.fit(gr_saved_floats(&v) * sizeof(float), s));
+      GR_EXEC_TRY(W.error.fit(gr_error_ws_bytes(&v, n, &plan), s));
+      GR_EXEC_CALL(gr_fwd_render(&v, n, &plan, geom[j], bins, W.bins.cap, scratch, W.scratch.cap, nullptr, nullptr,
+                                 nullptr, (float*)W.saved.p, s));
+      GR_EXEC_CALL(gr_error_view(&v, n, &plan, geom[j], bins, (const float*)W.saved.p, views[j].target_rgb, err, W.error.p,
+                                 W.error.cap, s));
     } else if (ssim) {
       // the saved sums only (no image: the D-SSIM forward stages the colours from them); sums3 with a depth target
       GR_EXEC_TRY(W.saved.fit(gr_saved_floats(&v) * sizeof(float), s));

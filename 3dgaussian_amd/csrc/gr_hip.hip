@@ -4035,6 +4035,101 @@ __global__ __launch_bounds__(256) void k_contrib_gather(int n, const Cnt2* __res
   atomicMax(peak + i, __float_as_uint(m));
 }
 
+// ------------------------------------------------------------------------------------------------
+// Blend-weighted pixel error per Gaussian (gr_error_view): err[i] = max(err[i], sum_p w_i(p) r(p) e(p)) over the
+// pixels of Gaussian i's kept pairs, r = 1 / (1 + W) and e(p) the mean absolute difference of the three channels
+// between the view's colour (write_pixel's expression on the saved sums: a target equal to that image gives e = 0
+// exactly) and the target.  The blend weights w r and the background's r sum to one, so the view's L1 error is
+// partitioned exactly among the Gaussians and the background.
+// k_error_view: k_contrib_view's mapping and factors.  The tile's m(p) = r(p) e(p) is staged once in LDS (0 outside
+// the image); one lane per pair forms o sum_y ey[y] sum_x ex[x] m(x, y): per row two packed f32 FMA chains over the
+// even and the odd pixel pairs (x ascending in each), their lanes added as (lo + hi), then one FMA into the pair's
+// sum, y ascending: a fixed order.  No cross-lane step; the pair's value goes to vals[k].
+__global__ __launch_bounds__(256, 4) void k_error_view(ViewK v, const int4* __restrict__ items, const int* __restrict__ num_items,
+                                                    const int* __restrict__ pairs, const float4* __restrict__ rec,
+                                                    const float4* __restrict__ saved4, const float* __restrict__ target,
+                                                    float* __restrict__ vals) {
+  __shared__ __attribute__((aligned(16))) float m[TP];
+  const int nfull = num_items[1];  // the non-empty items are listed first
+  if ((int)blockIdx.x >= nfull) return;
+  const int4 it = items[xcd_item(blockIdx.x, nfull)];
+  const int tile = it.x >> 1, k0 = it.y, k1 = it.z;
+  const int tx = tile % v.tiles_x, ty = tile / v.tiles_x;
+  const int tid = threadIdx.x;
+  {
+    const int x = tx * T + (tid & (T - 1)), y = ty * T + (tid >> 4);
+    float mv = 0.0f;
+    if (x < v.W && y < v.H) {
+      const size_t p = (size_t)y * v.W + x;
+      const float4 s = saved4[p];
+      const float den = 1.0f + s.x;
+      const float d0 = clamp01((view_bg(v, 0) + s.y) / den) - target[3 * p + 0];
+      const float d1 = clamp01((view_bg(v, 1) + s.z) / den) - target[3 * p + 1];
+      const float d2 = clamp01((view_bg(v, 2) + s.w) / den) - target[3 * p + 2];
+      mv = (1.0f / den) * (((fabsf(d0) + fabsf(d1)) + fabsf(d2)) / 3.0f);
+    }
+    m[tid] = mv;
+  }
+  __syncthreads();
+  for (int k = k0 + tid; k < k1; k += 256) {
+    // m is read from LDS in every round (k_contrib_view: hoisted, the 256 values take every register of the SIMD)
+    asm volatile("" ::: "memory");
+    const int g = pairs[k];
+    const float4 a = rec[(size_t)REC4 * g];
+    const float o = rec[(size_t)REC4 * g + 1].x;
+    f32x2_t ex[T / 2];
+#pragma unroll
+    for (int j = 0; j < T / 2; ++j) {
+      const float dx0 = ((float)(tx * T + 2 * j) + 0.5f) - a.x, dx1 = ((float)(tx * T + 2 * j + 1) + 0.5f) - a.x;
+      ex[j] = f32x2_t{__builtin_amdgcn_exp2f((dx0 * a.z) * dx0), __builtin_amdgcn_exp2f((dx1 * a.z) * dx1)};
+    }
+    float sum = 0.0f;
+#pragma unroll
+    for (int y = 0; y < T; ++y) {
+      const float dy = ((float)(ty * T + y) + 0.5f) - a.y;
+      const float ey = o * __builtin_amdgcn_exp2f((dy * a.w) * dy);
+      f32x2_t s0 = {0.0f, 0.0f}, s1 = {0.0f, 0.0f};
+#pragma unroll
+      for (int j = 0; j < T / 4; ++j) {
+        const float4 u = *reinterpret_cast<const float4*>(m + y * T + 4 * j);
+        s0 = __builtin_elementwise_fma(ex[2 * j], f32x2_t{u.x, u.y}, s0);
+        s1 = __builtin_elementwise_fma(ex[2 * j + 1], f32x2_t{u.z, u.w}, s1);
+      }
+      const f32x2_t st = s0 + s1;
+      sum = fmaf(ey, st.x + st.y, sum);
+    }
+    vals[k] = sum;
+  }
+}
+
+// One lane per Gaussian: the sum of its pairs' values, its core pairs then its tail pairs in emission order through
+// pos_of (k_contrib_gather's walk; a fixed order, so the sum is deterministic), and one unsigned atomic maximum on the
+// float's bits into err[i] (a sum of non-negative terms is non-negative).  A Gaussian without pairs is not touched.
+__global__ __launch_bounds__(256) void k_error_gather(int n, const Cnt2* __restrict__ offsets, const int* __restrict__ pos_of,
+                                                      const float* __restrict__ vals, unsigned* __restrict__ err) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const Cnt2 o0 = offsets[i], o1 = offsets[i + 1];
+  const unsigned cc = o1.c() - o0.c(), tc = o1.t() - o0.t();
+  if (cc + tc == 0) return;
+  const int* pc = pos_of + o0.c();
+  const int* pt = pos_of + (size_t)offsets[n].c() + o0.t();
+  float s = 0.0f;
+  // four index -> value loads in flight, added in emission order (a sum's order is fixed: the compiler would keep one)
+  auto walk = [&](const int* __restrict__ p, unsigned c) {
+    unsigned j = 0;
+    for (; j + 4 <= c; j += 4) {
+      const int i0 = p[j], i1 = p[j + 1], i2 = p[j + 2], i3 = p[j + 3];
+      const float v0 = vals[i0], v1 = vals[i1], v2 = vals[i2], v3 = vals[i3];
+      s = (((s + v0) + v1) + v2) + v3;
+    }
+    for (; j < c; ++j) s += vals[p[j]];
+  };
+  walk(pc, cc);
+  walk(pt, tc);
+  atomicMax(err + i, __float_as_uint(s));
+}
+
 
 // Chain rule of up to GR_REDUCE_MAX_VIEWS views' gathered sums: one lane per Gaussian; the crw waves of a
 // Gaussian group take views u, u + crw, ... (crw = 4 from three views, else the view count, so that no
@@ -7131,6 +7226,40 @@ gr_status gr_contrib_view(const gr_view* v, int n, const gr_plan* plan, const vo
   GR_HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(k_contrib_gather, dim3(blocks_for(n)), dim3(256), 0, s, n, (const Cnt2*)c.g.offsets,
                      (const int*)c.b.pos_of, (const float*)ws, (unsigned*)peak);
+  GR_HIP_TRY(hipGetLastError());
+  return GR_OK;
+}
+
+// Blend-weighted pixel error: one float per pair (k_error_view's values by sorted position).
+size_t gr_error_ws_bytes(const gr_view* v, int n, const gr_plan* plan) {
+  if (!v || !plan || n <= 0 || plan->num_pairs <= 0) return 0;
+  return align_up((size_t)plan->num_pairs * sizeof(float));
+}
+
+gr_status gr_error_view(const gr_view* v, int n, const gr_plan* plan, const void* geom, const void* bins, const float* saved,
+                        const float* target_rgb, float* err, void* ws, size_t ws_bytes, void* stream) {
+  gr_status st = check_view(v);
+  if (st != GR_OK) return st;
+  if (tile_of(v) != T)
+    return set_error(GR_ERR_INVALID_ARGUMENT, "gr_error_view: 32-pixel tiles (gr_view.tile = 32): 16-pixel tiles only");
+  if (v->rows > 0) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_error_view: a band of tile rows (gr_view.rows): whole views only");
+  if (v->device_counts)
+    return set_error(GR_ERR_INVALID_ARGUMENT, "gr_error_view: device-sized views (device_counts = 1) are not supported");
+  if (!plan) return set_error(GR_ERR_INVALID_ARGUMENT, "plan is null");
+  if (plan->num_pairs < 0) return set_error(GR_ERR_OVERFLOW, "pair count overflows int32");
+  if (n < 0) return set_error(GR_ERR_INVALID_ARGUMENT, "n must be >= 0");
+  if (!geom || !bins || !saved || !target_rgb || !err) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_error_view: null pointer");
+  if (n == 0 || plan->num_pairs == 0) return GR_OK;  // no pair: every value stays
+  if (!ws) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_error_view: null pointer");
+  if (ws_bytes < gr_error_ws_bytes(v, n, plan)) return set_error(GR_ERR_WORKSPACE, "gr_error_view: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const ViewCtx c = view_ctx(v, n, plan, geom, bins, nullptr, nullptr);
+  hipLaunchKernelGGL(k_error_view, dim3((unsigned)c.cap), dim3(256), 0, s, c.vk, (const int4*)c.b.items,
+                     (const int*)c.b.num_items, (const int*)c.b.pairs, (const float4*)c.g.rec, (const float4*)saved,
+                     target_rgb, (float*)ws);
+  GR_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_error_gather, dim3(blocks_for(n)), dim3(256), 0, s, n, (const Cnt2*)c.g.offsets,
+                     (const int*)c.b.pos_of, (const float*)ws, (unsigned*)err);
   GR_HIP_TRY(hipGetLastError());
   return GR_OK;
 }

@@ -337,26 +337,76 @@ def densify_by_gradient(params: dict, gsum: torch.Tensor, seen: torch.Tensor, gr
         if idx.numel() > room:  # a stable sort: equal averages keep their index order
             first = torch.sort(avg[idx], descending=True, stable=True).indices[:room]
             idx = torch.sort(idx[first]).values
-        s = torch.nn.functional.softplus(scales_raw[idx]) + 1e-3
-        split = s[:, :2].max(dim=1).values > split_scale
-        clones, parents, sp = idx[~split], idx[split], s[split]
-        survive = keep.clone()
-        survive[parents] = False
-        k2 = 2 * int(parents.numel())
-        if noise is not None:
-            z = noise[:k2].to(device=dev, dtype=means.dtype)
-        else:
-            z = torch.randn((k2, 3), generator=generator, device=dev, dtype=means.dtype)
-        two = parents.repeat_interleave(2)
-        child_means = means[two] + sp.repeat_interleave(2, dim=0) * z
-        # softplus^-1 of s / 1.6 (torch's softplus is the identity above its threshold of 20)
-        a = (sp / 1.6 - 1e-3).clamp_min(1e-6)
-        child_raw = torch.where(a > 20.0, a, torch.log(torch.expm1(a))).repeat_interleave(2, dim=0)
-        out = {"means": torch.cat([means[survive], means[clones], child_means]),
-               "scales_raw": torch.cat([scales_raw[survive], scales_raw[clones], child_raw]),
-               "opacities_raw": torch.cat([op_raw[survive], op_raw[clones], op_raw[two]]),
-               key: torch.cat([col[survive], col[clones], col[two]])}
+        return _clone_split(means, scales_raw, op_raw, key, col, keep, idx, split_scale, generator, noise)
+
+
+def _clone_split(means, scales_raw, op_raw, key: str, col, keep, idx, split_scale: float, generator, noise) -> dict:
+    """Step 3 of densify_by_gradient, shared with densify_by_error: of the candidate rows ``idx`` (ascending, all kept)
+    clone the small and split the large, and assemble the output rows in the documented order."""
+    dev = means.device
+    s = torch.nn.functional.softplus(scales_raw[idx]) + 1e-3
+    split = s[:, :2].max(dim=1).values > split_scale
+    clones, parents, sp = idx[~split], idx[split], s[split]
+    survive = keep.clone()
+    survive[parents] = False
+    k2 = 2 * int(parents.numel())
+    if noise is not None:
+        z = noise[:k2].to(device=dev, dtype=means.dtype)
+    else:
+        z = torch.randn((k2, 3), generator=generator, device=dev, dtype=means.dtype)
+    two = parents.repeat_interleave(2)
+    child_means = means[two] + sp.repeat_interleave(2, dim=0) * z
+    # softplus^-1 of s / 1.6 (torch's softplus is the identity above its threshold of 20)
+    a = (sp / 1.6 - 1e-3).clamp_min(1e-6)
+    child_raw = torch.where(a > 20.0, a, torch.log(torch.expm1(a))).repeat_interleave(2, dim=0)
+    out = {"means": torch.cat([means[survive], means[clones], child_means]),
+           "scales_raw": torch.cat([scales_raw[survive], scales_raw[clones], child_raw]),
+           "opacities_raw": torch.cat([op_raw[survive], op_raw[clones], op_raw[two]]),
+           key: torch.cat([col[survive], col[clones], col[two]])}
     return {k: torch.nn.Parameter(v.contiguous()) for k, v in out.items()}
+
+
+def densify_by_error(params: dict, err: torch.Tensor, threshold: float, split_scale: float, max_gaussians: int,
+                     prune_opacity: float, max_new: Optional[int] = None, generator: Optional[torch.Generator] = None,
+                     noise: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None,
+                     report: Optional[dict] = None) -> dict:
+    """Error-driven density control (an extension) from each Gaussian's blend-weighted pixel error
+    (ViewShardedFitter.error_state: the largest, over the training views, of its share sum_p b_i(p) e(p) of the view's
+    L1 error, b = w / (1 + W) the blend weight), on the tensors' device:
+      1. prune as densify_and_prune (or the rows of ``keep`` when given);
+      2. candidates: kept rows with err > threshold, at most min(max_gaussians - kept, max_new) of them (each adds one
+         row net; max_new None: no second cap), the largest err first, ties to the lower index;
+      3. densify_by_gradient's clone / split step on them (_clone_split): the same output row order and ``noise``
+         contract.
+    ``report`` (a dict) receives the numbers of ``clones`` and ``splits`` made."""
+    with torch.no_grad():
+        means, scales_raw, op_raw = params["means"].detach(), params["scales_raw"].detach(), params["opacities_raw"].detach()
+        key = "sh_raw" if "sh_raw" in params else "colors_raw"
+        col = params[key].detach()
+        op = torch.sigmoid(op_raw)
+        if keep is not None:
+            keep = _keep_mask(keep, op)
+        else:
+            keep = op > prune_opacity
+            if int(keep.sum()) < 64:
+                top_keep = torch.topk(op, k=min(64, op.shape[0]), largest=True).indices
+                keep = torch.zeros_like(keep, dtype=torch.bool)
+                keep[top_keep] = True
+        err = err.to(means.device)
+        if tuple(err.shape) != tuple(op.shape):
+            raise ValueError(f"err: expected shape {tuple(op.shape)}, got {tuple(err.shape)}")
+        idx = torch.nonzero(keep & (err > threshold)).flatten()
+        room = max(0, max_gaussians - int(keep.sum()))
+        if max_new is not None:
+            room = min(room, max(0, int(max_new)))
+        if idx.numel() > room:  # a stable sort: equal errors keep their index order
+            first = torch.sort(err[idx], descending=True, stable=True).indices[:room]
+            idx = torch.sort(idx[first]).values
+        if report is not None:
+            s = torch.nn.functional.softplus(scales_raw[idx]) + 1e-3
+            report["splits"] = int((s[:, :2].max(dim=1).values > split_scale).sum())
+            report["clones"] = int(idx.numel()) - report["splits"]
+        return _clone_split(means, scales_raw, op_raw, key, col, keep, idx, split_scale, generator, noise)
 
 
 def spatial_order(params: dict) -> dict:
@@ -585,7 +635,7 @@ class ViewShardedFitter:
         self._rows_cache = {}  # estimated pairs per tile row by (view, tile, Gaussians, re-sort epoch)
         self._cam_ws = {}  # render stream -> its gr_camera_grads_sums workspace (_camera_ws)
         self._cam_pin = None  # pinned host copy of the step's camera-gradient rows (_camera_step_fused)
-        # (density_report / contribution_report exist only once densify_and_prune has filled them)
+        # (density_report / contribution_report / error_report exist only once densify_and_prune has filled them)
         self.density_stats = bool(density_stats)
         self._stats = []  # one (n, 2) buffer per render stream: [sum of gradient norms, seeing views]
         if self.density_stats and dev.type == "cuda":
@@ -2103,8 +2153,8 @@ class ViewShardedFitter:
 
     def _exec_views(self, fn: str, m, s, c, o, gvs, targets, out) -> None:
         """One native executor call over views that are only rendered: gr_eval_views (the views' metrics against
-        ``targets`` into ``out`` (len(gvs), 3)) or gr_contrib_views (targets None: every view's peak blend weights into
-        the one ``out``)."""
+        ``targets`` into ``out`` (len(gvs), 3)), gr_contrib_views (targets None: every view's peak blend weights into
+        the one ``out``) or gr_error_views (every view's blend-weighted error against ``targets`` into the one ``out``)."""
         device = m.device
         arr = (tr._native.GrFitTarget * len(gvs))()
         for j, gv in enumerate(gvs):
@@ -2233,25 +2283,97 @@ class ViewShardedFitter:
             peak = canon
         return peak
 
+    # ---- error (blend-weighted pixel error per Gaussian) --------------------------------------------------------
+    def _error_direct(self, m, s, c, o, gvs, targets, err) -> None:
+        """The Python schedule of gr_error_views' calls (_view_loop): per view forward_native (saved sums only) +
+        error_view_native against ``targets[j]``, every view into the one ``err``."""
+        def body(j, take):
+            pv = take(j)
+            _, _, _, rs = tr.forward_native(m, s, c, o, pv.gv, pv, images=False)
+            tr.error_view_native(rs, pv, targets[j], err)
+
+        self._view_loop(m.device, len(gvs), self._preparer(m, s, c, o, gvs.__getitem__, len(gvs)), body)
+
+    def error_state(self, cams: Optional[list] = None, targets: Optional[list] = None) -> torch.Tensor:
+        """Per Gaussian in canonical order (as canonical_params), its blend-weighted pixel error: the maximum over the
+        views (default: the training views; else ``cams`` and ``targets``, (H, W, 3) images, both or neither) of
+        sum_p b_i(p) e(p), b = w / (1 + W) the Gaussian's blend weight and e the mean absolute colour error of the
+        pixel.  The blend weights and the background's 1 / (1 + W) sum to one, so per view the values and the
+        background's share add up to the view's summed L1 error: the unit is pixels x colour error.  (N,) float32 on
+        the parameters' device.
+        The views are rendered as evaluate() renders them.  A collective: view i belongs to rank i % world, the ranks
+        meet in one all-reduce (MAX: exact), every rank returns the same tensor.  On the HIP device through
+        gr_error_view (the native executor's gr_error_views where the fit step uses it, else a Python schedule of the
+        same calls), under evaluate()'s conditions for its HIP kernel (it raises when they do not hold: there is no
+        other form on that device); on other devices cpu_renderer.blend_error, which with exposure=True and the
+        default views compares E_v (x, 1) with the target as the fit's photometric term does (caller-passed cameras
+        have no exposure).  Collected on demand, nothing during steps.  Changes nothing of the fit."""
+        self.graph_sync()
+        if (cams is None) != (targets is None):
+            raise ValueError("error_state: pass both cams and targets, or neither (the training views)")
+        own = cams is None
+        if own:
+            cams, targets = self.cams, self.targets
+        if len(cams) != len(targets):
+            raise ValueError(f"error_state: {len(cams)} cameras for {len(targets)} targets")
+        device = self.params["means"].device
+        n = int(self.params["means"].shape[0])
+        mine = list(range(self.rank, len(cams), self.world))
+        err = torch.zeros((n,), dtype=torch.float32, device=device)
+        with torch.no_grad():
+            if mine and n > 0:
+                m, s, c, o = (t.detach().float().contiguous() for t in self._eval_activations(device))
+                if device.type == "cuda":
+                    tg = [targets[i] for i in mine]
+                    if not self._eval_native_ok(device, tg):
+                        raise ValueError("error_state on the HIP device needs the HIP render op, float32 parameters and "
+                                         f"contiguous float32 targets of shape {(self.height, self.width, 3)} on {device}: "
+                                         "gr_error_view reads them through raw pointers and has no other form")
+                    gvs = [self._eval_view(cams[i], device) for i in mine]
+                    if self._native_exec() and GATHER:
+                        self._exec_views("gr_error_views", m, s, c, o, gvs, tg, err)
+                    else:
+                        self._error_direct(m, s, c, o, gvs, tg, err)
+                else:
+                    from . import cpu_renderer
+                    E = self._expo.detach() if (own and self.exposure) else None
+                    for i in mine:
+                        err = torch.maximum(err, cpu_renderer.blend_error(
+                            m, s, c, o, cams[i].view, cams[i].proj, self.width, self.height, targets[i],
+                            self._background(device), exposure=None if E is None else E[i]))
+        if self.world > 1:
+            dist.all_reduce(err, op=dist.ReduceOp.MAX, group=self.group)
+        if self.perm is not None:
+            canon = torch.empty_like(err)
+            canon[self.perm] = err
+            err = canon
+        return err
+
     def densify_and_prune(self, max_gaussians: int, densify_ratio: float, prune_opacity: float,
                           on_device: Optional[bool] = None, mode: str = "opacity", grad_threshold: float = 0.0002,
                           split_scale: float = 0.01, prune_mode: str = "opacity",
-                          prune_contribution: float = 1.0 / 510.0) -> None:
+                          prune_contribution: float = 1.0 / 510.0, error_threshold: float = 0.0) -> None:
         """on_device (default: N >= DEVICE_DENSIFY_MIN): the device-side rule with a device generator
         (densify_and_prune_device); otherwise the host rule with the stub's CPU random stream.
         mode "gradient" (a fitter with density_stats): densify_by_gradient on the statistics since the last call, on
         the parameters' device with its generator (densify_ratio <= 0: prune only); the same rank-0-decides flow.
         Either mode leaves the statistics zeroed at the new size.
+        mode "error" (any fitter: no density_stats, nothing collected during steps): densify_by_error on error_state(),
+        taken here once, on the parameters' device with its generator: the kept Gaussians with err > error_threshold,
+        the largest first, at most int(kept * densify_ratio) of them (densify_ratio <= 0: prune only).  Fills
+        self.error_report (n, p50 / p90 / p99 / max of err, the count over the threshold; the clones and splits made
+        on the rank that decides, rank 0).
         prune_mode "contribution": the rows that survive are prune_by_contribution(contribution_state(),
         prune_contribution) instead of the opacity rule's (whichever densify mode is active; prune_opacity is then only
         counted for the report).  The default threshold 1 / 510 bounds the change of any training pixel by half an
         8-bit level (t / (1 - t) = 1 / 509) per removed Gaussian.  Fills self.contribution_report."""
-        if mode not in ("opacity", "gradient"):
-            raise ValueError(f"densify mode must be 'opacity' or 'gradient', got {mode!r}")
+        if mode not in ("opacity", "gradient", "error"):
+            raise ValueError(f"densify mode must be 'opacity', 'gradient' or 'error', got {mode!r}")
         if prune_mode not in ("opacity", "contribution"):
             raise ValueError(f"prune mode must be 'opacity' or 'contribution', got {prune_mode!r}")
         self.graph_sync()
         state = self.density_state() if mode == "gradient" else None  # (a collective: before rank 0 decides)
+        err = self.error_state() if mode == "error" else None  # (a collective too)
         n_now = int(self.params["means"].shape[0])
         keep = None
         if prune_mode == "contribution":
@@ -2278,6 +2400,13 @@ class ViewShardedFitter:
             self.density_report = {"seen": int(avg.numel()), "n": n_now, "p50": qs[0], "p90": qs[1], "p99": qs[2],
                                    "max": float(avg.max()) if avg.numel() else 0.0,
                                    "over": int((avg >= grad_threshold).sum())}
+        if mode == "error":
+            on_device = True
+            ec = err.float().cpu()
+            qs = torch.quantile(ec, torch.tensor([0.5, 0.9, 0.99])).tolist() if ec.numel() else [0.0] * 3
+            self.error_report = {"n": n_now, "p50": qs[0], "p90": qs[1], "p99": qs[2],
+                                 "max": float(ec.max()) if ec.numel() else 0.0, "threshold": float(error_threshold),
+                                 "over": int((ec > error_threshold).sum()), "clones": 0, "splits": 0}
         if on_device is None:
             on_device = self.params["means"].device.type == "cuda" and n_now >= DEVICE_DENSIFY_MIN
         if on_device and self._dgen is None:
@@ -2288,6 +2417,12 @@ class ViewShardedFitter:
             if mode == "gradient":
                 newp = densify_by_gradient(base, state[0], state[1], grad_threshold if densify_ratio > 0.0 else math.inf,
                                            split_scale, max_gaussians, prune_opacity, self._dgen, keep=keep)
+            elif mode == "error":
+                op = torch.sigmoid(base["opacities_raw"].detach())
+                kept = int(keep.sum()) if keep is not None else max(int((op > prune_opacity).sum()), min(64, n_now))
+                newp = densify_by_error(base, err, error_threshold, split_scale, max_gaussians, prune_opacity,
+                                        int(kept * densify_ratio) if densify_ratio > 0.0 else 0, self._dgen, keep=keep,
+                                        report=self.error_report)
             elif on_device:
                 newp = densify_and_prune_device(base, max_gaussians, densify_ratio, prune_opacity, self._dgen, keep=keep)
             else:
@@ -2374,10 +2509,16 @@ def main(argv=None) -> None:
                     help="contribution mode: the peak blend weight t at or below which a Gaussian is pruned.  Removing one "
                          "such Gaussian moves no training pixel by more than t / (1 - t); the default 1/510 makes that "
                          "1/509, half an 8-bit level.  A bound per removed Gaussian, not a measured quality result")
-    ap.add_argument("--densify_mode", choices=("opacity", "gradient"), default="opacity",
+    ap.add_argument("--densify_mode", choices=("opacity", "gradient", "error"), default="opacity",
                     help="opacity: the reference's rule (duplicate the most opaque Gaussians); gradient: adaptive density "
                          "control from each Gaussian's accumulated screen-space positional gradient (clone small, split "
-                         "large, at most --max_gaussians)")
+                         "large, at most --max_gaussians); error: the same clone / split step on the Gaussians that own "
+                         "the most L1 error, each pixel's error shared out by the blend weights w / (1 + W) and the "
+                         "largest view taken, measured once per densify (nothing is collected during steps)")
+    ap.add_argument("--densify_error_threshold", type=float, default=0.0,
+                    help="error mode: only Gaussians whose blend-weighted error (pixels x colour error, largest view) "
+                         "exceeds this are candidates.  The default 0 leaves the choice to the ranking and "
+                         "--densify_ratio (the int(kept x ratio) largest); no default threshold has been measured")
     ap.add_argument("--densify_grad_threshold", type=float, default=0.0002,
                     help="gradient mode: densify where the mean NDC-position gradient norm per seeing view reaches this; "
                          "the default is the splatting trainers' convention, not measured for this renderer's "
@@ -2534,7 +2675,8 @@ def main(argv=None) -> None:
                                      args.prune_opacity, mode=args.densify_mode,
                                      grad_threshold=args.densify_grad_threshold,
                                      split_scale=args.densify_percent_dense * extent, prune_mode=args.prune_mode,
-                                     prune_contribution=args.prune_contribution)
+                                     prune_contribution=args.prune_contribution,
+                                     error_threshold=args.densify_error_threshold)
             if rank == 0 and args.prune_mode == "contribution":
                 r = fitter.contribution_report
                 print(f"prune at iter {it + 1}: peak blend weight of {r['n']} Gaussians: p1={r['p1']:.3e} p10={r['p10']:.3e} "
@@ -2546,6 +2688,11 @@ def main(argv=None) -> None:
                 print(f"densify at iter {it + 1}: avg gradient over {r['seen']} of {r['n']} Gaussians seen: p50={r['p50']:.3e} "
                       f"p90={r['p90']:.3e} p99={r['p99']:.3e} max={r['max']:.3e}, {r['over']} at or over "
                       f"{args.densify_grad_threshold:g}; N -> {fitter.params['means'].shape[0]}")
+            if rank == 0 and args.densify_mode == "error":
+                r = fitter.error_report
+                print(f"densify at iter {it + 1}: blend-weighted error of {r['n']} Gaussians: p50={r['p50']:.3e} "
+                      f"p90={r['p90']:.3e} p99={r['p99']:.3e} max={r['max']:.3e}, {r['over']} over {r['threshold']:g}; "
+                      f"{r['clones']} cloned, {r['splits']} split; N -> {fitter.params['means'].shape[0]}")
     if args.refine_cameras:  # all input views in input order: the training views refined, the held-out ones as given
         all_cams = list(all_cams)
         for i, cam in zip(train, fitter.refined_cameras()):

@@ -924,6 +924,25 @@ def contrib_view_native(rs: RenderState, pv: Prepared, peak) -> None:
                                     ws.numel(), _stream(dev)), "gr_contrib_view")
 
 
+def error_view_native(rs: RenderState, pv: Prepared, target, err) -> None:
+    """gr_error_view on the current stream: ``err`` ((n,) float32 on the device, zeroed by the caller) takes, per
+    Gaussian, the maximum of its value and the Gaussian's blend-weighted pixel error in this view, sum_p w r e: e the mean
+    absolute difference of the three channels between the view's colour (composed from ``rs``'s saved sums) and
+    ``target`` ((H, W, 3) float32 on the device), r = 1 / (1 + W).  ``rs``, ``pv``: as contrib_view_native's.  Calls
+    accumulate across views, in any order and from any streams."""
+    L = _native.lib()
+    dev = rs.saved.device
+    if pv.n != rs.n or pv.gv.width != rs.gv.width or pv.gv.height != rs.gv.height:
+        raise ValueError("prepared view does not match the render state (Gaussian count or image size)")
+    _check_operand(err, (rs.n,), "err", dev)
+    _check_operand(target, (rs.gv.height, rs.gv.width, 3), "target", dev)
+    ws = torch.empty((int(L.gr_error_ws_bytes(ctypes.byref(rs.gv), rs.n, ctypes.byref(rs.plan))),), dtype=torch.uint8,
+                     device=dev)
+    _native.check(L.gr_error_view(ctypes.byref(rs.gv), rs.n, ctypes.byref(rs.plan), _native.ptr(pv.geom),
+                                  _native.ptr(rs.bins), _native.ptr(rs.saved), _native.ptr(target), _native.ptr(err),
+                                  _native.ptr(ws), ws.numel(), _stream(dev)), "gr_error_view")
+
+
 def _grad_background(st: RenderState, background: torch.Tensor, g_out: torch.Tensor) -> torch.Tensor:
     """d(out)/d(bg) = sum_p g_out * [0<=out_r<=1] / (1+W)  (torch_renderer.py:194-196)."""
     HW = st.gv.width * st.gv.height
@@ -1295,5 +1314,5 @@ __all__ = ["Camera", "get_default_device", "perspective", "look_at", "render_gau
            "make_view", "prepare_view", "prepare_native", "Prepared", "forward_native", "backward_native",
            "backward_l1_native", "backward_fit_native", "backward_fit_gather_native", "forward_l1_native", "backward_splat_native", "reduce_views_native",
            "gather_view_native", "reduce_sums_native", "density_stats_native", "camera_grads_sums_native", "eval_view_native",
-           "contrib_view_native",
+           "contrib_view_native", "error_view_native",
            "DEFAULT_CUTOFF", "DEPTH_GRAD_CUTOFF", "DEFAULT_CORE_CUTOFF", "FIT_CUTOFF", "default_cutoff"]

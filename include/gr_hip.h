@@ -541,6 +541,41 @@ gr_status gr_contrib_views(gr_executor* executor, const gr_fit_config* config, i
                            const float* colors, int color_dim, const float* opacities, float* peak /* [n], device */,
                            void* stream);
 
+/* Blend-weighted pixel error per Gaussian, for error-driven densification (an extension; the statistic of Bulo et
+ * al., "Revising Densification in Gaussian Splatting").  With x(p) = clamp((bg + C) / (1 + W)) the view's colour
+ * formed from `saved` exactly as gr_fwd_render / gr_fwd_compose write it (background / background_dev honoured),
+ * t = target_rgb ([H][W][3] float32, device), e(p) = (|x0 - t0| + |x1 - t1| + |x2 - t2|) / 3 and r(p) = 1 / (1 + W(p)):
+ *   err[i] = max(err[i], sum_p w_i(p) r(p) e(p))
+ * over the in-image pixels p of every kept (Gaussian i, tile) pair of the view, core and tail lists alike, w_i(p) as
+ * gr_contrib_view forms it (plain f32 whatever the view's precision mode).  The blend weights w r and the
+ * background's r sum to one at every pixel, so sum_i err_i^v + sum_p r e = sum_p e: the view's L1 error partitioned
+ * among the Gaussians and the background (up to the pixels outside a Gaussian's kept tiles, w < o exp(-cutoff^2 / 2)).
+ * A target equal to the composed image gives e = 0 and every sum 0 exactly.
+ *   - the caller zeroes err ([n] float32, device); calls accumulate the maximum across views.  A Gaussian without
+ *     pairs keeps its value
+ *   - two launches: one workgroup per work item writes each pair's sum into ws (one float per pair) in a fixed order,
+ *     then one lane per Gaussian sums its pairs (core, then tail, in emission order) and issues one unsigned atomic
+ *     maximum on the float's bit pattern: as with gr_contrib_view, several streams and views may share one buffer and
+ *     the result is the same bits in any order
+ *   - refusals as gr_contrib_view's (tile = 32, rows > 0, device_counts = 1, null pointers: GR_ERR_INVALID_ARGUMENT;
+ *     ws shorter than gr_error_ws_bytes: GR_ERR_WORKSPACE; nothing is launched on a refusal); n == 0 or a plan without
+ *     pairs: no-op, nothing launched, ws may be null
+ *   - stream-ordered, no allocation, deterministic */
+size_t gr_error_ws_bytes(const gr_view* v, int n, const gr_plan* plan); /* 0 for a plan without pairs */
+gr_status gr_error_view(const gr_view* v, int n, const gr_plan* plan, const void* geom, const void* bins,
+                        const float* saved, const float* target_rgb, float* err /* [n], device */, void* ws,
+                        size_t ws_bytes, void* stream);
+/* gr_error_view over several views of the same Gaussians: gr_contrib_views' schedule with views[j].target_rgb read
+ * (per view gr_fwd_render keeping the saved sums only, then gr_error_view into the one err buffer, view j on render
+ * stream j % num_streams).  Every view needs a target_rgb; masks and depths are ignored; config->caps must be NULL.
+ * The caller zeroes err.  The executor's accumulators, density statistics and camera rows are left untouched.
+ * Ordered after and before `stream` as gr_fit_views; n == 0 or num_views == 0: no-op.  Bit-identical to per-view
+ * gr_fwd_render + gr_error_view calls in any order. */
+gr_status gr_error_views(gr_executor* executor, const gr_fit_config* config, int num_views,
+                         const gr_fit_target* views, int n, const float* means, const float* scales,
+                         const float* colors, int color_dim, const float* opacities, float* err /* [n], device */,
+                         void* stream);
+
 /* ------------------------------------------------------------------------------------------ */
 /* Legacy uint8 surface (host pointers), replaces gr::render_gaussians (renderer.h:33-39).    */
 /* Semantics of renderer_cpu.cpp: 3-sigma box, w < 1e-5 skip, uint8 round-half-up, A = 255.  */
