@@ -15,10 +15,10 @@
 // must grow is replaced after its stream has drained (rare: the first step, a densify).
 // The schedule (streams, preparation groups, reduction batches) is exactly fit_multiview._views_direct's,
 // so both give bit-identical losses and gradients (tests/test_fit_exec_gpu.py).
-// gr_eval_views is the same schedule without a backward: per view gr_fwd_render (saved sums only) and gr_eval_view, with a
-// partial-sum workspace per render stream; it writes nothing but those workspaces and the caller's metrics.
-// gr_contrib_views is gr_eval_views with gr_contrib_view in place of gr_eval_view: every view into the caller's one peak buffer.
-// gr_error_views is gr_contrib_views with gr_error_view against views[j].target_rgb: every view into the caller's one err buffer.
+// gr_eval_views, gr_contrib_views and gr_error_views are the same schedule without a backward (a render-only pass): per
+// view gr_fwd_render (saved sums only) and the pass's one call (gr_eval_view into the view's row of metrics; gr_contrib_view
+// or gr_error_view, every view into the caller's one buffer), with one pass workspace per render stream; a pass writes
+// nothing but those workspaces and the caller's output.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -84,9 +84,7 @@ struct Buf {
 
 struct StreamWs {  // one render stream's buffers
   Buf bins, scratch, ws, saved;
-  Buf eval;                      // gr_eval_views: the view metrics' partial sums
-  Buf contrib;                   // gr_contrib_views: the pairs' peak blend weights
-  Buf error;                     // gr_error_views: the pairs' blend-weighted error sums
+  Buf pass;                      // a render-only pass's workspace: gr_eval_view's partial sums or the pairs' values
   Buf cam;                       // gr_executor_camera_grads: a batch's camera-gradient partials
   std::vector<Buf> sums, sums3;  // one per view of a reduction batch (sums3: the depth-loss path's depth sums)
 };
@@ -124,16 +122,23 @@ struct gr_executor {
     if (s_ != GR_OK) return s_;     \
   } while (0)
 
+// What is done with each view: the fit (loss, backward, reductions) or a render-only pass (no losses, accumulators or
+// statistics: per view the render and one call that reads its saved sums).
+struct Pass {
+  enum Kind { fit, eval, contrib, error } kind = fit;
+  float* out = nullptr;  // eval: the views' metrics rows; contrib, error: the one per-Gaussian buffer
+  bool fwd_only() const { return kind != fit; }
+};
+
 static gr_status fit_views_on_device(gr_executor* ex, const gr_fit_config* cfg, int num_views, const gr_fit_target* views,
                                      int n, const float* means, const float* scales, const float* colors, int color_dim,
                                      const float* opacities, float w_sil, float w_depth, float g_scale, float w_dssim,
-                                     float* losses, float* const* acc, void* stream, float* metrics = nullptr,
-                                     float* peak = nullptr, float* err = nullptr);
+                                     float* losses, float* const* acc, void* stream, Pass pass = {});
 static gr_status enqueue_views(gr_executor* ex, const gr_fit_config* cfg, int num_views, const gr_fit_target* views, int n,
                                const float* means, const float* scales, const float* colors, int color_dim,
                                const float* opacities, float w_sil, float w_depth, float g_scale, float w_dssim, float* losses,
                                float* const* acc, const Sched& sc, const std::vector<hipStream_t>& st, hipStream_t prep,
-                               bool depth, int nslots, int& ngroups, float* metrics, float* peak, float* err);
+                               bool depth, int nslots, int& ngroups, Pass pass);
 
 extern "C" {
 
@@ -170,9 +175,7 @@ void gr_executor_destroy(gr_executor* ex) {
     w.scratch.release();
     w.ws.release();
     w.saved.release();
-    w.eval.release();
-    w.contrib.release();
-    w.error.release();
+    w.pass.release();
     w.cam.release();
     for (auto& b : w.sums) b.release();
     for (auto& b : w.sums3) b.release();
@@ -249,18 +252,21 @@ gr_status gr_fit_views_ssim(gr_executor* ex, const gr_fit_config* cfg, int num_v
                            g_scale, w_dssim, losses, acc, stream);
 }
 
-gr_status gr_eval_views(gr_executor* ex, const gr_fit_config* cfg, int num_views, const gr_fit_target* views, int n,
-                        const float* means, const float* scales, const float* colors, int color_dim, const float* opacities,
-                        float* metrics, void* stream) {
-  if (!ex || !cfg || (num_views > 0 && (!views || !metrics)))
-    return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, "gr_eval_views: null argument");
+// A render-only pass's entry point: its checks (`name` in each message) and the schedule on the executor's device.
+static gr_status pass_views_checked(const char* name, Pass pass, gr_executor* ex, const gr_fit_config* cfg, int num_views,
+                                    const gr_fit_target* views, int n, const float* means, const float* scales,
+                                    const float* colors, int color_dim, const float* opacities, void* stream) {
+  const std::string who = name;
+  if (!ex || !cfg || (num_views > 0 && (!views || !pass.out)))
+    return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, (who + ": null argument").c_str());
   if (cfg->num_streams < 1 || cfg->prep_ahead < 1 || cfg->prep_group < 1 || cfg->prep_group > GR_PREPARE_MAX_VIEWS ||
       cfg->prep_first < 1 || cfg->prep_first > GR_PREPARE_MAX_VIEWS)
-    return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, "gr_eval_views: configuration out of range");
-  if (cfg->caps) return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, "gr_eval_views: device-side sizing (caps) is not supported");
+    return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, (who + ": configuration out of range").c_str());
+  if (cfg->caps)
+    return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, (who + ": device-side sizing (caps) is not supported").c_str());
   if (num_views <= 0 || n <= 0) return GR_OK;
-  for (int j = 0; j < num_views; ++j)
-    if (!views[j].target_rgb) return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, "gr_eval_views: null target");
+  for (int j = 0; pass.kind != Pass::contrib && j < num_views; ++j)
+    if (!views[j].target_rgb) return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, (who + ": null target").c_str());
   gr_fit_config c = *cfg;  // no reductions: the batch settings are ignored
   c.reduce_batch = 1;
   c.reduce_tail = 0;
@@ -268,55 +274,30 @@ gr_status gr_eval_views(gr_executor* ex, const gr_fit_config* cfg, int num_views
   GR_EXEC_TRY(hipGetDevice(&prev_dev));
   GR_EXEC_TRY(hipSetDevice(ex->device));
   const gr_status st = fit_views_on_device(ex, &c, num_views, views, n, means, scales, colors, color_dim, opacities, 0.0f, 0.0f,
-                                           1.0f, 0.0f, nullptr, nullptr, stream, metrics);
+                                           1.0f, 0.0f, nullptr, nullptr, stream, pass);
   (void)hipSetDevice(prev_dev);
   return st;
+}
+
+gr_status gr_eval_views(gr_executor* ex, const gr_fit_config* cfg, int num_views, const gr_fit_target* views, int n,
+                        const float* means, const float* scales, const float* colors, int color_dim, const float* opacities,
+                        float* metrics, void* stream) {
+  return pass_views_checked("gr_eval_views", {Pass::eval, metrics}, ex, cfg, num_views, views, n, means, scales, colors,
+                            color_dim, opacities, stream);
 }
 
 gr_status gr_contrib_views(gr_executor* ex, const gr_fit_config* cfg, int num_views, const gr_fit_target* views, int n,
                            const float* means, const float* scales, const float* colors, int color_dim,
                            const float* opacities, float* peak, void* stream) {
-  if (!ex || !cfg || (num_views > 0 && (!views || !peak)))
-    return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, "gr_contrib_views: null argument");
-  if (cfg->num_streams < 1 || cfg->prep_ahead < 1 || cfg->prep_group < 1 || cfg->prep_group > GR_PREPARE_MAX_VIEWS ||
-      cfg->prep_first < 1 || cfg->prep_first > GR_PREPARE_MAX_VIEWS)
-    return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, "gr_contrib_views: configuration out of range");
-  if (cfg->caps) return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, "gr_contrib_views: device-side sizing (caps) is not supported");
-  if (num_views <= 0 || n <= 0) return GR_OK;
-  gr_fit_config c = *cfg;  // no reductions: the batch settings are ignored
-  c.reduce_batch = 1;
-  c.reduce_tail = 0;
-  int prev_dev = 0;
-  GR_EXEC_TRY(hipGetDevice(&prev_dev));
-  GR_EXEC_TRY(hipSetDevice(ex->device));
-  const gr_status st = fit_views_on_device(ex, &c, num_views, views, n, means, scales, colors, color_dim, opacities, 0.0f, 0.0f,
-                                           1.0f, 0.0f, nullptr, nullptr, stream, nullptr, peak);
-  (void)hipSetDevice(prev_dev);
-  return st;
+  return pass_views_checked("gr_contrib_views", {Pass::contrib, peak}, ex, cfg, num_views, views, n, means, scales, colors,
+                            color_dim, opacities, stream);
 }
 
 gr_status gr_error_views(gr_executor* ex, const gr_fit_config* cfg, int num_views, const gr_fit_target* views, int n,
                          const float* means, const float* scales, const float* colors, int color_dim,
                          const float* opacities, float* err, void* stream) {
-  if (!ex || !cfg || (num_views > 0 && (!views || !err)))
-    return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, "gr_error_views: null argument");
-  if (cfg->num_streams < 1 || cfg->prep_ahead < 1 || cfg->prep_group < 1 || cfg->prep_group > GR_PREPARE_MAX_VIEWS ||
-      cfg->prep_first < 1 || cfg->prep_first > GR_PREPARE_MAX_VIEWS)
-    return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, "gr_error_views: configuration out of range");
-  if (cfg->caps) return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, "gr_error_views: device-side sizing (caps) is not supported");
-  if (num_views <= 0 || n <= 0) return GR_OK;
-  for (int j = 0; j < num_views; ++j)
-    if (!views[j].target_rgb) return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, "gr_error_views: null target");
-  gr_fit_config c = *cfg;  // no reductions: the batch settings are ignored
-  c.reduce_batch = 1;
-  c.reduce_tail = 0;
-  int prev_dev = 0;
-  GR_EXEC_TRY(hipGetDevice(&prev_dev));
-  GR_EXEC_TRY(hipSetDevice(ex->device));
-  const gr_status st = fit_views_on_device(ex, &c, num_views, views, n, means, scales, colors, color_dim, opacities, 0.0f, 0.0f,
-                                           1.0f, 0.0f, nullptr, nullptr, stream, nullptr, nullptr, err);
-  (void)hipSetDevice(prev_dev);
-  return st;
+  return pass_views_checked("gr_error_views", {Pass::error, err}, ex, cfg, num_views, views, n, means, scales, colors,
+                            color_dim, opacities, stream);
 }
 
 }  // extern "C"
@@ -324,11 +305,8 @@ gr_status gr_error_views(gr_executor* ex, const gr_fit_config* cfg, int num_view
 static gr_status fit_views_on_device(gr_executor* ex, const gr_fit_config* cfg, int num_views, const gr_fit_target* views,
                                      int n, const float* means, const float* scales, const float* colors, int color_dim,
                                      const float* opacities, float w_sil, float w_depth, float g_scale, float w_dssim,
-                                     float* losses, float* const* acc, void* stream, float* metrics, float* peak,
-                                     float* err) {
-  // metrics: gr_eval_views' form (no losses, accumulators or statistics: per view the render and gr_eval_view);
-  // peak: gr_contrib_views' (the same with gr_contrib_view); err: gr_error_views' (with gr_error_view)
-  const bool fwd_only = metrics || peak || err;
+                                     float* losses, float* const* acc, void* stream, Pass pass) {
+  const bool fwd_only = pass.fwd_only();
   const bool depth = !fwd_only && views[0].target_depth != nullptr;
   const Sched sc = schedule(num_views, *cfg);
   const int ns = sc.ns;
@@ -405,8 +383,7 @@ static gr_status fit_views_on_device(gr_executor* ex, const gr_fit_config* cfg, 
       (void)hipStreamSynchronize(prep);
   };
   const gr_status status = enqueue_views(ex, cfg, num_views, views, n, means, scales, colors, color_dim, opacities, w_sil,
-                                         w_depth, g_scale, w_dssim, losses, acc, sc, st, prep, depth, nslots, ngroups, metrics, peak,
-                                         err);
+                                         w_depth, g_scale, w_dssim, losses, acc, sc, st, prep, depth, nslots, ngroups, pass);
   join();
   return status;
 }
@@ -415,8 +392,8 @@ static gr_status enqueue_views(gr_executor* ex, const gr_fit_config* cfg, int nu
                                const float* means, const float* scales, const float* colors, int color_dim,
                                const float* opacities, float w_sil, float w_depth, float g_scale, float w_dssim, float* losses,
                                float* const* acc, const Sched& sc, const std::vector<hipStream_t>& st, hipStream_t prep,
-                               bool depth, int nslots, int& ngroups, float* metrics, float* peak, float* err) {
-  const bool fwd_only = metrics || peak || err;  // gr_eval_views / gr_contrib_views / gr_error_views: no backward, no reductions
+                               bool depth, int nslots, int& ngroups, Pass pass) {
+  const bool fwd_only = pass.fwd_only();  // no backward, no reductions
   const int ns = sc.ns;
   const bool sized = cfg->caps != nullptr;  // device-side sizing: the plans are capacities, nothing to wait for
   const size_t geom_bytes = gr_geom_bytes(n);
@@ -484,7 +461,7 @@ static gr_status enqueue_views(gr_executor* ex, const gr_fit_config* cfg, int nu
                                 acc[4 * k + 2], acc[4 * k + 3], started[k], st[k]));
     if (ex->stats)  // the batch's density statistics beside its chain rule (gr_executor_density_stats)
       GR_EXEC_CALL(gr_density_stats(nb, b, n, means, scales, opacities, 1.0f / g_scale, ex->stats[k], st[k]));
-    if (ex->cams && !metrics) {  // the batch's camera gradients, view j into row j (gr_executor_camera_grads)
+    if (ex->cams) {  // the batch's camera gradients, view j into row j (gr_executor_camera_grads)
       float* rows[GR_REDUCE_MAX_VIEWS];
       for (int q = 0; q < nb; ++q) rows[q] = ex->cams + (size_t)GR_CAMERA_GRADS * pending[k][q].j;
       Buf& cw = ex->ws[k].cam;
@@ -517,29 +494,23 @@ static gr_status enqueue_views(gr_executor* ex, const gr_fit_config* cfg, int nu
     GR_EXEC_TRY(W.scratch.fit(scratch_bytes, s));
     if (!fwd_only) GR_EXEC_TRY(W.ws.fit(ws_bytes, s));
     void *bins = W.bins.p, *scratch = W.scratch.p, *ws = W.ws.p;
-    if (metrics) {
-      // gr_eval_views: the saved sums only (no image, no depth output), then the view's metrics from them
+    if (fwd_only) {
+      // the saved sums only (no image, no depth output), then the pass's one call on them: the view's metrics, or its
+      // pairs' values into the one per-Gaussian buffer (atomic maxima)
+      const size_t pass_bytes = pass.kind == Pass::eval      ? gr_eval_ws_bytes(&v)
+                                : pass.kind == Pass::contrib ? gr_contrib_ws_bytes(&v, n, &plan)
+                                                             : gr_error_ws_bytes(&v, n, &plan);
       GR_EXEC_TRY(W.saved.fit(gr_saved_floats(&v) * sizeof(float), s));
-      GR_EXEC_TRY(W.eval.fit(gr_eval_ws_bytes(&v), s));
+      GR_EXEC_TRY(W.pass.fit(pass_bytes, s));
       GR_EXEC_CALL(gr_fwd_render(&v, n, &plan, geom[j], bins, W.bins.cap, scratch, W.scratch.cap, nullptr, nullptr,
                                  nullptr, (float*)W.saved.p, s));
-      GR_EXEC_CALL(gr_eval_view(&v, (const float*)W.saved.p, views[j].target_rgb, metrics + (size_t)GR_EVAL_METRICS * j,
-                                W.eval.p, W.eval.cap, s));
-    } else if (peak) {
-      // gr_contrib_views: the saved sums only, then the view's peak blend weights into the one buffer (atomic maxima)
-      GR_EXEC_TRY(W.saved.fit(gr_saved_floats(&v) * sizeof(float), s));
-      GR_EXEC_TRY(W.contrib.fit(gr_contrib_ws_bytes(&v, n, &plan), s));
-      GR_EXEC_CALL(gr_fwd_render(&v, n, &plan, geom[j], bins, W.bins.cap, scratch, W.scratch.cap, nullptr, nullptr,
-                                 nullptr, (float*)W.saved.p, s));
-      GR_EXEC_CALL(gr_contrib_view(&v, n, &plan, geom[j], bins, (const float*)W.saved.p, peak, W.contrib.p, W.contrib.cap, s));
-    } else if (err) {
-      // gr_error_views: the saved sums only, then the view's blend-weighted error into the one buffer (atomic maxima)
-      GR_EXEC_TRY(W.saved.fit(gr_saved_floats(&v) * sizeof(float), s));
-      GR_EXEC_TRY(W.error.fit(gr_error_ws_bytes(&v, n, &plan), s));
-      GR_EXEC_CALL(gr_fwd_render(&v, n, &plan, geom[j], bins, W.bins.cap, scratch, W.scratch.cap, nullptr, nullptr,
-                                 nullptr, (float*)W.saved.p, s));
-      GR_EXEC_CALL(gr_error_view(&v, n, &plan, geom[j], bins, (const float*)W.saved.p, views[j].target_rgb, err, W.error.p,
-                                 W.error.cap, s));
+      const float* saved = (const float*)W.saved.p;
+      if (pass.kind == Pass::eval)
+        GR_EXEC_CALL(gr_eval_view(&v, saved, views[j].target_rgb, pass.out + (size_t)GR_EVAL_METRICS * j, W.pass.p, W.pass.cap, s));
+      else if (pass.kind == Pass::contrib)
+        GR_EXEC_CALL(gr_contrib_view(&v, n, &plan, geom[j], bins, saved, pass.out, W.pass.p, W.pass.cap, s));
+      else
+        GR_EXEC_CALL(gr_error_view(&v, n, &plan, geom[j], bins, saved, views[j].target_rgb, pass.out, W.pass.p, W.pass.cap, s));
     } else if (ssim) {
       // the saved sums only (no image: the D-SSIM forward stages the colours from them); sums3 with a depth target
       GR_EXEC_TRY(W.saved.fit(gr_saved_floats(&v) * sizeof(float), s));

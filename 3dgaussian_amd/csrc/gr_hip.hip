@@ -3962,93 +3962,70 @@ __global__ __launch_bounds__(256) void k_gather_view_views(VBatch<k_gather_view_
 }
 
 // ------------------------------------------------------------------------------------------------
-// Peak blend weight per Gaussian (gr_contrib_view): peak[i] = max(peak[i], max_p w_i(p) / (1 + W(p))) over the pixels
-// of Gaussian i's kept pairs (core and tail lists alike), W the view's weight sums as the render saved them.
-// k_contrib_view: the splats' mapping, one workgroup per non-empty work item.  The tile's r(p) = 1 / (1 + W(p)) is
-// staged once in LDS (0 outside the image: such a pixel never wins); then one lane per pair of the item: the 16 + 16
-// separable factors exp2(qx dx^2), o exp2(qy dy^2) in plain f32 at the forward's pixel centres, and per tile row the
-// maximum of ex[x] r(x, y) against broadcast LDS reads, scaled by the row's factor (all factors are >= 0 and an f32
-// multiply is monotonic, so max_x (ey ex r) = ey max_x (ex r) exactly).  No cross-lane step: the pair's value goes to
-// vals[k], k its sorted position (a coalesced store).
-__global__ __launch_bounds__(256, 4) void k_contrib_view(ViewK v, const int4* __restrict__ items, const int* __restrict__ num_items,
-                                                      const int* __restrict__ pairs, const float4* __restrict__ rec,
-                                                      const float4* __restrict__ saved4, float* __restrict__ vals) {
-  __shared__ __attribute__((aligned(16))) float r[TP];
-  const int nfull = num_items[1];  // the non-empty items are listed first
-  if ((int)blockIdx.x >= nfull) return;
-  const int4 it = items[xcd_item(blockIdx.x, nfull)];
-  const int tile = it.x >> 1, k0 = it.y, k1 = it.z;
-  const int tx = tile % v.tiles_x, ty = tile / v.tiles_x;
-  const int tid = threadIdx.x;
-  {
-    const int x = tx * T + (tid & (T - 1)), y = ty * T + (tid >> 4);
-    r[tid] = x < v.W && y < v.H ? 1.0f / (1.0f + saved4[(size_t)y * v.W + x].x) : 0.0f;
-  }
-  __syncthreads();
-  for (int k = k0 + tid; k < k1; k += 256) {
-    // r is read from LDS in every round: hoisted out of the loop its 256 values took every register of the SIMD
-    asm volatile("" ::: "memory");
-    const int g = pairs[k];
-    const float4 a = rec[(size_t)REC4 * g];
-    const float o = rec[(size_t)REC4 * g + 1].x;
-    f32x2_t ex[T / 2];
+// Per-Gaussian statistics of a rendered view (gr_contrib_view, gr_error_view): stat[i] = max(stat[i], S_i) with S_i
+// one combine over the pixels of Gaussian i's kept pairs (core and tail lists alike) of w_i(p) m(p), m a per-pixel
+// value formed from the sums the render saved.  Two kernels, written once over a statistic type that supplies
+//   pixel(v, s, target, p)  m(p) from the pixel's saved sums (and the target),
+//   row(ex, m)              the combine over one tile row of ex[x] m(x, y),
+//   fold(acc, ey, row)      a row's result, scaled by the row's factor, into the pair's value,
+//   gather(acc, val)        a pair's value into the Gaussian's;
+// every value is >= 0 and 0 is each combine's identity.
+// Peak blend weight: m = r = 1 / (1 + W(p)), W the view's weight sums; maximum over pixels and pairs.  All factors
+// are >= 0 and an f32 multiply is monotonic, so max_x (ey ex r) = ey max_x (ex r) exactly.
+struct PeakWeightStat {
+  static __device__ __forceinline__ float pixel(const ViewK&, const float4 s, const float*, size_t) { return 1.0f / (1.0f + s.x); }
+  static __device__ __forceinline__ float row(const f32x2_t* ex, const float* m) {
+    f32x2_t mm = {0.0f, 0.0f};
 #pragma unroll
-    for (int j = 0; j < T / 2; ++j) {
-      const float dx0 = ((float)(tx * T + 2 * j) + 0.5f) - a.x, dx1 = ((float)(tx * T + 2 * j + 1) + 0.5f) - a.x;
-      ex[j] = f32x2_t{__builtin_amdgcn_exp2f((dx0 * a.z) * dx0), __builtin_amdgcn_exp2f((dx1 * a.z) * dx1)};
+    for (int j = 0; j < T / 4; ++j) {
+      const float4 u = *reinterpret_cast<const float4*>(m + 4 * j);
+      mm = __builtin_elementwise_max(mm, ex[2 * j] * f32x2_t{u.x, u.y});
+      mm = __builtin_elementwise_max(mm, ex[2 * j + 1] * f32x2_t{u.z, u.w});
     }
-    float m = 0.0f;
-#pragma unroll
-    for (int y = 0; y < T; ++y) {
-      const float dy = ((float)(ty * T + y) + 0.5f) - a.y;
-      const float ey = o * __builtin_amdgcn_exp2f((dy * a.w) * dy);
-      f32x2_t mm = {0.0f, 0.0f};
-#pragma unroll
-      for (int j = 0; j < T / 4; ++j) {
-        const float4 u = *reinterpret_cast<const float4*>(r + y * T + 4 * j);
-        mm = __builtin_elementwise_max(mm, ex[2 * j] * f32x2_t{u.x, u.y});
-        mm = __builtin_elementwise_max(mm, ex[2 * j + 1] * f32x2_t{u.z, u.w});
-      }
-      m = fmaxf(m, ey * fmaxf(mm.x, mm.y));
-    }
-    vals[k] = m;
+    return fmaxf(mm.x, mm.y);
   }
-}
+  static __device__ __forceinline__ float fold(float acc, float ey, float row) { return fmaxf(acc, ey * row); }
+  static __device__ __forceinline__ float gather(float acc, float val) { return fmaxf(acc, val); }
+};
+// Blend-weighted pixel error: m = r e, e(p) the mean absolute difference of the three channels between the view's
+// colour (write_pixel's expression on the saved sums: a target equal to that image gives e = 0 exactly) and the
+// target; sum over pixels and pairs.  The blend weights w r and the background's r sum to one, so the view's L1 error
+// is partitioned exactly among the Gaussians and the background.  A fixed order: per row two packed f32 FMA chains
+// over the even and the odd pixel pairs (x ascending in each), their lanes added as (lo + hi), then one FMA into the
+// pair's sum, y ascending; the pairs' values in emission order.
+struct PixelErrorStat {
+  static __device__ __forceinline__ float pixel(const ViewK& v, const float4 s, const float* target, size_t p) {
+    const float den = 1.0f + s.x;
+    const float d0 = clamp01((view_bg(v, 0) + s.y) / den) - target[3 * p + 0];
+    const float d1 = clamp01((view_bg(v, 1) + s.z) / den) - target[3 * p + 1];
+    const float d2 = clamp01((view_bg(v, 2) + s.w) / den) - target[3 * p + 2];
+    return (1.0f / den) * (((fabsf(d0) + fabsf(d1)) + fabsf(d2)) / 3.0f);
+  }
+  static __device__ __forceinline__ float row(const f32x2_t* ex, const float* m) {
+    f32x2_t s0 = {0.0f, 0.0f}, s1 = {0.0f, 0.0f};
+#pragma unroll
+    for (int j = 0; j < T / 4; ++j) {
+      const float4 u = *reinterpret_cast<const float4*>(m + 4 * j);
+      s0 = __builtin_elementwise_fma(ex[2 * j], f32x2_t{u.x, u.y}, s0);
+      s1 = __builtin_elementwise_fma(ex[2 * j + 1], f32x2_t{u.z, u.w}, s1);
+    }
+    const f32x2_t st = s0 + s1;
+    return st.x + st.y;
+  }
+  static __device__ __forceinline__ float fold(float acc, float ey, float row) { return fmaf(ey, row, acc); }
+  static __device__ __forceinline__ float gather(float acc, float val) { return acc + val; }
+};
 
-// One lane per Gaussian: the maximum of its pairs' values (its core pairs, then its tail pairs, contiguous in
-// emission order; pos_of gives their sorted positions, as in k_gather_view) and one unsigned atomic maximum on the
-// float's bits into peak[i] (non-negative floats order as their bit patterns; the lanes of a wave address 256
-// contiguous bytes).  A maximum does not depend on the order of arrival, so the result is the same bits whichever
-// views, on whichever streams, share the buffer.  A Gaussian without pairs in this view is not touched.
-__global__ __launch_bounds__(256) void k_contrib_gather(int n, const Cnt2* __restrict__ offsets, const int* __restrict__ pos_of,
-                                                        const float* __restrict__ vals, unsigned* __restrict__ peak) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const Cnt2 o0 = offsets[i], o1 = offsets[i + 1];
-  const unsigned cc = o1.c() - o0.c(), tc = o1.t() - o0.t();
-  if (cc + tc == 0) return;
-  const int* pc = pos_of + o0.c();
-  const int* pt = pos_of + (size_t)offsets[n].c() + o0.t();
-  float m = 0.0f;
-  for (unsigned j = 0; j < cc; ++j) m = fmaxf(m, vals[pc[j]]);
-  for (unsigned j = 0; j < tc; ++j) m = fmaxf(m, vals[pt[j]]);
-  atomicMax(peak + i, __float_as_uint(m));
-}
-
-// ------------------------------------------------------------------------------------------------
-// Blend-weighted pixel error per Gaussian (gr_error_view): err[i] = max(err[i], sum_p w_i(p) r(p) e(p)) over the
-// pixels of Gaussian i's kept pairs, r = 1 / (1 + W) and e(p) the mean absolute difference of the three channels
-// between the view's colour (write_pixel's expression on the saved sums: a target equal to that image gives e = 0
-// exactly) and the target.  The blend weights w r and the background's r sum to one, so the view's L1 error is
-// partitioned exactly among the Gaussians and the background.
-// k_error_view: k_contrib_view's mapping and factors.  The tile's m(p) = r(p) e(p) is staged once in LDS (0 outside
-// the image); one lane per pair forms o sum_y ey[y] sum_x ex[x] m(x, y): per row two packed f32 FMA chains over the
-// even and the odd pixel pairs (x ascending in each), their lanes added as (lo + hi), then one FMA into the pair's
-// sum, y ascending: a fixed order.  No cross-lane step; the pair's value goes to vals[k].
-__global__ __launch_bounds__(256, 4) void k_error_view(ViewK v, const int4* __restrict__ items, const int* __restrict__ num_items,
-                                                    const int* __restrict__ pairs, const float4* __restrict__ rec,
-                                                    const float4* __restrict__ saved4, const float* __restrict__ target,
-                                                    float* __restrict__ vals) {
+// The splats' mapping, one workgroup per non-empty work item.  The tile's m(p) is staged once in LDS (0 outside the
+// image: such a pixel adds nothing and never wins); then one lane per pair of the item: the 16 + 16 separable factors
+// exp2(qx dx^2), o exp2(qy dy^2) in plain f32 at the forward's pixel centres, and per tile row the statistic's combine
+// of ex[x] m(x, y) against broadcast LDS reads.  No cross-lane step: the pair's value goes to vals[k], k its sorted
+// position (a coalesced store).
+template <class S>
+__device__ __forceinline__ void pair_stat_view(const ViewK& v, const int4* __restrict__ items, const int* __restrict__ num_items,
+                                               const int* __restrict__ pairs, const float4* __restrict__ rec,
+                                               const float4* __restrict__ saved4, const float* __restrict__ target,
+                                               float* __restrict__ vals) {
   __shared__ __attribute__((aligned(16))) float m[TP];
   const int nfull = num_items[1];  // the non-empty items are listed first
   if ((int)blockIdx.x >= nfull) return;
@@ -4061,18 +4038,13 @@ __global__ __launch_bounds__(256, 4) void k_error_view(ViewK v, const int4* __re
     float mv = 0.0f;
     if (x < v.W && y < v.H) {
       const size_t p = (size_t)y * v.W + x;
-      const float4 s = saved4[p];
-      const float den = 1.0f + s.x;
-      const float d0 = clamp01((view_bg(v, 0) + s.y) / den) - target[3 * p + 0];
-      const float d1 = clamp01((view_bg(v, 1) + s.z) / den) - target[3 * p + 1];
-      const float d2 = clamp01((view_bg(v, 2) + s.w) / den) - target[3 * p + 2];
-      mv = (1.0f / den) * (((fabsf(d0) + fabsf(d1)) + fabsf(d2)) / 3.0f);
+      mv = S::pixel(v, saved4[p], target, p);
     }
     m[tid] = mv;
   }
   __syncthreads();
   for (int k = k0 + tid; k < k1; k += 256) {
-    // m is read from LDS in every round (k_contrib_view: hoisted, the 256 values take every register of the SIMD)
+    // m is read from LDS in every round: hoisted out of the loop its 256 values took every register of the SIMD
     asm volatile("" ::: "memory");
     const int g = pairs[k];
     const float4 a = rec[(size_t)REC4 * g];
@@ -4083,30 +4055,37 @@ __global__ __launch_bounds__(256, 4) void k_error_view(ViewK v, const int4* __re
       const float dx0 = ((float)(tx * T + 2 * j) + 0.5f) - a.x, dx1 = ((float)(tx * T + 2 * j + 1) + 0.5f) - a.x;
       ex[j] = f32x2_t{__builtin_amdgcn_exp2f((dx0 * a.z) * dx0), __builtin_amdgcn_exp2f((dx1 * a.z) * dx1)};
     }
-    float sum = 0.0f;
+    float acc = 0.0f;
 #pragma unroll
     for (int y = 0; y < T; ++y) {
       const float dy = ((float)(ty * T + y) + 0.5f) - a.y;
       const float ey = o * __builtin_amdgcn_exp2f((dy * a.w) * dy);
-      f32x2_t s0 = {0.0f, 0.0f}, s1 = {0.0f, 0.0f};
-#pragma unroll
-      for (int j = 0; j < T / 4; ++j) {
-        const float4 u = *reinterpret_cast<const float4*>(m + y * T + 4 * j);
-        s0 = __builtin_elementwise_fma(ex[2 * j], f32x2_t{u.x, u.y}, s0);
-        s1 = __builtin_elementwise_fma(ex[2 * j + 1], f32x2_t{u.z, u.w}, s1);
-      }
-      const f32x2_t st = s0 + s1;
-      sum = fmaf(ey, st.x + st.y, sum);
+      acc = S::fold(acc, ey, S::row(ex, m + y * T));
     }
-    vals[k] = sum;
+    vals[k] = acc;
   }
 }
+__global__ __launch_bounds__(256, 4) void k_contrib_view(ViewK v, const int4* __restrict__ items, const int* __restrict__ num_items,
+                                                      const int* __restrict__ pairs, const float4* __restrict__ rec,
+                                                      const float4* __restrict__ saved4, float* __restrict__ vals) {
+  pair_stat_view<PeakWeightStat>(v, items, num_items, pairs, rec, saved4, nullptr, vals);
+}
+__global__ __launch_bounds__(256, 4) void k_error_view(ViewK v, const int4* __restrict__ items, const int* __restrict__ num_items,
+                                                    const int* __restrict__ pairs, const float4* __restrict__ rec,
+                                                    const float4* __restrict__ saved4, const float* __restrict__ target,
+                                                    float* __restrict__ vals) {
+  pair_stat_view<PixelErrorStat>(v, items, num_items, pairs, rec, saved4, target, vals);
+}
 
-// One lane per Gaussian: the sum of its pairs' values, its core pairs then its tail pairs in emission order through
-// pos_of (k_contrib_gather's walk; a fixed order, so the sum is deterministic), and one unsigned atomic maximum on the
-// float's bits into err[i] (a sum of non-negative terms is non-negative).  A Gaussian without pairs is not touched.
-__global__ __launch_bounds__(256) void k_error_gather(int n, const Cnt2* __restrict__ offsets, const int* __restrict__ pos_of,
-                                                      const float* __restrict__ vals, unsigned* __restrict__ err) {
+// One lane per Gaussian: the statistic's combine of its pairs' values (its core pairs, then its tail pairs, contiguous
+// in emission order; pos_of gives their sorted positions, as in k_gather_view: a fixed order, so a sum is
+// deterministic) and one unsigned atomic maximum on the float's bits into stat[i] (non-negative floats order as their
+// bit patterns; the lanes of a wave address 256 contiguous bytes).  A maximum does not depend on the order of arrival,
+// so the result is the same bits whichever views, on whichever streams, share the buffer.  A Gaussian without pairs in
+// this view is not touched.
+template <class S>
+__device__ __forceinline__ void pair_stat_gather(int n, const Cnt2* __restrict__ offsets, const int* __restrict__ pos_of,
+                                                 const float* __restrict__ vals, unsigned* __restrict__ stat) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const Cnt2 o0 = offsets[i], o1 = offsets[i + 1];
@@ -4115,19 +4094,27 @@ __global__ __launch_bounds__(256) void k_error_gather(int n, const Cnt2* __restr
   const int* pc = pos_of + o0.c();
   const int* pt = pos_of + (size_t)offsets[n].c() + o0.t();
   float s = 0.0f;
-  // four index -> value loads in flight, added in emission order (a sum's order is fixed: the compiler would keep one)
+  // four index -> value loads in flight, combined in emission order (a sum's order is fixed: the compiler would keep one)
   auto walk = [&](const int* __restrict__ p, unsigned c) {
     unsigned j = 0;
     for (; j + 4 <= c; j += 4) {
       const int i0 = p[j], i1 = p[j + 1], i2 = p[j + 2], i3 = p[j + 3];
       const float v0 = vals[i0], v1 = vals[i1], v2 = vals[i2], v3 = vals[i3];
-      s = (((s + v0) + v1) + v2) + v3;
+      s = S::gather(S::gather(S::gather(S::gather(s, v0), v1), v2), v3);
     }
-    for (; j < c; ++j) s += vals[p[j]];
+    for (; j < c; ++j) s = S::gather(s, vals[p[j]]);
   };
   walk(pc, cc);
   walk(pt, tc);
-  atomicMax(err + i, __float_as_uint(s));
+  atomicMax(stat + i, __float_as_uint(s));
+}
+__global__ __launch_bounds__(256) void k_contrib_gather(int n, const Cnt2* __restrict__ offsets, const int* __restrict__ pos_of,
+                                                        const float* __restrict__ vals, unsigned* __restrict__ peak) {
+  pair_stat_gather<PeakWeightStat>(n, offsets, pos_of, vals, peak);
+}
+__global__ __launch_bounds__(256) void k_error_gather(int n, const Cnt2* __restrict__ offsets, const int* __restrict__ pos_of,
+                                                      const float* __restrict__ vals, unsigned* __restrict__ err) {
+  pair_stat_gather<PixelErrorStat>(n, offsets, pos_of, vals, err);
 }
 
 
@@ -7196,72 +7183,61 @@ gr_status gr_eval_view(const gr_view* v, const float* saved, const float* target
   return GR_OK;
 }
 
-// Peak blend weights: one float per pair (k_contrib_view's values by sorted position).
-size_t gr_contrib_ws_bytes(const gr_view* v, int n, const gr_plan* plan) {
+// Peak blend weights and blend-weighted pixel error: one float per pair (the view kernel's values by sorted position).
+static size_t pair_stat_ws_bytes(const gr_view* v, int n, const gr_plan* plan) {
   if (!v || !plan || n <= 0 || plan->num_pairs <= 0) return 0;
   return align_up((size_t)plan->num_pairs * sizeof(float));
 }
 
-gr_status gr_contrib_view(const gr_view* v, int n, const gr_plan* plan, const void* geom, const void* bins, const float* saved,
-                          float* peak, void* ws, size_t ws_bytes, void* stream) {
+// The checks and the two launches of a per-Gaussian statistic; `name` is the entry point's, for its messages, and the
+// error statistic (needs_target) reads a target.
+static gr_status pair_stat_view_host(const char* name, bool needs_target, const gr_view* v, int n, const gr_plan* plan,
+                                     const void* geom, const void* bins, const float* saved, const float* target_rgb,
+                                     float* stat, void* ws, size_t ws_bytes, void* stream) {
+  const std::string who = name;
   gr_status st = check_view(v);
   if (st != GR_OK) return st;
   if (tile_of(v) != T)
-    return set_error(GR_ERR_INVALID_ARGUMENT, "gr_contrib_view: 32-pixel tiles (gr_view.tile = 32): 16-pixel tiles only");
-  if (v->rows > 0) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_contrib_view: a band of tile rows (gr_view.rows): whole views only");
+    return set_error(GR_ERR_INVALID_ARGUMENT, who + ": 32-pixel tiles (gr_view.tile = 32): 16-pixel tiles only");
+  if (v->rows > 0) return set_error(GR_ERR_INVALID_ARGUMENT, who + ": a band of tile rows (gr_view.rows): whole views only");
   if (v->device_counts)
-    return set_error(GR_ERR_INVALID_ARGUMENT, "gr_contrib_view: device-sized views (device_counts = 1) are not supported");
+    return set_error(GR_ERR_INVALID_ARGUMENT, who + ": device-sized views (device_counts = 1) are not supported");
   if (!plan) return set_error(GR_ERR_INVALID_ARGUMENT, "plan is null");
   if (plan->num_pairs < 0) return set_error(GR_ERR_OVERFLOW, "pair count overflows int32");
   if (n < 0) return set_error(GR_ERR_INVALID_ARGUMENT, "n must be >= 0");
-  if (!geom || !bins || !saved || !peak) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_contrib_view: null pointer");
-  if (n == 0 || plan->num_pairs == 0) return GR_OK;  // no pair: every peak stays
-  if (!ws) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_contrib_view: null pointer");
-  if (ws_bytes < gr_contrib_ws_bytes(v, n, plan)) return set_error(GR_ERR_WORKSPACE, "gr_contrib_view: workspace too small");
+  if (!geom || !bins || !saved || (needs_target && !target_rgb) || !stat)
+    return set_error(GR_ERR_INVALID_ARGUMENT, who + ": null pointer");
+  if (n == 0 || plan->num_pairs == 0) return GR_OK;  // no pair: every value stays
+  if (!ws) return set_error(GR_ERR_INVALID_ARGUMENT, who + ": null pointer");
+  if (ws_bytes < pair_stat_ws_bytes(v, n, plan)) return set_error(GR_ERR_WORKSPACE, who + ": workspace too small");
   hipStream_t s = (hipStream_t)stream;
   const ViewCtx c = view_ctx(v, n, plan, geom, bins, nullptr, nullptr);
-  hipLaunchKernelGGL(k_contrib_view, dim3((unsigned)c.cap), dim3(256), 0, s, c.vk, (const int4*)c.b.items,
-                     (const int*)c.b.num_items, (const int*)c.b.pairs, (const float4*)c.g.rec, (const float4*)saved,
-                     (float*)ws);
+  if (needs_target)
+    hipLaunchKernelGGL(k_error_view, dim3((unsigned)c.cap), dim3(256), 0, s, c.vk, (const int4*)c.b.items,
+                       (const int*)c.b.num_items, (const int*)c.b.pairs, (const float4*)c.g.rec, (const float4*)saved,
+                       target_rgb, (float*)ws);
+  else
+    hipLaunchKernelGGL(k_contrib_view, dim3((unsigned)c.cap), dim3(256), 0, s, c.vk, (const int4*)c.b.items,
+                       (const int*)c.b.num_items, (const int*)c.b.pairs, (const float4*)c.g.rec, (const float4*)saved,
+                       (float*)ws);
   GR_HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_contrib_gather, dim3(blocks_for(n)), dim3(256), 0, s, n, (const Cnt2*)c.g.offsets,
-                     (const int*)c.b.pos_of, (const float*)ws, (unsigned*)peak);
+  hipLaunchKernelGGL(needs_target ? k_error_gather : k_contrib_gather, dim3(blocks_for(n)), dim3(256), 0, s, n,
+                     (const Cnt2*)c.g.offsets, (const int*)c.b.pos_of, (const float*)ws, (unsigned*)stat);
   GR_HIP_TRY(hipGetLastError());
   return GR_OK;
 }
 
-// Blend-weighted pixel error: one float per pair (k_error_view's values by sorted position).
-size_t gr_error_ws_bytes(const gr_view* v, int n, const gr_plan* plan) {
-  if (!v || !plan || n <= 0 || plan->num_pairs <= 0) return 0;
-  return align_up((size_t)plan->num_pairs * sizeof(float));
+size_t gr_contrib_ws_bytes(const gr_view* v, int n, const gr_plan* plan) { return pair_stat_ws_bytes(v, n, plan); }
+size_t gr_error_ws_bytes(const gr_view* v, int n, const gr_plan* plan) { return pair_stat_ws_bytes(v, n, plan); }
+
+gr_status gr_contrib_view(const gr_view* v, int n, const gr_plan* plan, const void* geom, const void* bins, const float* saved,
+                          float* peak, void* ws, size_t ws_bytes, void* stream) {
+  return pair_stat_view_host("gr_contrib_view", false, v, n, plan, geom, bins, saved, nullptr, peak, ws, ws_bytes, stream);
 }
 
 gr_status gr_error_view(const gr_view* v, int n, const gr_plan* plan, const void* geom, const void* bins, const float* saved,
                         const float* target_rgb, float* err, void* ws, size_t ws_bytes, void* stream) {
-  gr_status st = check_view(v);
-  if (st != GR_OK) return st;
-  if (tile_of(v) != T)
-    return set_error(GR_ERR_INVALID_ARGUMENT, "gr_error_view: 32-pixel tiles (gr_view.tile = 32): 16-pixel tiles only");
-  if (v->rows > 0) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_error_view: a band of tile rows (gr_view.rows): whole views only");
-  if (v->device_counts)
-    return set_error(GR_ERR_INVALID_ARGUMENT, "gr_error_view: device-sized views (device_counts = 1) are not supported");
-  if (!plan) return set_error(GR_ERR_INVALID_ARGUMENT, "plan is null");
-  if (plan->num_pairs < 0) return set_error(GR_ERR_OVERFLOW, "pair count overflows int32");
-  if (n < 0) return set_error(GR_ERR_INVALID_ARGUMENT, "n must be >= 0");
-  if (!geom || !bins || !saved || !target_rgb || !err) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_error_view: null pointer");
-  if (n == 0 || plan->num_pairs == 0) return GR_OK;  // no pair: every value stays
-  if (!ws) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_error_view: null pointer");
-  if (ws_bytes < gr_error_ws_bytes(v, n, plan)) return set_error(GR_ERR_WORKSPACE, "gr_error_view: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  const ViewCtx c = view_ctx(v, n, plan, geom, bins, nullptr, nullptr);
-  hipLaunchKernelGGL(k_error_view, dim3((unsigned)c.cap), dim3(256), 0, s, c.vk, (const int4*)c.b.items,
-                     (const int*)c.b.num_items, (const int*)c.b.pairs, (const float4*)c.g.rec, (const float4*)saved,
-                     target_rgb, (float*)ws);
-  GR_HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_error_gather, dim3(blocks_for(n)), dim3(256), 0, s, n, (const Cnt2*)c.g.offsets,
-                     (const int*)c.b.pos_of, (const float*)ws, (unsigned*)err);
-  GR_HIP_TRY(hipGetLastError());
-  return GR_OK;
+  return pair_stat_view_host("gr_error_view", true, v, n, plan, geom, bins, saved, target_rgb, err, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -2169,26 +2169,23 @@ class ViewShardedFitter:
             ctypes_stream(device)), fn)
         self._eval_keep = (m, s, c, o)  # read by the executor's streams until the caller's stream passes them
 
-    def _eval_direct(self, m, s, c, o, gvs, targets, out) -> None:
-        """The Python schedule of gr_eval_views' calls (_view_loop): per view forward_native (saved sums only) +
-        eval_view_native into ``out[j]``."""
+    def _pass_direct(self, m, s, c, o, gvs, view_call: Callable) -> None:
+        """The Python schedule of a render-only executor pass's calls (_view_loop): per view forward_native (saved sums
+        only) + ``view_call(j, rs, pv)``, the pass's one native call on view j's render state and Prepared."""
         def body(j, take):
             pv = take(j)
             _, _, _, rs = tr.forward_native(m, s, c, o, pv.gv, pv, images=False)
-            pv = None
-            tr.eval_view_native(rs, targets[j], out[j])
+            view_call(j, rs, pv)
 
         self._view_loop(m.device, len(gvs), self._preparer(m, s, c, o, gvs.__getitem__, len(gvs)), body)
 
-    def _contrib_direct(self, m, s, c, o, gvs, peak) -> None:
-        """The Python schedule of gr_contrib_views' calls (_view_loop): per view forward_native (saved sums only) +
-        contrib_view_native, every view into the one ``peak``."""
-        def body(j, take):
-            pv = take(j)
-            _, _, _, rs = tr.forward_native(m, s, c, o, pv.gv, pv, images=False)
-            tr.contrib_view_native(rs, pv, peak)
-
-        self._view_loop(m.device, len(gvs), self._preparer(m, s, c, o, gvs.__getitem__, len(gvs)), body)
+    def _pass_views(self, fn: str, m, s, c, o, gvs, targets, out, view_call: Callable) -> None:
+        """A render-only pass over ``gvs``: the native executor's ``fn`` (_exec_views) where the fit step uses it, else
+        the Python schedule of the same calls (_pass_direct)."""
+        if self._native_exec() and GATHER:
+            self._exec_views(fn, m, s, c, o, gvs, targets, out)
+        else:
+            self._pass_direct(m, s, c, o, gvs, view_call)
 
     def evaluate(self, cams: Optional[list] = None, targets: Optional[list] = None) -> dict:
         """Per-view metrics of the current Gaussians against target images: float64 numpy arrays ``l1`` (mean|x - y|),
@@ -2221,10 +2218,9 @@ class ViewShardedFitter:
                 m, s, c, o = (t.detach().float().contiguous() for t in (means, scales, colors, opacities))
                 gvs = [self._eval_view(cams[i], device) for i in mine]
                 out = torch.empty((len(mine), tr._native.EVAL_METRICS), dtype=torch.float32, device=device)
-                if self._native_exec() and GATHER:
-                    self._exec_views("gr_eval_views", m, s, c, o, gvs, [targets[i] for i in mine], out)
-                else:
-                    self._eval_direct(m, s, c, o, gvs, [targets[i] for i in mine], out)
+                tg = [targets[i] for i in mine]
+                self._pass_views("gr_eval_views", m, s, c, o, gvs, tg, out,
+                                 lambda j, rs, pv: tr.eval_view_native(rs, tg[j], out[j]))
                 res[mine] = out
             else:
                 for i in mine:
@@ -2257,43 +2253,47 @@ class ViewShardedFitter:
         cpu_renderer.peak_contribution.  Changes nothing of the fit."""
         self.graph_sync()
         cams = self.cams if cams is None else cams
+
+        def cpu_view(i, m, s, c, o):
+            from . import cpu_renderer
+            return cpu_renderer.peak_contribution(m, s, o, cams[i].view, cams[i].proj, self.width, self.height)
+
+        return self._gaussian_state(cams, None, "gr_contrib_views",
+                                    lambda rs, pv, _target, peak: tr.contrib_view_native(rs, pv, peak), cpu_view)
+
+    def _gaussian_state(self, cams, targets, fn: str, view_call: Callable, cpu_view: Callable,
+                        unmet: Optional[str] = None) -> torch.Tensor:
+        """contribution_state's and error_state's flow: this rank's share of ``cams`` (rendered against ``targets``, or
+        None), every view's values folded by maximum into one zeroed (n,) buffer, all-reduced (MAX) and scattered to
+        canonical order.  On the HIP device the render-only pass ``fn`` (_pass_views; per view
+        ``view_call(rs, pv, target, out)``), with targets only under _eval_native_ok (else ValueError(``unmet``)); on
+        other devices ``cpu_view(i, m, s, c, o)`` per view."""
         device = self.params["means"].device
         n = int(self.params["means"].shape[0])
         mine = list(range(self.rank, len(cams), self.world))
-        peak = torch.zeros((n,), dtype=torch.float32, device=device)
+        stat = torch.zeros((n,), dtype=torch.float32, device=device)
         with torch.no_grad():
             if mine and n > 0:
                 m, s, c, o = (t.detach().float().contiguous() for t in self._eval_activations(device))
                 if device.type == "cuda":
+                    tg = None if targets is None else [targets[i] for i in mine]
+                    if tg is not None and not self._eval_native_ok(device, tg):
+                        raise ValueError(unmet)
                     gvs = [self._eval_view(cams[i], device) for i in mine]
-                    if self._native_exec() and GATHER:
-                        self._exec_views("gr_contrib_views", m, s, c, o, gvs, None, peak)
-                    else:
-                        self._contrib_direct(m, s, c, o, gvs, peak)
+                    self._pass_views(fn, m, s, c, o, gvs, tg, stat,
+                                     lambda j, rs, pv: view_call(rs, pv, None if tg is None else tg[j], stat))
                 else:
-                    from . import cpu_renderer
                     for i in mine:
-                        peak = torch.maximum(peak, cpu_renderer.peak_contribution(m, s, o, cams[i].view, cams[i].proj,
-                                                                                  self.width, self.height))
+                        stat = torch.maximum(stat, cpu_view(i, m, s, c, o))
         if self.world > 1:
-            dist.all_reduce(peak, op=dist.ReduceOp.MAX, group=self.group)
+            dist.all_reduce(stat, op=dist.ReduceOp.MAX, group=self.group)
         if self.perm is not None:
-            canon = torch.empty_like(peak)
-            canon[self.perm] = peak
-            peak = canon
-        return peak
+            canon = torch.empty_like(stat)
+            canon[self.perm] = stat
+            stat = canon
+        return stat
 
     # ---- error (blend-weighted pixel error per Gaussian) --------------------------------------------------------
-    def _error_direct(self, m, s, c, o, gvs, targets, err) -> None:
-        """The Python schedule of gr_error_views' calls (_view_loop): per view forward_native (saved sums only) +
-        error_view_native against ``targets[j]``, every view into the one ``err``."""
-        def body(j, take):
-            pv = take(j)
-            _, _, _, rs = tr.forward_native(m, s, c, o, pv.gv, pv, images=False)
-            tr.error_view_native(rs, pv, targets[j], err)
-
-        self._view_loop(m.device, len(gvs), self._preparer(m, s, c, o, gvs.__getitem__, len(gvs)), body)
-
     def error_state(self, cams: Optional[list] = None, targets: Optional[list] = None) -> torch.Tensor:
         """Per Gaussian in canonical order (as canonical_params), its blend-weighted pixel error: the maximum over the
         views (default: the training views; else ``cams`` and ``targets``, (H, W, 3) images, both or neither) of
@@ -2317,37 +2317,18 @@ class ViewShardedFitter:
         if len(cams) != len(targets):
             raise ValueError(f"error_state: {len(cams)} cameras for {len(targets)} targets")
         device = self.params["means"].device
-        n = int(self.params["means"].shape[0])
-        mine = list(range(self.rank, len(cams), self.world))
-        err = torch.zeros((n,), dtype=torch.float32, device=device)
-        with torch.no_grad():
-            if mine and n > 0:
-                m, s, c, o = (t.detach().float().contiguous() for t in self._eval_activations(device))
-                if device.type == "cuda":
-                    tg = [targets[i] for i in mine]
-                    if not self._eval_native_ok(device, tg):
-                        raise ValueError("error_state on the HIP device needs the HIP render op, float32 parameters and "
-                                         f"contiguous float32 targets of shape {(self.height, self.width, 3)} on {device}: "
-                                         "gr_error_view reads them through raw pointers and has no other form")
-                    gvs = [self._eval_view(cams[i], device) for i in mine]
-                    if self._native_exec() and GATHER:
-                        self._exec_views("gr_error_views", m, s, c, o, gvs, tg, err)
-                    else:
-                        self._error_direct(m, s, c, o, gvs, tg, err)
-                else:
-                    from . import cpu_renderer
-                    E = self._expo.detach() if (own and self.exposure) else None
-                    for i in mine:
-                        err = torch.maximum(err, cpu_renderer.blend_error(
-                            m, s, c, o, cams[i].view, cams[i].proj, self.width, self.height, targets[i],
-                            self._background(device), exposure=None if E is None else E[i]))
-        if self.world > 1:
-            dist.all_reduce(err, op=dist.ReduceOp.MAX, group=self.group)
-        if self.perm is not None:
-            canon = torch.empty_like(err)
-            canon[self.perm] = err
-            err = canon
-        return err
+
+        def cpu_view(i, m, s, c, o):
+            from . import cpu_renderer
+            E = self._expo.detach() if (own and self.exposure) else None
+            return cpu_renderer.blend_error(m, s, c, o, cams[i].view, cams[i].proj, self.width, self.height, targets[i],
+                                            self._background(device), exposure=None if E is None else E[i])
+
+        return self._gaussian_state(
+            cams, targets, "gr_error_views", tr.error_view_native, cpu_view,
+            unmet="error_state on the HIP device needs the HIP render op, float32 parameters and "
+                  f"contiguous float32 targets of shape {(self.height, self.width, 3)} on {device}: "
+                  "gr_error_view reads them through raw pointers and has no other form")
 
     def densify_and_prune(self, max_gaussians: int, densify_ratio: float, prune_opacity: float,
                           on_device: Optional[bool] = None, mode: str = "opacity", grad_threshold: float = 0.0002,

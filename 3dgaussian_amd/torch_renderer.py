@@ -912,16 +912,7 @@ def contrib_view_native(rs: RenderState, pv: Prepared, peak) -> None:
     pairs in this view.  ``rs``: the ``forward_native`` state of the view (its bins and saved sums; with or without
     images, 16-pixel tiles, a whole view); ``pv``: the ``Prepared`` it was rendered from (its geom: the raster records
     and the pairs' offsets).  Calls accumulate across views, in any order and from any streams."""
-    L = _native.lib()
-    dev = rs.saved.device
-    if pv.n != rs.n or pv.gv.width != rs.gv.width or pv.gv.height != rs.gv.height:
-        raise ValueError("prepared view does not match the render state (Gaussian count or image size)")
-    _check_operand(peak, (rs.n,), "peak", dev)
-    ws = torch.empty((int(L.gr_contrib_ws_bytes(ctypes.byref(rs.gv), rs.n, ctypes.byref(rs.plan))),), dtype=torch.uint8,
-                     device=dev)
-    _native.check(L.gr_contrib_view(ctypes.byref(rs.gv), rs.n, ctypes.byref(rs.plan), _native.ptr(pv.geom),
-                                    _native.ptr(rs.bins), _native.ptr(rs.saved), _native.ptr(peak), _native.ptr(ws),
-                                    ws.numel(), _stream(dev)), "gr_contrib_view")
+    _pair_stat_view("gr_contrib", rs, pv, peak, "peak")
 
 
 def error_view_native(rs: RenderState, pv: Prepared, target, err) -> None:
@@ -930,17 +921,25 @@ def error_view_native(rs: RenderState, pv: Prepared, target, err) -> None:
     absolute difference of the three channels between the view's colour (composed from ``rs``'s saved sums) and
     ``target`` ((H, W, 3) float32 on the device), r = 1 / (1 + W).  ``rs``, ``pv``: as contrib_view_native's.  Calls
     accumulate across views, in any order and from any streams."""
+    _pair_stat_view("gr_error", rs, pv, err, "err", target)
+
+
+def _pair_stat_view(prefix: str, rs: RenderState, pv: Prepared, stat, stat_name: str, target=None) -> None:
+    """``{prefix}_view`` with a fresh ``{prefix}_ws_bytes`` workspace: contrib_view_native (no target) and
+    error_view_native."""
     L = _native.lib()
     dev = rs.saved.device
     if pv.n != rs.n or pv.gv.width != rs.gv.width or pv.gv.height != rs.gv.height:
         raise ValueError("prepared view does not match the render state (Gaussian count or image size)")
-    _check_operand(err, (rs.n,), "err", dev)
-    _check_operand(target, (rs.gv.height, rs.gv.width, 3), "target", dev)
-    ws = torch.empty((int(L.gr_error_ws_bytes(ctypes.byref(rs.gv), rs.n, ctypes.byref(rs.plan))),), dtype=torch.uint8,
-                     device=dev)
-    _native.check(L.gr_error_view(ctypes.byref(rs.gv), rs.n, ctypes.byref(rs.plan), _native.ptr(pv.geom),
-                                  _native.ptr(rs.bins), _native.ptr(rs.saved), _native.ptr(target), _native.ptr(err),
-                                  _native.ptr(ws), ws.numel(), _stream(dev)), "gr_error_view")
+    _check_operand(stat, (rs.n,), stat_name, dev)
+    if target is not None:
+        _check_operand(target, (rs.gv.height, rs.gv.width, 3), "target", dev)
+    ws_bytes = getattr(L, prefix + "_ws_bytes")(ctypes.byref(rs.gv), rs.n, ctypes.byref(rs.plan))
+    ws = torch.empty((int(ws_bytes),), dtype=torch.uint8, device=dev)
+    targets = () if target is None else (_native.ptr(target),)
+    _native.check(getattr(L, prefix + "_view")(ctypes.byref(rs.gv), rs.n, ctypes.byref(rs.plan), _native.ptr(pv.geom),
+                                               _native.ptr(rs.bins), _native.ptr(rs.saved), *targets, _native.ptr(stat),
+                                               _native.ptr(ws), ws.numel(), _stream(dev)), prefix + "_view")
 
 
 def _grad_background(st: RenderState, background: torch.Tensor, g_out: torch.Tensor) -> torch.Tensor:

@@ -9,6 +9,7 @@ from __future__ import annotations
 import ctypes
 import importlib
 
+import numpy as np
 import pytest
 import torch
 
@@ -307,6 +308,43 @@ def test_fitter_error_state(mods, cuda, views):
     assert delta < 1e-4  # (the project's parity bar: the render is sound)
     assert bool(((got["1"].double().cpu() - ref).abs() <= tol).all())
     assert bool((got["1"][-(er.DEAD - 1):] == 0).all()) and float(got["1"][:FN].min()) > 0.0
+
+
+def _same(a, b) -> bool:
+    """Bit equality of two results: tensors, or evaluate()'s dicts of float64 arrays and floats."""
+    if isinstance(a, dict):
+        return a.keys() == b.keys() and all(np.array_equal(np.asarray(a[k]), np.asarray(b[k])) for k in a)
+    return torch.equal(a, b)
+
+
+@pytest.mark.parametrize("streams", [None, 1], ids=["streams-default", "streams-1"])
+def test_passes_share_the_executor_workspace(mods, cuda, views, streams):
+    """evaluate(), contribution_state() and error_state() interleaved on one fitter through the native executor, whose
+    streams keep one workspace for whichever pass runs (the metrics' partial sums and the pairs' values differ in
+    size): every repeated call gives the bits of its first, and each result those of a fresh fitter that made only
+    that call."""
+    _, fm = mods
+    cams, targets = fm.orbit_cameras(3, FW, FH, cuda), views[1][:3]
+    saved = _with(fm, NATIVE_EXEC="1", **({} if streams is None else {"NUM_STREAMS": streams}))
+    try:
+        def fitter():
+            f = fm.ViewShardedFitter(_raw_params(cuda), cams, targets, FW, FH)
+            f.step()
+            assert f._native_exec()
+            return f
+
+        f = fitter()
+        order = ("evaluate", "contribution_state", "error_state", "contribution_state", "evaluate", "error_state")
+        first = {}
+        for name in order:
+            got = getattr(f, name)()
+            assert _same(got, first.setdefault(name, got)), name
+        for name, got in first.items():
+            assert _same(getattr(fitter(), name)(), got), name
+        assert float(first["contribution_state"].max()) > 0.0 and float(first["error_state"].max()) > 0.0
+        assert not torch.equal(first["contribution_state"], first["error_state"]) and first["evaluate"]["mean_l1"] > 0.0
+    finally:
+        _with(fm, **saved)
 
 
 @pytest.mark.parametrize("native", ["1", "0"], ids=["executor", "python"])

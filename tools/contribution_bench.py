@@ -13,157 +13,51 @@ GPU, and the golden fit under the two pruning rules.
     python tools/contribution_bench.py [--gaussians 1000000 --views 50 --res 800] [--reps 3] [--windows 5] [--label C4]
                                        [--out FILE (appended)] [--kernel-loop | --golden]
 """
-import argparse
-import importlib
-import os
-import statistics
-import sys
-import tempfile
-import time
-
 import torch
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-fm = importlib.import_module("3dgaussian_amd.fit_multiview")
-tr = importlib.import_module("3dgaussian_amd.torch_renderer")
-bench = importlib.import_module("bench")
+from state_bench_common import emit, golden, kernel_loop, measure, parse_args
 
 
-def timed(fn, reps):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(reps):
-        fn()
-    torch.cuda.synchronize()
-    return 1e3 * (time.perf_counter() - t0) / reps
+def golden_spy(fit, a, kw, run):
+    n0 = int(fit.params["means"].shape[0])
+    by_op = int((torch.sigmoid(fit.params["opacities_raw"].detach()) <= a[2]).sum())
+    run()
+    r = getattr(fit, "contribution_report", None) if kw.get("prune_mode") == "contribution" else None
+    return n0, by_op, r, int(fit.params["means"].shape[0])
 
 
-def kernel_loop(n, R, calls, dev):
-    p = bench.synthetic_params(n, dev)
-    m, s, c, o = (t.detach().contiguous() for t in fm.activations(p))
-    cam = fm.orbit_cameras(3, R, R, dev)[1]
-    gv = tr.make_view(cam.view, cam.proj, R, R, None, depth_grad=False)
-    peak = torch.zeros((n,), device=dev)
-    for _ in range(calls):
-        pv = tr.prepare_native(m, s, c, o, gv)
-        _, _, _, rs = tr.forward_native(m, s, c, o, gv, pv, images=False)
-        tr.contrib_view_native(rs, pv, peak)
-    torch.cuda.synchronize()
-    print(f"kernel loop: {calls} x (prepare, gr_fwd_render, gr_contrib_view) at {R}x{R}, {n} Gaussians, "
-          f"{rs.plan.num_pairs} pairs ({rs.plan.num_core_pairs} core); {int((peak > 0).sum())} Gaussians with a pair")
-
-
-def golden(out):
-    """The golden three-view fit under both pruning rules, through the CLI's main()."""
-    lines = ["golden three-view fit (tests/golden/fit_targets), 300 steps, --densify_mode gradient, CLI defaults otherwise "
-             f"(128x128, 800 Gaussians, cap 3000), on {'the HIP device' if torch.cuda.is_available() else 'host tensors'}; one "
-             "run per mode, recorded and not asserted"]
-    base = fm.ViewShardedFitter
-    for mode in ("opacity", "contribution"):
-        log = []
-
-        class Spy(base):
-            def densify_and_prune(self, *a, **kw):
-                n0 = int(self.params["means"].shape[0])
-                by_op = int((torch.sigmoid(self.params["opacities_raw"].detach()) <= a[2]).sum())
-                super().densify_and_prune(*a, **kw)
-                r = getattr(self, "contribution_report", None) if kw.get("prune_mode") == "contribution" else None
-                log.append((n0, by_op, r, int(self.params["means"].shape[0])))
-
-        fm.ViewShardedFitter = Spy
-        try:
-            with tempfile.TemporaryDirectory() as d:
-                fm.main(["--targets_dir", os.path.join(REPO, "tests", "golden", "fit_targets"), "--out_dir", d, "--iters", "300",
-                         "--seed", "1", "--densify_mode", "gradient", "--prune_mode", mode])
-                loss = [float(x) for x in open(os.path.join(d, "loss.txt")).read().split()]
-        finally:
-            fm.ViewShardedFitter = base
-        lines.append(f"  --prune_mode {mode}: final loss {loss[-1]:.5f}, final N {log[-1][3]}")
-        for k, (n0, by_op, r, n1) in enumerate(log):
-            if r is None:
-                lines.append(f"    interval {k + 1} (iter {80 * (k + 1)}): N {n0}, the opacity rule pruned {by_op}; N -> {n1}")
-            else:
-                lines.append(f"    interval {k + 1} (iter {80 * (k + 1)}): N {n0}, the contribution rule pruned {r['pruned']} (peak "
-                             f"p1 {r['p1']:.2e} p10 {r['p10']:.2e} p50 {r['p50']:.2e}); the opacity rule would have pruned "
-                             f"{r['opacity_would_prune']} ({r['both']} in common); N -> {n1}")
-    text = "\n".join(lines) + "\n"
-    print(text)
-    if out:
-        with open(out, "a") as f:
-            f.write(text)
+def golden_lines(mode, loss, log):
+    lines = [f"  --prune_mode {mode}: final loss {loss[-1]:.5f}, final N {log[-1][3]}"]
+    for k, (n0, by_op, r, n1) in enumerate(log):
+        if r is None:
+            lines.append(f"    interval {k + 1} (iter {80 * (k + 1)}): N {n0}, the opacity rule pruned {by_op}; N -> {n1}")
+        else:
+            lines.append(f"    interval {k + 1} (iter {80 * (k + 1)}): N {n0}, the contribution rule pruned {r['pruned']} (peak "
+                         f"p1 {r['p1']:.2e} p10 {r['p10']:.2e} p50 {r['p50']:.2e}); the opacity rule would have pruned "
+                         f"{r['opacity_would_prune']} ({r['both']} in common); N -> {n1}")
+    return lines
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gaussians", type=int, default=1_000_000)
-    ap.add_argument("--views", type=int, default=50)
-    ap.add_argument("--res", type=int, default=800)
-    ap.add_argument("--reps", type=int, default=3, help="calls (or fit steps x 5) per window")
-    ap.add_argument("--windows", type=int, default=5)
-    ap.add_argument("--label", default="")
-    ap.add_argument("--out", default="")
-    ap.add_argument("--kernel-loop", action="store_true")
-    ap.add_argument("--golden", action="store_true")
-    args = ap.parse_args()
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    args = parse_args()
     if args.golden:
-        return golden(args.out)
+        return golden(args.out, "golden three-view fit (tests/golden/fit_targets), 300 steps, --densify_mode gradient, CLI "
+                      "defaults otherwise (128x128, 800 Gaussians, cap 3000), on "
+                      f"{'the HIP device' if torch.cuda.is_available() else 'host tensors'}; one run per mode, recorded and not "
+                      "asserted",
+                      {mode: ["--densify_mode", "gradient", "--prune_mode", mode] for mode in ("opacity", "contribution")},
+                      golden_spy, golden_lines)
     if not torch.cuda.is_available():
         raise SystemExit("contribution_bench: no HIP device (timings are taken on the GPU only)")
     dev = torch.device("cuda", 0)
-    R = args.res
     if args.kernel_loop:
-        return kernel_loop(args.gaussians, R, 20, dev)
-    cams = fm.orbit_cameras(args.views, R, R, dev)
-    g = torch.Generator(device=dev).manual_seed(3)
-    targets = [torch.rand((R, R, 3), generator=g, device=dev) for _ in cams]
-    masks = [(t.mean(dim=2) > 0.5).float() for t in targets]
-    fit = fm.ViewShardedFitter(bench.synthetic_params(args.gaussians, dev), cams, targets, R, R, masks=masks)
-    for _ in range(3):
-        fit.step()
-    fit.graph_sync()
-
-    def state(native):
-        saved = fm.NATIVE_EXEC
-        fm.NATIVE_EXEC = native
-        try:
-            return fit.contribution_state()
-        finally:
-            fm.NATIVE_EXEC = saved
-
-    ways = {"executor (gr_contrib_views)": lambda: state("1"), "Python schedule": lambda: state("0"),
-            "evaluate()": fit.evaluate}
-    res = {k: f() for k, f in ways.items()}  # warm-up, and the agreement of the two schedules
-    a, b = res["executor (gr_contrib_views)"], res["Python schedule"]
-    same = torch.equal(a, b)
-    times = {k: [] for k in ways}
-    for _ in range(args.windows):
-        for k, f in ways.items():
-            times[k].append(timed(f, args.reps))
-    step = [timed(fit.step, 5 * args.reps) for _ in range(args.windows)]
-    fit.graph_sync()
-    med = {k: statistics.median(v) for k, v in times.items()}
-    lines = [f"{args.label + ': ' if args.label else ''}{args.gaussians} Gaussians, {args.views} views, {R}x{R}, "
-             f"{torch.cuda.get_device_name(0)}; {args.windows} alternating windows of {args.reps} calls after one warm-up each, "
-             "median ms per call over all views [min .. max]"]
-    for k in ways:
-        lines.append(f"  {k:28s}: {med[k]:9.3f} ms  [{min(times[k]):.3f} .. {max(times[k]):.3f}]  {med[k] / args.views:.3f} ms per view")
-    ms = statistics.median(step)
-    key = "executor (gr_contrib_views)" if fit._native_exec() else "Python schedule"
+        return kernel_loop(args.gaussians, args.res, 20, dev, error=False)
+    lines, _, _, _, a, same = measure(args, dev, "contribution_state", "executor (gr_contrib_views)", "evaluate")
     q = torch.quantile(a.float().cpu(), torch.tensor([0.01, 0.1, 0.5, 0.99])).tolist()
-    lines.append(f"  one L1 fit step               : {ms:9.3f} ms  [{min(step):.3f} .. {max(step):.3f}]  (windows of {5 * args.reps} "
-                 f"steps); contribution_state() as the fitter's defaults run it ({key}) = {med[key] / ms:.2f} fit steps = "
-                 f"{med[key] / med['evaluate()']:.2f} evaluate()")
     lines.append(f"  executor and Python schedule {'bit-identical' if same else 'DIFFER'}; peak p1 {q[0]:.2e} p10 {q[1]:.2e} p50 "
                  f"{q[2]:.2e} p99 {q[3]:.2e}, {int((a <= 1.0 / 510.0).sum())} of {a.numel()} at or below 1/510, "
                  f"{int((a == 0).sum())} never seen")
-    text = "\n".join(lines) + "\n"
-    print(text)
-    if args.out:
-        with open(args.out, "a") as f:
-            f.write(text)
+    emit(lines, args.out)
 
 
 if __name__ == "__main__":
