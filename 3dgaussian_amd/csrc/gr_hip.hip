@@ -22,8 +22,8 @@
 //                    tile, its gradient added to the L1 term's per pixel (gr_bwd_fit_ssim; no gradient image).
 //   k_raster_bwd_bf16   per work item: the two K = 16 contractions (over x, over y) of U with the
 //                    Gaussians' exponentials; 8- or 9-float partial rows at the pairs' sorted positions.
-//   k_reduce_bwd     per Gaussian: its rows (through pos_of) summed in a fixed order (deterministic, no
-//                    float atomics), then the chain rule back to means/scales/colours/opacity.
+//   k_gather_view    per Gaussian: its rows (through pos_of) summed in a fixed order (deterministic, no
+//   k_reduce_sums    float atomics), then the chain rule back to means/scales/colours/opacity.
 //
 // The legacy uint8 surface (gr_render_u8, renderer_cpu.cpp semantics) reuses the binning with a
 // 3-sigma box, and adds exact depth-sorted front-to-back compositing (enable_depth_sort=1).
@@ -347,7 +347,7 @@ constexpr int REC4 = 2;  // float4 per record
 // Per-Gaussian pair counts of the two zones, packed core | tail << 32 into one u64; its exclusive
 // scan gives each Gaussian's first core pair (low word, in [0, Kc)) and first tail pair (high word,
 // relative to Kc: tail pairs fill [Kc, K)).  A pair's index in this emission order is also its
-// backward partial-sum slot, so each Gaussian's partials are contiguous (k_reduce_bwd).  The packed
+// backward partial-sum slot, so each Gaussian's partials are contiguous (k_gather_view).  The packed
 // words cannot carry into each other as long as K < 2^31, which k_plan checks against an exact
 // 64-bit total (Geom::total) before trusting them.
 struct Cnt2 {
@@ -440,7 +440,7 @@ struct Bins {
   int4* items;         // [cap] work items (tile, k0, k1, chunk)
   int* num_items;      // [2]: all work items, the non-empty ones (listed first; an empty tile's item comes after them)
   int* tile_item0;     // [tiles] first work item of each tile
-  int* pos_of;         // [K] sorted position of each pair, by emission index (k_reduce_bwd's map)
+  int* pos_of;         // [K] sorted position of each pair, by emission index (the reductions' map)
   int* ticket;         // [tiles] arrivals of a split tile's items (k_raster_fwd_mfma), then the finished-tile fan-in's
                        // counters (arrive_last_tile); zeroed by the work-item builder, left zero by every user
 };
@@ -3560,8 +3560,8 @@ __global__ __launch_bounds__(256, GR_BWD32_WAVES) void k_bwd32_views(VBatch<k_bw
 #endif
 constexpr int RG = GR_RG;        // Gaussians per reduce block (4 lanes each; one wave runs the chain rule)
 
-// Where the chain rule puts one view's gradient of Gaussian i: GradOut writes (or adds, acc) it to the
-// gradient buffers; GradRegs adds it to registers (k_reduce_views: several views, one write).
+// Where the chain rule puts one view's gradient of Gaussian i: GradRegs adds it to registers (several views, one
+// write); GradOut writes (or adds, acc) the total to the gradient buffers.
 struct GradOut {
   float *dm, *ds, *dc, *dop;  // Gaussian i's entries
   bool acc;
@@ -3570,136 +3570,70 @@ struct GradOut {
   __device__ void scale(int j, float x) const { put(ds + j, x); }
   __device__ void opac(float x) const { put(dop, x); }
   __device__ void color(int q, float x) const { put(dc + q, x); }
-  __device__ void none(int cd) const {  // a Gaussian on no tile: zero gradient
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      mean(q, 0.f);
-      scale(q, 0.f);
-    }
-    for (int q = 0; q < cd; ++q) color(q, 0.f);
-    opac(0.f);
-  }
   __device__ void scale_z() const { put(ds + 2, 0.f); }
 };
 template <int CD>
 struct GradRegs {
+  static constexpr int NG = 6 + CD;  // gradient floats per Gaussian (means 3, scales 2, opacity, colours)
   float m[3] = {0.f, 0.f, 0.f}, s[2] = {0.f, 0.f}, o = 0.f, c[CD] = {};
   __device__ void mean(int j, float x) { m[j] += x; }
   __device__ void scale(int j, float x) { s[j] += x; }
   __device__ void opac(float x) { o += x; }
   __device__ void color(int q, float x) { c[q] += x; }
-  __device__ void none(int) {}
-  __device__ void scale_z() {}
+  // to and from an LDS row of NG floats (the reductions combine their waves' rows, wave_rows_sum)
+  __device__ __forceinline__ void store(float* row) const {
+#pragma unroll
+    for (int q = 0; q < 3; ++q) row[q] = m[q];
+    row[3] = s[0];
+    row[4] = s[1];
+    row[5] = o;
+#pragma unroll
+    for (int q = 0; q < CD; ++q) row[6 + q] = c[q];
+  }
+  __device__ __forceinline__ void load(const float* row) {
+#pragma unroll
+    for (int q = 0; q < 3; ++q) m[q] = row[q];
+    s[0] = row[3];
+    s[1] = row[4];
+    o = row[5];
+#pragma unroll
+    for (int q = 0; q < CD; ++q) c[q] = row[6 + q];
+  }
+  // the write-out: Gaussian gi's entries of the four gradient buffers (the z scale has no gradient: zero)
+  __device__ __forceinline__ void write(int gi, float* d_means, float* d_scales, float* d_colors, float* d_opac,
+                                        int acc) const {
+    GradOut out{d_means + 3 * (size_t)gi, d_scales + 3 * (size_t)gi, d_colors + (size_t)CD * gi, d_opac + gi, acc != 0};
+#pragma unroll
+    for (int q = 0; q < 3; ++q) out.mean(q, m[q]);
+    out.scale(0, s[0]);
+    out.scale(1, s[1]);
+    out.scale_z();
+    out.opac(o);
+#pragma unroll
+    for (int q = 0; q < CD; ++q) out.color(q, c[q]);
+  }
 };
+// Sums the LDS rows of k waves (`stride` floats apart) into the first, in wave order.
+template <int NG>
+__device__ __forceinline__ void wave_rows_sum(float* row, int stride, int k) {
+#pragma unroll
+  for (int q = 0; q < NG; ++q) {
+    float t = row[q];
+    for (int u = 1; u < k; ++u) t += row[u * stride + q];
+    row[q] = t;
+  }
+}
 
 template <int CD, typename F, typename Out>
 __device__ void chain_rule(const ViewK& v, int i, const F* S, unsigned cnt, const float* __restrict__ means,
                            const float* __restrict__ scales, const float* __restrict__ colors,
                            const float* __restrict__ opac, Out& out);
 
-// Block of RG Gaussians, 4 lanes each.  A Gaussian's pairs are its emission indices: core pairs
-// [c_i, c_i + core_i) and (only with an upstream depth gradient; otherwise the backward skipped them)
-// tail pairs Kc + [t_i, t_i + tail_i); their partial sums sit at the pairs' sorted positions
-// (pos_of), where the backward splat wrote them with coalesced stores.  Lane q sums pairs q, q+4, ...
-// (core, then tail), the 4 sums are combined in a fixed order (deterministic, no atomics), and one
-// lane per Gaussian applies the chain rule.
-// ROW8: rows written by the no-depth split backward (8 floats, see bwd_item_bf16); else 9 floats.
-template <int CD, bool ROW8>
-__global__ __launch_bounds__(4 * RG) void k_reduce_bwd(ViewK v, int n, const float* __restrict__ means,
-                                                    const float* __restrict__ scales, const float* __restrict__ colors,
-                                                    const float* __restrict__ opac, const Cnt2* __restrict__ counts,
-                                                    const Cnt2* __restrict__ offsets, const int* __restrict__ pos_of,
-                                                    const float* __restrict__ partials, float* __restrict__ d_means,
-                                                    float* __restrict__ d_scales, float* __restrict__ d_colors,
-                                                    float* __restrict__ d_opac, int depth, int acc) {
-  const int g0 = blockIdx.x * RG;
-  const int tid = threadIdx.x, q4 = tid & 3;
-  const int i = g0 + (tid >> 2);
-  const long long Kc = (long long)offsets[n].c();
-  double S[NPART];
-#pragma unroll
-  for (int q = 0; q < NPART; ++q) S[q] = 0.0;
-  unsigned cnt = 0;
-  if (i < n) {
-    const Cnt2 cn = counts[i], of = offsets[i];
-    cnt = cn.v != 0 ? 1u : 0u;  // any kept tile (core or tail)
-    // pair e of this Gaussian (emission index) was written by the backward splat at its sorted
-    // position pos_of[e]: the block's Gaussians are consecutive, so within each tile their rows are
-    // one contiguous run of the sorted array
-    const int* pc = pos_of + (long long)of.c();
-    if constexpr (ROW8) {
-      // four rows per lane in flight at a time (their positions first, then the rows), summed in the
-      // same order as one row at a time
-      const float4* rows = reinterpret_cast<const float4*>(partials);
-      const int cc = (int)cn.c();
-      for (int j0 = q4; j0 < cc; j0 += 16) {
-        int pos[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) pos[u] = j0 + 4 * u < cc ? pc[j0 + 4 * u] : -1;
-        float4 ru[4], rw[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const size_t r = pos[u] >= 0 ? (size_t)pos[u] : 0;
-          ru[u] = rows[2 * r];
-          rw[u] = rows[2 * r + 1];
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          if (pos[u] < 0) break;
-          const float4 a = ru[u], w = rw[u];  // [o S0, o S2, S4, S6], [o S1, S8, S5, S7]
-          S[0] += (double)a.x;
-          S[2] += (double)a.y;
-          S[4] += (double)a.z;
-          S[6] += (double)a.w;
-          S[1] += (double)w.x;
-          S[8] += (double)w.y;
-          S[5] += (double)w.z;
-          S[7] += (double)w.w;
-        }
-      }
-    }
-    for (int j = q4; !ROW8 && j < (int)cn.c(); j += 4) {
-      {
-        const float* src = partials + (size_t)pc[j] * NPART;
-#pragma unroll
-        for (int q = 0; q < NPART; ++q) S[q] += (double)src[q];
-      }
-    }
-    if (depth) {
-      const int* pt = pos_of + Kc + (long long)of.t();
-      for (int j = q4; j < (int)cn.t(); j += 4) {
-        const float* src = partials + (size_t)pt[j] * NPART;
-#pragma unroll
-        for (int q = 0; q < NPART; ++q) S[q] += (double)src[q];
-      }
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < NPART; ++q) {
-    S[q] += __shfl_xor(S[q], 1);
-    S[q] += __shfl_xor(S[q], 2);
-  }
-  // the block's sums -> LDS; then one lane per Gaussian (wave 0, every lane busy) runs the chain rule
-  // in f32 (the reference's autograd precision)
-  __shared__ float sS[RG][NPART + 1];
-  if (q4 == 0) {
-#pragma unroll
-    for (int q = 0; q < NPART; ++q) sS[tid >> 2][q] = (float)S[q];
-    sS[tid >> 2][NPART] = cnt ? 1.0f : 0.0f;
-  }
-  __syncthreads();
-  if (tid >= RG || g0 + tid >= n) return;
-  float Sf[NPART];
-#pragma unroll
-  for (int q = 0; q < NPART; ++q) Sf[q] = sS[tid][q];
-  const int gi = g0 + tid;
-  GradOut out{d_means + 3 * (size_t)gi, d_scales + 3 * (size_t)gi, d_colors + (size_t)CD * gi, d_opac + gi, acc != 0};
-  chain_rule<CD, float>(v, gi, Sf, sS[tid][NPART] != 0.0f ? 1u : 0u, means, scales, colors, opac, out);
-}
-
 // Batched reduction (gr_reduce_views): the 8-float rows of up to GR_REDUCE_MAX_VIEWS views rendered
-// without a depth gradient, one pass over the Gaussians.  Per view a Gaussian's rows are gathered as in
-// k_reduce_bwd (4 lanes, fixed order, double sums); the chain rules then run one lane per Gaussian,
+// without a depth gradient, one pass over the Gaussians.  A Gaussian's pairs are its emission indices, core pairs
+// [c_i, c_i + core_i); their rows sit at the pairs' sorted positions (pos_of), where the backward splat wrote them
+// with coalesced stores.  Per view, lane q of the Gaussian's 4 sums rows q, q + 4, ... and the 4 sums are combined in a
+// fixed order (double sums; deterministic, no atomics); the chain rules then run one lane per Gaussian,
 // wave w taking views w, w + 4 (CRW = 4 waves; SH degree 3: wave 0 alone), their gradients summed in
 // registers and the wave sums combined in wave order: the parameters are read and the gradient written
 // (or added to, acc) once per batch instead of once per view.  Deterministic.
@@ -3721,7 +3655,7 @@ __global__ __launch_bounds__(4 * RG) void k_reduce_views(RBatch B, int n, const 
                                                       float* __restrict__ d_scales, float* __restrict__ d_colors,
                                                       float* __restrict__ d_opac, int acc) {
   constexpr int CRW = CD == 48 ? 1 : 4;  // waves running chain rules
-  constexpr int NG = 6 + CD;             // gradient floats per Gaussian (means 3, scales 2, opacity, colours)
+  constexpr int NG = GradRegs<CD>::NG;
   constexpr int VG = 8;                  // views staged in LDS at a time
   // per view and Gaussian: the 9 sums; S3 (the depth sum) is 0 without a depth gradient, so its slot
   // carries the "on any tile" flag
@@ -3822,44 +3756,14 @@ __global__ __launch_bounds__(4 * RG) void k_reduce_views(RBatch B, int n, const 
   }
   }
   if constexpr (CRW > 1) {
-    if (w < CRW) {
-      float* mine = sG[w][lane];
-#pragma unroll
-      for (int q = 0; q < 3; ++q) mine[q] = gr.m[q];
-      mine[3] = gr.s[0];
-      mine[4] = gr.s[1];
-      mine[5] = gr.o;
-#pragma unroll
-      for (int q = 0; q < CD; ++q) mine[6 + q] = gr.c[q];
-    }
+    if (w < CRW) gr.store(sG[w][lane]);
     __syncthreads();
     if (w != 0 || gi >= n) return;
-#pragma unroll
-    for (int q = 0; q < NG; ++q) {
-      float t = sG[0][lane][q];
-#pragma unroll
-      for (int u = 1; u < CRW; ++u) t += sG[u][lane][q];
-      sG[0][lane][q] = t;
-    }
-    const float* tot = sG[0][lane];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) gr.m[q] = tot[q];
-    gr.s[0] = tot[3];
-    gr.s[1] = tot[4];
-    gr.o = tot[5];
-#pragma unroll
-    for (int q = 0; q < CD; ++q) gr.c[q] = tot[6 + q];
+    wave_rows_sum<NG>(sG[0][lane], RG * (NG + 1), CRW);
+    gr.load(sG[0][lane]);
   }
   if (w != 0 || gi >= n) return;
-  GradOut out{d_means + 3 * (size_t)gi, d_scales + 3 * (size_t)gi, d_colors + (size_t)CD * gi, d_opac + gi, acc != 0};
-#pragma unroll
-  for (int q = 0; q < 3; ++q) out.mean(q, gr.m[q]);
-  out.scale(0, gr.s[0]);
-  out.scale(1, gr.s[1]);
-  out.scale_z();
-  out.opac(gr.o);
-#pragma unroll
-  for (int q = 0; q < CD; ++q) out.color(q, gr.c[q]);
+  gr.write(gi, d_means, d_scales, d_colors, d_opac, acc);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -4130,9 +4034,22 @@ struct SViewK {
   const float* sums3;  // [n] depth sums o S3 (k_gather_view<true>), or null (no depth gradient: S3 = 0)
 };
 struct SBatch {
-  int nv;
+  int nv = 0;
   SViewK r[GR_REDUCE_MAX_VIEWS];
+  void add(const ViewK& v, const float* sums, const float* sums3) { r[nv++] = SViewK{v, (const float4*)sums, sums3}; }
 };
+// Row i of a view's gathered sums, unpacked: [o S0, o S2, S4, S6 | o S1, S8, S5, S7] -> S0..S8 (S3, the depth sum, is
+// 0 without a depth gradient).  Returns whether the view saw the Gaussian: a row that is all zero touched no tile (its
+// chain rule, statistic or camera term would add zero).  The one statement of the layout for every consumer.
+__device__ __forceinline__ bool sums_row(const SViewK& r, size_t i, float (&S)[NPART]) {
+  const float4 a = r.sums[2 * i], b = r.sums[2 * i + 1];
+  const float s3 = r.sums3 ? r.sums3[i] : 0.0f;
+  const float row[NPART] = {a.x, b.x, a.y, s3, a.z, b.z, a.w, b.w, b.y};
+#pragma unroll
+  for (int q = 0; q < NPART; ++q) S[q] = row[q];
+  return a.x != 0.f || a.y != 0.f || a.z != 0.f || a.w != 0.f || b.x != 0.f || b.y != 0.f || b.z != 0.f || b.w != 0.f ||
+         s3 != 0.f;
+}
 // waves per Gaussian group of k_reduce_sums (host and device)
 __host__ __device__ constexpr int reduce_sums_crw(int nv, int cd) { return nv >= 3 ? 4 : (nv >= 1 ? nv : 1); }
 
@@ -4144,7 +4061,7 @@ __global__ __launch_bounds__(256) void k_reduce_sums(SBatch B, int n, const floa
                                                      float* __restrict__ d_opac, int acc, const int* __restrict__ sum_index) {
   // sum_index (gr_bwd_indexed): Gaussian gi's sums are row sum_index[gi] of the views' sums (a render of a permuted
   // copy); its parameters and gradients stay row gi
-  constexpr int NG = 6 + CD;
+  constexpr int NG = GradRegs<CD>::NG;
   __shared__ float sG[4][64][NG + 1];
   const int crw = reduce_sums_crw(B.nv, CD);
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
@@ -4154,53 +4071,22 @@ __global__ __launch_bounds__(256) void k_reduce_sums(SBatch B, int n, const floa
   if (gi < n) {
     const size_t si = sum_index ? (size_t)sum_index[gi] : (size_t)gi;
     for (int vi = u; vi < B.nv; vi += crw) {
-      const float4 a = B.r[vi].sums[2 * si], b = B.r[vi].sums[2 * si + 1];
-      // [o S0, o S2, S4, S6 | o S1, S8, S5, S7] -> S0..S8 (S3, the depth sum, is 0 without a depth gradient)
-      const float s3 = B.r[vi].sums3 ? B.r[vi].sums3[si] : 0.0f;
-      const float Sf[NPART] = {a.x, b.x, a.y, s3, a.z, b.z, a.w, b.w, b.y};
-      const unsigned on = (a.x != 0.f || a.y != 0.f || a.z != 0.f || a.w != 0.f || b.x != 0.f || b.y != 0.f ||
-                           b.z != 0.f || b.w != 0.f || s3 != 0.f) ? 1u : 0u;
+      float Sf[NPART];
+      const unsigned on = sums_row(B.r[vi], si, Sf) ? 1u : 0u;
       chain_rule<CD, float>(B.r[vi].v, gi, Sf, on, means, scales, colors, opac, gr);
     }
   }
   {
     if (crw > 1) {  // uniform per launch
-      float* mine = sG[w][lane];
-#pragma unroll
-      for (int q = 0; q < 3; ++q) mine[q] = gr.m[q];
-      mine[3] = gr.s[0];
-      mine[4] = gr.s[1];
-      mine[5] = gr.o;
-#pragma unroll
-      for (int q = 0; q < CD; ++q) mine[6 + q] = gr.c[q];
+      gr.store(sG[w][lane]);
       __syncthreads();
       if (u != 0 || gi >= n) return;
-#pragma unroll
-      for (int q = 0; q < NG; ++q) {
-        float t = sG[w][lane][q];
-        for (int v = 1; v < crw; ++v) t += sG[w + v][lane][q];
-        sG[w][lane][q] = t;
-      }
-      const float* tot = sG[w][lane];
-#pragma unroll
-      for (int q = 0; q < 3; ++q) gr.m[q] = tot[q];
-      gr.s[0] = tot[3];
-      gr.s[1] = tot[4];
-      gr.o = tot[5];
-#pragma unroll
-      for (int q = 0; q < CD; ++q) gr.c[q] = tot[6 + q];
+      wave_rows_sum<NG>(sG[w][lane], 64 * (NG + 1), crw);
+      gr.load(sG[w][lane]);
     }
   }
   if (u != 0 || gi >= n) return;
-  GradOut out{d_means + 3 * (size_t)gi, d_scales + 3 * (size_t)gi, d_colors + (size_t)CD * gi, d_opac + gi, acc != 0};
-#pragma unroll
-  for (int q = 0; q < 3; ++q) out.mean(q, gr.m[q]);
-  out.scale(0, gr.s[0]);
-  out.scale(1, gr.s[1]);
-  out.scale_z();
-  out.opac(gr.o);
-#pragma unroll
-  for (int q = 0; q < CD; ++q) out.color(q, gr.c[q]);
+  gr.write(gi, d_means, d_scales, d_colors, d_opac, acc);
 }
 
 // Density statistics of a batch of gathered views (gr_density_stats): one lane per Gaussian, the views in batch
@@ -4220,16 +4106,13 @@ __global__ __launch_bounds__(256) void k_density_stats(SBatch B, int n, const fl
   const float o = op < 0.0f ? 0.0f : op;
   float g = 0.0f, seen = 0.0f;
   for (int vi = 0; vi < B.nv; ++vi) {
-    const float4 a = B.r[vi].sums[2 * (size_t)i], b = B.r[vi].sums[2 * (size_t)i + 1];
-    const float s3 = B.r[vi].sums3 ? B.r[vi].sums3[i] : 0.0f;
-    const bool on = a.x != 0.f || a.y != 0.f || a.z != 0.f || a.w != 0.f || b.x != 0.f || b.y != 0.f || b.z != 0.f ||
-                    b.w != 0.f || s3 != 0.f;
-    if (!on) continue;
+    float S[NPART];
+    if (!sums_row(B.r[vi], (size_t)i, S)) continue;
     const ViewK& v = B.r[vi].v;
     Proj p;
     project(v, mx, my, mz, s0, s1, p);
-    // [o S0, o S2, S4, S6 | o S1, S8, S5, S7]: the position moments S5 = b.z, S6 = a.w
-    const float dpx = o * b.z / (p.sx * p.sx), dpy = o * a.w / (p.sy * p.sy);
+    // the position moments S5, S6
+    const float dpx = o * S[5] / (p.sx * p.sx), dpy = o * S[6] / (p.sy * p.sy);
     const float dndx = dpx * 0.5f * (v.W - 1), dndy = dpy * 0.5f * (v.H - 1);
     g += inv_g_scale * hypotf(dndx, dndy);
     seen += 1.0f;
@@ -4242,7 +4125,7 @@ __global__ __launch_bounds__(256) void k_density_stats(SBatch B, int n, const fl
 
 // The projection half of the chain rule (torch_renderer.py:57-78, 146-150) from a Gaussian's sums S (SURVEY.md
 // App. A): the gradients of its clamped sigmas, of its camera-space point pc and of its clip-space point (shared
-// by chain_rule and the camera gradient, k_camera_grad).
+// by chain_rule and the camera gradient, k_camera_grad_views).
 template <typename F>
 struct ProjGrad {
   F dsx, dsy;   // d L / d sigma_x, sigma_y (zero where the clamp at 1 is active)
@@ -4332,10 +4215,7 @@ __device__ void chain_rule(const ViewK& v, int i, const F* S, unsigned cnt, cons
   const float s0 = scales[3 * i], s1 = scales[3 * i + 1];
   const float op = opac[i];
   const float* col = colors + (size_t)CD * i;
-  if (cnt == 0) {
-    out.none(CD);
-    return;
-  }
+  if (cnt == 0) return;  // on no tile of the view: nothing to add
   Proj p;
   project(v, mx, my, mz, s0, s1, p);
   const F o = op < 0.0f ? F(0) : (F)op;
@@ -4347,7 +4227,6 @@ __device__ void chain_rule(const ViewK& v, int i, const F* S, unsigned cnt, cons
   const F sgy = s1 > 0.f ? F(1) : (s1 < 0.f ? F(-1) : F(0));
   out.scale(0, (float)(pg.dsx * kx * sgx));
   out.scale(1, (float)(pg.dsy * ky * sgy));
-  out.scale_z();
   F dm[3];
 #pragma unroll
   for (int j = 0; j < 3; ++j) {
@@ -4378,36 +4257,48 @@ __device__ void chain_rule(const ViewK& v, int i, const F* S, unsigned cnt, cons
 }
 
 // ------------------------------------------------------------------------------------------------
-// Camera gradient (gr_bwd_camera).  The reference's camera is differentiable: view and proj are ordinary
-// torch operands of _project, of the SH view direction (cam = inv(view)[:3,3]) and of the sigma rule
+// Camera gradient (gr_bwd_camera: one view; gr_camera_grads_sums: a batch).  The reference's camera is
+// differentiable: view and proj are ordinary torch operands of _project, of the SH view direction (cam = inv(view)[:3,3]) and of the sigma rule
 // (torch_renderer.py:57-83, 140-150), so a caller whose camera tensors require grad gets d view / d proj.
 // From a view's per-Gaussian sums (k_gather_view's output, the same the chain rule reads), each Gaussian's
 //   d view += d pc (m, 1)^T,   d proj += d clip pc^T,   d proj[0][0] += d sigma_x |s0| W / (2 z) sign(P00)
 //   (the same for [1][1]),   d cam += d L / d (cam - m)  (SH colours),
 // summed per block in double (wave butterfly, then the four waves in order) and over the blocks by
-// k_camera_final (one wave per component, fixed order): deterministic.  The host turns d cam into
+// k_camera_final_views (one wave per component, fixed order): deterministic.  The host turns d cam into
 // d view through the inverse (torch_renderer.py:81-83).
 // ------------------------------------------------------------------------------------------------
 constexpr int CAM_GRADS = 35;  // d view (16, row-major), d proj (16), d cam_pos (3)
+
+// One lane per Gaussian: its parameters, loaded once per kernel.
+struct CamLane {
+  int i;
+  bool live;
+  float mx = 0.f, my = 0.f, mz = 0.f, s0 = 0.f, s1 = 0.f, op = 0.f;
+  __device__ __forceinline__ CamLane(int n, const float* __restrict__ means, const float* __restrict__ scales,
+                                     const float* __restrict__ opac)
+      : i(blockIdx.x * 256 + (int)threadIdx.x), live(i < n) {
+    if (live) {
+      mx = means[3 * (size_t)i], my = means[3 * (size_t)i + 1], mz = means[3 * (size_t)i + 2];
+      s0 = scales[3 * (size_t)i], s1 = scales[3 * (size_t)i + 1];
+      op = opac[i];
+    }
+  }
+};
+// One view's camera gradient over the block: each lane's terms above from the view's sums row (sums_row; a row that is
+// all zero adds nothing), the block reduction (wave butterfly in double, then the four waves in order through the LDS
+// rows `row`) and the block's partial to part[vi][block][CAM_GRADS].  The body of both kernels below.
 template <int CD>
-__global__ __launch_bounds__(256) void k_camera_grad(ViewK v, int n, const float* __restrict__ means,
-                                                     const float* __restrict__ scales, const float* __restrict__ colors,
-                                                     const float* __restrict__ opac, const float4* __restrict__ sums,
-                                                     const float* __restrict__ sums3, double* __restrict__ part) {
+__device__ __forceinline__ void camera_grad_view(const SViewK& r, int vi, const CamLane& g, const float* __restrict__ colors,
+                                                 double (*row)[CAM_GRADS], double* __restrict__ part) {
+  const float mx = g.mx, my = g.my, mz = g.mz, s0 = g.s0, s1 = g.s1, op = g.op;
+  const int i = g.i, w = (int)threadIdx.x >> 6;
   double acc[CAM_GRADS];
 #pragma unroll
   for (int q = 0; q < CAM_GRADS; ++q) acc[q] = 0.0;
-  const int i = blockIdx.x * 256 + (int)threadIdx.x;
-  if (i < n) {
-    const float4 a = sums[2 * (size_t)i], b = sums[2 * (size_t)i + 1];
-    const float s3 = sums3 ? sums3[i] : 0.0f;
-    const float S[NPART] = {a.x, b.x, a.y, s3, a.z, b.z, a.w, b.w, b.y};
-    const bool on = a.x != 0.f || a.y != 0.f || a.z != 0.f || a.w != 0.f || b.x != 0.f || b.y != 0.f || b.z != 0.f ||
-                    b.w != 0.f || s3 != 0.f;
-    if (on) {
-      const float mx = means[3 * i], my = means[3 * i + 1], mz = means[3 * i + 2];
-      const float s0 = scales[3 * i], s1 = scales[3 * i + 1];
-      const float op = opac[i];
+  if (g.live) {
+    float S[NPART];
+    if (sums_row(r, (size_t)i, S)) {
+      const ViewK& v = r.v;
       Proj p;
       project(v, mx, my, mz, s0, s1, p);
       ProjGrad<float> pg;
@@ -4436,104 +4327,44 @@ __global__ __launch_bounds__(256) void k_camera_grad(ViewK v, int n, const float
   for (int q = 0; q < CAM_GRADS; ++q)
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) acc[q] += __shfl_xor(acc[q], m);
-  __shared__ double sh[4][CAM_GRADS];
-  const int w = (int)threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0)
 #pragma unroll
-    for (int q = 0; q < CAM_GRADS; ++q) sh[w][q] = acc[q];
+    for (int q = 0; q < CAM_GRADS; ++q) row[w][q] = acc[q];
   __syncthreads();
   if ((int)threadIdx.x < CAM_GRADS) {
     const int q = threadIdx.x;
-    part[(size_t)blockIdx.x * CAM_GRADS + q] = ((sh[0][q] + sh[1][q]) + sh[2][q]) + sh[3][q];
+    part[((size_t)vi * gridDim.x + blockIdx.x) * CAM_GRADS + q] = ((row[0][q] + row[1][q]) + row[2][q]) + row[3][q];
   }
 }
 
-// Block partials -> the view's camera gradient: block q sums component q over the blocks (lane l takes blocks
-// l, l + 64, ..., then a butterfly), in a fixed order.
-__global__ __launch_bounds__(64) void k_camera_final(const double* __restrict__ part, int blocks, float* __restrict__ out) {
-  const int q = blockIdx.x, lane = threadIdx.x;
-  double s = 0.0;
-  for (int b = lane; b < blocks; b += 64) s += part[(size_t)b * CAM_GRADS + q];
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m);
-  if (lane == 0) out[q] = (float)s;
+// One view (gr_bwd_camera, the drop-in route).  A kernel of its own rather than a batch of one: the batch kernel's
+// registers (167 / 181 / 190 VGPRs against 130 / 142 / 142 here) cost the one-view call 1 % (RGB) to 3 % (SH degree 3)
+// at 1M Gaussians (profiles/sums_stage_refactor.txt).
+template <int CD>
+__global__ __launch_bounds__(256) void k_camera_grad(SViewK r, int n, const float* __restrict__ means,
+                                                     const float* __restrict__ scales, const float* __restrict__ colors,
+                                                     const float* __restrict__ opac, double* __restrict__ part) {
+  __shared__ double sh[4][CAM_GRADS];
+  camera_grad_view<CD>(r, 0, CamLane(n, means, scales, opac), colors, sh, part);
 }
 
-// Camera gradients of a batch of gathered views (gr_camera_grads_sums: the fit's pose refinement).  One lane per
-// Gaussian, its parameters loaded once for the batch, then the views in batch order: per view k_camera_grad's
-// terms from the view's sums row (k_reduce_sums' unpacking and `on` test; a row that is all zero adds nothing),
-// its block reduction (wave butterfly in double, then the four waves in order) and the block's partial to
-// part[view][block][CAM_GRADS].  The LDS rows alternate between two sets, so one barrier per view orders them.  A
-// view's partials depend on nothing but that view: its row is the same bits whatever shares the batch.
+// A batch of gathered views (gr_camera_grads_sums: the fit's pose refinement): the parameters loaded once for the
+// batch, then the views in batch order.  The LDS rows alternate between two sets, so one barrier per view orders them.
+// A view's partials depend on nothing but that view: its row is the same bits whatever shares the batch, and the same
+// as k_camera_grad's.
 template <int CD>
 __global__ __launch_bounds__(256) void k_camera_grad_views(SBatch B, int n, const float* __restrict__ means,
                                                            const float* __restrict__ scales,
                                                            const float* __restrict__ colors,
                                                            const float* __restrict__ opac, double* __restrict__ part) {
   __shared__ double sh[2][4][CAM_GRADS];
-  const int i = blockIdx.x * 256 + (int)threadIdx.x;
-  const int w = (int)threadIdx.x >> 6;
-  const bool live = i < n;
-  float mx = 0.f, my = 0.f, mz = 0.f, s0 = 0.f, s1 = 0.f, op = 0.f;
-  if (live) {
-    mx = means[3 * (size_t)i], my = means[3 * (size_t)i + 1], mz = means[3 * (size_t)i + 2];
-    s0 = scales[3 * (size_t)i], s1 = scales[3 * (size_t)i + 1];
-    op = opac[i];
-  }
-  for (int vi = 0; vi < B.nv; ++vi) {
-    double acc[CAM_GRADS];
-#pragma unroll
-    for (int q = 0; q < CAM_GRADS; ++q) acc[q] = 0.0;
-    if (live) {
-      const float4 a = B.r[vi].sums[2 * (size_t)i], b = B.r[vi].sums[2 * (size_t)i + 1];
-      const float s3 = B.r[vi].sums3 ? B.r[vi].sums3[i] : 0.0f;
-      const float S[NPART] = {a.x, b.x, a.y, s3, a.z, b.z, a.w, b.w, b.y};
-      const bool on = a.x != 0.f || a.y != 0.f || a.z != 0.f || a.w != 0.f || b.x != 0.f || b.y != 0.f || b.z != 0.f ||
-                      b.w != 0.f || s3 != 0.f;
-      if (on) {
-        const ViewK& v = B.r[vi].v;
-        Proj p;
-        project(v, mx, my, mz, s0, s1, p);
-        ProjGrad<float> pg;
-        proj_grads<float>(v, p, op < 0.0f ? 0.0f : op, S, pg);
-        const float mh[4] = {mx, my, mz, 1.0f};
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            acc[r * 4 + j] = (double)pg.dpc[r] * (double)mh[j];
-            acc[16 + r * 4 + j] = (double)pg.dclip[r] * (double)p.pc[j];
-          }
-        const float sg0 = v.P[0] > 0.f ? 1.f : (v.P[0] < 0.f ? -1.f : 0.f);
-        const float sg5 = v.P[5] > 0.f ? 1.f : (v.P[5] < 0.f ? -1.f : 0.f);
-        acc[16 + 0] += (double)(pg.dsx * (fabsf(s0) * 0.5f * (float)v.W / p.za) * sg0);
-        acc[16 + 5] += (double)(pg.dsy * (fabsf(s1) * 0.5f * (float)v.H / p.za) * sg5);
-        if constexpr (CD != 3) {
-          ColGrad<CD, float> cg;
-          color_grads<CD, float>(v, mx, my, mz, colors + (size_t)CD * i, S, cg);
-#pragma unroll
-          for (int j = 0; j < 3; ++j) acc[32 + j] = (double)cg.dd[j];
-        }
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < CAM_GRADS; ++q)
-#pragma unroll
-      for (int m = 32; m >= 1; m >>= 1) acc[q] += __shfl_xor(acc[q], m);
-    double(*row)[CAM_GRADS] = sh[vi & 1];
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-      for (int q = 0; q < CAM_GRADS; ++q) row[w][q] = acc[q];
-    __syncthreads();
-    if ((int)threadIdx.x < CAM_GRADS) {
-      const int q = threadIdx.x;
-      part[((size_t)vi * gridDim.x + blockIdx.x) * CAM_GRADS + q] = ((row[0][q] + row[1][q]) + row[2][q]) + row[3][q];
-    }
-  }
+  const CamLane g(n, means, scales, opac);
+  for (int vi = 0; vi < B.nv; ++vi) camera_grad_view<CD>(B.r[vi], vi, g, colors, sh[vi & 1], part);
 }
 
-// k_camera_final over a (component, view) grid: block (q, vi) sums component q of view vi over the blocks in
-// k_camera_final's order and writes the view's own output row.
+// Block partials -> the views' camera gradients, over a (component, view) grid: block (q, vi) sums component q of
+// view vi over the blocks (lane l takes blocks l, l + 64, ..., then a butterfly), in a fixed order, and writes the
+// view's own output row.
 struct CamRows {
   float* out[GR_REDUCE_MAX_VIEWS];
 };
@@ -6237,6 +6068,66 @@ gr_status gr_fwd_render_l1(const gr_view* v, int n, const gr_plan* plan, const v
 static bool ssim_shape_ok(int height, int width, int channels);
 static size_t ssim_partial_bytes(int height, int width);
 
+// ---- The host side of a consumer of gathered sums.  `name` is the entry point's, for its
+// messages.  An entry point checks its view count first (sums_batch_count) and builds the batch after its own
+// argument checks (sums_batch), so the two are separate calls; one that has a resolved view and the workspace's
+// sums (bwd_impl, gr_bwd_camera) uses SBatch::add directly.
+static gr_status sums_batch_count(const char* name, int num_views, int lo) {
+  if (num_views < lo || num_views > GR_REDUCE_MAX_VIEWS)
+    return set_error(GR_ERR_INVALID_ARGUMENT,
+                     std::string(name) + ": num_views must be in [" + std::to_string(lo) + ", GR_REDUCE_MAX_VIEWS]");
+  return GR_OK;
+}
+// skip_bands: a band of tile rows (gr_view.rows) is checked and left out
+static gr_status sums_batch(const char* name, int num_views, const gr_sums_view* views, bool skip_bands, SBatch& B) {
+  for (int k = 0; k < num_views; ++k) {
+    gr_status st = check_view(&views[k].view);
+    if (st != GR_OK) return st;
+    if (!views[k].sums) return set_error(GR_ERR_INVALID_ARGUMENT, std::string(name) + ": null sums");
+    if (skip_bands && views[k].view.rows > 0) continue;
+    B.add(make_viewk(&views[k].view), views[k].sums, views[k].sums3);
+  }
+  return GR_OK;
+}
+
+// The chain rule of a batch's sums (an empty batch: zero gradients, or with accumulate the buffers as they are).
+// opened: the caller has recorded the first mark of the PROF_REDUCE pair (its gather belongs to the pair).
+static gr_status launch_reduce_sums(const SBatch& B, int n, const float* means, const float* scales, const float* colors,
+                                    int color_dim, const float* opacities, float* d_means, float* d_scales,
+                                    float* d_colors, float* d_opacities, int accumulate, const int* sum_index,
+                                    bool opened, hipStream_t s) {
+  if (!opened) prof_mark(PROF_REDUCE, s);
+  const int gpb = 64 * (4 / reduce_sums_crw(B.nv, color_dim));
+  const dim3 grid((n + gpb - 1) / gpb), block(256);
+  with_color_dim(color_dim, [&](auto cd) {
+    hipLaunchKernelGGL(k_reduce_sums<cd()>, grid, block, 0, s, B, n, means, scales, colors, opacities, d_means, d_scales,
+                       d_colors, d_opacities, accumulate, sum_index);
+  });
+  GR_HIP_TRY(hipGetLastError());
+  prof_mark(PROF_REDUCE, s);
+  return GR_OK;
+}
+
+// The camera gradients of a batch's sums into d_camera[0 .. B.nv); part holds gr_camera_grads_ws_bytes(n, B.nv).
+// one_view (gr_bwd_camera): B holds one view, which takes the one-view kernel.
+static gr_status launch_camera_grads(const SBatch& B, int n, const float* means, const float* scales, const float* colors,
+                                     int color_dim, const float* opacities, float* const* d_camera, double* part,
+                                     bool one_view, hipStream_t s) {
+  CamRows rows;
+  for (int k = 0; k < GR_REDUCE_MAX_VIEWS; ++k) rows.out[k] = k < B.nv ? d_camera[k] : nullptr;
+  const int blocks = blocks_for(n);
+  with_color_dim(color_dim, [&](auto cd) {
+    if (one_view)
+      hipLaunchKernelGGL(k_camera_grad<cd()>, dim3(blocks), dim3(256), 0, s, B.r[0], n, means, scales, colors, opacities, part);
+    else
+      hipLaunchKernelGGL(k_camera_grad_views<cd()>, dim3(blocks), dim3(256), 0, s, B, n, means, scales, colors, opacities, part);
+  });
+  GR_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_camera_final_views, dim3(CAM_GRADS, B.nv), dim3(64), 0, s, (const double*)part, blocks, rows);
+  GR_HIP_TRY(hipGetLastError());
+  return GR_OK;
+}
+
 static gr_status bwd_impl(const gr_view* v, int n, const gr_plan* plan, const float* means, const float* scales,
                           const float* colors, int color_dim, const float* opacities, const void* geom, const void* bins,
                           const float* saved, const float* g_rgb, const float* g_alpha, const float* g_depth,
@@ -6275,11 +6166,9 @@ static gr_status bwd_impl(const gr_view* v, int n, const gr_plan* plan, const fl
   const ViewCtx c = view_ctx(v, n, plan, geom, bins, nullptr, ws);
   const ViewK& vk = c.vk;
   const int tiles = c.tiles;
-  const Geom& g = c.g;
   const Bins& b = c.b;
   const size_t HW = c.HW;
   const BwdWs& w = c.w;
-  float* partials = w.partials;
   uint4* UF = w.UF;
   const bool dfit = t_rgb && t_depth;  // fused depth loss (gr_bwd_fit)
   // the view loss: written by k_pixel_grads' last tile
@@ -6324,7 +6213,7 @@ static gr_status bwd_impl(const gr_view* v, int n, const gr_plan* plan, const fl
   if (num_pairs > 0) {
     // 32-byte rows: the lean gather into per-Gaussian sums (with a depth gradient also the tail pairs and
     // the depth sums), then the chain rule of that one view (the two stages of gr_gather_view +
-    // gr_reduce_sums; k_reduce_bwd's one pass needs 117 VGPRs for the chain rule while it gathers)
+    // gr_reduce_sums; a one-pass kernel needs 117 VGPRs for the chain rule while it gathers)
     float* sums = gather_only ? g_sums : w.sums;
     float* sums3 = gather_only ? g_sums3 : w.sums3;
     launch_one(depth ? k_gather_view<true> : k_gather_view<false>, dim3((n + 63) / 64), 256, 0, s,
@@ -6336,36 +6225,21 @@ static gr_status bwd_impl(const gr_view* v, int n, const gr_plan* plan, const fl
       return GR_OK;
     }
     SBatch B;
-    B.nv = 1;
-    B.r[0].v = vk;
-    B.r[0].sums = (const float4*)w.sums;
-    B.r[0].sums3 = depth ? w.sums3 : nullptr;
-    const int gpb = 64 * (4 / reduce_sums_crw(1, color_dim));
-    const dim3 grid((n + gpb - 1) / gpb), block(256);
-    with_color_dim(color_dim, [&](auto cd) {
-      hipLaunchKernelGGL(k_reduce_sums<cd()>, grid, block, 0, s, B, n, means, scales, colors, opacities, d_means, d_scales,
-                         d_colors, d_opacities, accumulate, sum_index);
-    });
-  } else if (gather_only) {  // no pair: every sum is zero
+    B.add(vk, w.sums, depth ? w.sums3 : nullptr);
+    return launch_reduce_sums(B, n, means, scales, colors, color_dim, opacities, d_means, d_scales, d_colors, d_opacities,
+                              accumulate, sum_index, true, s);
+  }
+  if (gather_only) {  // no pair: every sum is zero
     GR_HIP_TRY(hipMemsetAsync(g_sums, 0, gr_view_sums_floats(n) * sizeof(float), s));
     if (g_sums3) GR_HIP_TRY(hipMemsetAsync(g_sums3, 0, (size_t)n * sizeof(float), s));
-  } else {
-    // the backward without a depth gradient writes 8-float rows (bwd_item_bf16).  No pair: every sum is zero, so
-    // the one-pass kernel's rows are the parameters' own (the gradients are zero or the accumulator unchanged in any
-    // order: sum_index needs no mapping here)
-    const bool row8 = !depth;
-    auto launch = [&](auto kern) {
-      hipLaunchKernelGGL(kern, dim3((n + RG - 1) / RG), dim3(4 * RG), 0, s, vk, n, means, scales, colors, opacities,
-                         (const Cnt2*)g.counts, (const Cnt2*)g.offsets, (const int*)b.pos_of, (const float*)partials,
-                         d_means, d_scales, d_colors, d_opacities, depth ? 1 : 0, accumulate);
-    };
-    with_color_dim(color_dim, [&](auto cd) {
-      row8 ? launch(k_reduce_bwd<cd(), true>) : launch(k_reduce_bwd<cd(), false>);
-    });
+    GR_HIP_TRY(hipGetLastError());
+    prof_mark(PROF_REDUCE, s);
+    return GR_OK;
   }
-  GR_HIP_TRY(hipGetLastError());
-  prof_mark(PROF_REDUCE, s);
-  return GR_OK;
+  // No pair: every sum is zero, so the chain rule of an empty batch writes the result (the gradients are zero or the
+  // accumulator unchanged, whatever the row: sum_index needs no mapping here)
+  return launch_reduce_sums(SBatch{}, n, means, scales, colors, color_dim, opacities, d_means, d_scales, d_colors,
+                            d_opacities, accumulate, nullptr, true, s);
 }
 
 extern "C" {
@@ -6670,8 +6544,7 @@ gr_status gr_gather_view(const gr_view* v, int n, const gr_plan* plan, const voi
 gr_status gr_reduce_sums(int num_views, const gr_sums_view* views, int n, const float* means, const float* scales,
                          const float* colors, int color_dim, const float* opacities, float* d_means, float* d_scales,
                          float* d_colors, float* d_opacities, int accumulate, void* stream) {
-  if (num_views < 0 || num_views > GR_REDUCE_MAX_VIEWS)
-    return set_error(GR_ERR_INVALID_ARGUMENT, "gr_reduce_sums: num_views must be in [0, GR_REDUCE_MAX_VIEWS]");
+  if (gr_status st = sums_batch_count("gr_reduce_sums", num_views, 0); st != GR_OK) return st;
   if (gr_status st = check_color_dim(color_dim); st != GR_OK) return st;
   if (n < 0) return set_error(GR_ERR_INVALID_ARGUMENT, "n must be >= 0");
   if (n == 0) return GR_OK;
@@ -6679,49 +6552,21 @@ gr_status gr_reduce_sums(int num_views, const gr_sums_view* views, int n, const 
       (num_views > 0 && !views))
     return set_error(GR_ERR_INVALID_ARGUMENT, "null pointer");
   SBatch B;
-  B.nv = num_views;
-  for (int k = 0; k < num_views; ++k) {
-    gr_status st = check_view(&views[k].view);
-    if (st != GR_OK) return st;
-    if (!views[k].sums) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_reduce_sums: null sums");
-    B.r[k].v = make_viewk(&views[k].view);
-    B.r[k].sums = (const float4*)views[k].sums;
-    B.r[k].sums3 = views[k].sums3;
-  }
-  hipStream_t s = (hipStream_t)stream;
+  if (gr_status st = sums_batch("gr_reduce_sums", num_views, views, false, B); st != GR_OK) return st;
   if (GR_DEBUG_SKIP & 8) return GR_OK;
-  prof_mark(PROF_REDUCE, s);
-  const int gpb = 64 * (4 / reduce_sums_crw(num_views, color_dim));
-  const dim3 grid((n + gpb - 1) / gpb), block(256);
-  with_color_dim(color_dim, [&](auto cd) {
-    hipLaunchKernelGGL(k_reduce_sums<cd()>, grid, block, 0, s, B, n, means, scales, colors, opacities, d_means, d_scales,
-                       d_colors, d_opacities, accumulate, (const int*)nullptr);
-  });
-  GR_HIP_TRY(hipGetLastError());
-  prof_mark(PROF_REDUCE, s);
-  return GR_OK;
+  return launch_reduce_sums(B, n, means, scales, colors, color_dim, opacities, d_means, d_scales, d_colors, d_opacities,
+                            accumulate, nullptr, false, (hipStream_t)stream);
 }
 
 gr_status gr_density_stats(int num_views, const gr_sums_view* views, int n, const float* means, const float* scales,
                            const float* opacities, float inv_g_scale, float* stats, void* stream) {
-  if (num_views < 1 || num_views > GR_REDUCE_MAX_VIEWS)
-    return set_error(GR_ERR_INVALID_ARGUMENT, "gr_density_stats: num_views must be in [1, GR_REDUCE_MAX_VIEWS]");
+  if (gr_status st = sums_batch_count("gr_density_stats", num_views, 1); st != GR_OK) return st;
   if (n < 0) return set_error(GR_ERR_INVALID_ARGUMENT, "n must be >= 0");
   if (n == 0) return GR_OK;
   if (!views || !means || !scales || !opacities || !stats)
     return set_error(GR_ERR_INVALID_ARGUMENT, "gr_density_stats: null pointer");
-  SBatch B;
-  B.nv = 0;
-  for (int k = 0; k < num_views; ++k) {
-    gr_status st = check_view(&views[k].view);
-    if (st != GR_OK) return st;
-    if (!views[k].sums) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_density_stats: null sums");
-    if (views[k].view.rows > 0) continue;  // a band: its partial gradient norm is no share of the view's
-    B.r[B.nv].v = make_viewk(&views[k].view);
-    B.r[B.nv].sums = (const float4*)views[k].sums;
-    B.r[B.nv].sums3 = views[k].sums3;
-    ++B.nv;
-  }
+  SBatch B;  // without the bands: a band's partial gradient norm is no share of the view's
+  if (gr_status st = sums_batch("gr_density_stats", num_views, views, true, B); st != GR_OK) return st;
   if (B.nv == 0) return GR_OK;
   hipLaunchKernelGGL(k_density_stats, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, B, n, means, scales,
                      opacities, inv_g_scale, (float2*)stats);
@@ -6737,8 +6582,7 @@ size_t gr_camera_grads_ws_bytes(int n, int num_views) {
 gr_status gr_camera_grads_sums(int num_views, const gr_sums_view* views, int n, const float* means, const float* scales,
                                const float* colors, int color_dim, const float* opacities, float* const* d_camera,
                                void* ws, size_t ws_bytes, void* stream) {
-  if (num_views < 1 || num_views > GR_REDUCE_MAX_VIEWS)
-    return set_error(GR_ERR_INVALID_ARGUMENT, "gr_camera_grads_sums: num_views must be in [1, GR_REDUCE_MAX_VIEWS]");
+  if (gr_status st = sums_batch_count("gr_camera_grads_sums", num_views, 1); st != GR_OK) return st;
   if (gr_status st = check_color_dim(color_dim); st != GR_OK) return st;
   if (n < 0) return set_error(GR_ERR_INVALID_ARGUMENT, "n must be >= 0");
   if (!d_camera) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_camera_grads_sums: null output rows");
@@ -6752,29 +6596,10 @@ gr_status gr_camera_grads_sums(int num_views, const gr_sums_view* views, int n, 
   if (!views || !means || !scales || !colors || !opacities || !ws)
     return set_error(GR_ERR_INVALID_ARGUMENT, "gr_camera_grads_sums: null pointer");
   SBatch B;
-  CamRows rows;
-  B.nv = num_views;
-  for (int k = 0; k < num_views; ++k) {
-    gr_status st = check_view(&views[k].view);
-    if (st != GR_OK) return st;
-    if (!views[k].sums) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_camera_grads_sums: null sums");
-    B.r[k].v = make_viewk(&views[k].view);
-    B.r[k].sums = (const float4*)views[k].sums;
-    B.r[k].sums3 = views[k].sums3;
-    rows.out[k] = d_camera[k];
-  }
-  for (int k = num_views; k < GR_REDUCE_MAX_VIEWS; ++k) rows.out[k] = nullptr;
+  if (gr_status st = sums_batch("gr_camera_grads_sums", num_views, views, false, B); st != GR_OK) return st;
   if (ws_bytes < gr_camera_grads_ws_bytes(n, num_views))
     return set_error(GR_ERR_WORKSPACE, "gr_camera_grads_sums: workspace too small");
-  const int blocks = blocks_for(n);
-  double* part = (double*)ws;
-  with_color_dim(color_dim, [&](auto cd) {
-    hipLaunchKernelGGL(k_camera_grad_views<cd()>, dim3(blocks), dim3(256), 0, s, B, n, means, scales, colors, opacities, part);
-  });
-  GR_HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_camera_final_views, dim3(CAM_GRADS, num_views), dim3(64), 0, s, (const double*)part, blocks, rows);
-  GR_HIP_TRY(hipGetLastError());
-  return GR_OK;
+  return launch_camera_grads(B, n, means, scales, colors, color_dim, opacities, d_camera, (double*)ws, false, s);
 }
 
 gr_status gr_bwd_camera(const gr_view* v, int n, const gr_plan* plan, const float* means, const float* scales,
@@ -6795,19 +6620,10 @@ gr_status gr_bwd_camera(const gr_view* v, int n, const gr_plan* plan, const floa
   }
   if (!means || !scales || !colors || !opacities || !ws) return set_error(GR_ERR_INVALID_ARGUMENT, "null pointer");
   if (ws_bytes < gr_bwd_bytes(v, n, plan)) return set_error(GR_ERR_WORKSPACE, "backward workspace too small");
-  const ViewK vk = make_viewk(v);
-  const BwdWs w = bwd_ws(v, n, plan, ws);
-  const int blocks = blocks_for(n);
-  const float4* sums = (const float4*)w.sums;
-  const float* sums3 = depth ? (const float*)w.sums3 : nullptr;
-  with_color_dim(color_dim, [&](auto cd) {
-    hipLaunchKernelGGL(k_camera_grad<cd()>, dim3(blocks), dim3(256), 0, s, vk, n, means, scales, colors, opacities, sums, sums3,
-                       w.cam_part);
-  });
-  GR_HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_camera_final, dim3(CAM_GRADS), dim3(64), 0, s, (const double*)w.cam_part, blocks, d_camera);
-  GR_HIP_TRY(hipGetLastError());
-  return GR_OK;
+  const BwdWs w = bwd_ws(v, n, plan, ws);  // cam_part: the one-view workspace, gr_camera_grads_ws_bytes(n, 1)
+  SBatch B;
+  B.add(make_viewk(v), w.sums, depth ? w.sums3 : nullptr);
+  return launch_camera_grads(B, n, means, scales, colors, color_dim, opacities, &d_camera, w.cam_part, true, s);
 }
 
 gr_status gr_render_u8(const gr_render_params* p, int n, const float* means, const float* scales, const float* colors,

@@ -800,6 +800,21 @@ def backward_fit_ssim_gather_native(st: RenderState, target, mask, w_sil: float,
     return sums, sums3
 
 
+def _sums_views(batch, n: int, dev):
+    """The gr_sums_view array of a batch of gathered views, [(gr_view, sums (n, 8)[, depth sums (n,) or None]), ...] on
+    ``dev``: what every consumer of gathered sums passes (an empty batch: one unused entry)."""
+    arr = (_native.GrSumsView * max(1, len(batch)))()
+    for k, item in enumerate(batch):
+        gv, sums = item[0], item[1]
+        sums3 = item[2] if len(item) > 2 else None
+        _check_operand(sums, (n, 8), "sums", dev)
+        _check_operand(sums3, (n,), "sums3", dev)
+        arr[k].view = gv
+        arr[k].sums = sums.data_ptr()
+        arr[k].sums3 = sums3.data_ptr() if sums3 is not None else None
+    return arr
+
+
 def reduce_sums_native(means, scales, colors, opacities, batch, grads, accumulate: bool) -> None:
     """gr_reduce_sums on the current stream: ``batch`` = [(gr_view, sums from gather_view_native), ...] or
     [(gr_view, sums, depth sums from backward_fit_gather_native), ...] (at most _native.REDUCE_MAX_VIEWS); the views'
@@ -810,15 +825,7 @@ def reduce_sums_native(means, scales, colors, opacities, batch, grads, accumulat
         raise ValueError(f"at most {_native.REDUCE_MAX_VIEWS} views per gr_reduce_sums batch")
     _check_params(means, scales, colors, opacities)
     n = int(means.shape[0])
-    arr = (_native.GrSumsView * max(1, len(batch)))()
-    for k, item in enumerate(batch):
-        gv, sums = item[0], item[1]
-        sums3 = item[2] if len(item) > 2 else None
-        _check_operand(sums, (n, 8), "sums", means.device)
-        _check_operand(sums3, (n,), "sums3", means.device)
-        arr[k].view = gv
-        arr[k].sums = sums.data_ptr()
-        arr[k].sums3 = sums3.data_ptr() if sums3 is not None else None
+    arr = _sums_views(batch, n, means.device)
     for g, p, nm in zip(grads, (means, scales, colors, opacities), ("d_means", "d_scales", "d_colors", "d_opacities")):
         _check_operand(g, tuple(p.shape), nm, means.device)
     dm, ds, dc, do = grads
@@ -842,15 +849,7 @@ def density_stats_native(means, scales, opacities, batch, inv_g_scale: float, st
     _check_operand(scales, (n, 3), "scales", dev)
     _check_operand(opacities, (n,), "opacities", dev)
     _check_operand(stats, (n, 2), "stats", dev)
-    arr = (_native.GrSumsView * len(batch))()
-    for k, item in enumerate(batch):
-        gv, sums = item[0], item[1]
-        sums3 = item[2] if len(item) > 2 else None
-        _check_operand(sums, (n, 8), "sums", dev)
-        _check_operand(sums3, (n,), "sums3", dev)
-        arr[k].view = gv
-        arr[k].sums = sums.data_ptr()
-        arr[k].sums3 = sums3.data_ptr() if sums3 is not None else None
+    arr = _sums_views(batch, n, dev)
     _native.check(L.gr_density_stats(len(batch), arr, n, _native.ptr(means), _native.ptr(scales), _native.ptr(opacities),
                                      ctypes.c_float(inv_g_scale), _native.ptr(stats), _stream(dev)), "gr_density_stats")
 
@@ -869,18 +868,11 @@ def camera_grads_sums_native(means, scales, colors, opacities, batch, rows, ws=N
     _check_params(means, scales, colors, opacities)
     n = int(means.shape[0])
     dev = means.device
-    arr = (_native.GrSumsView * len(batch))()
+    arr = _sums_views(batch, n, dev)
     out = (ctypes.c_void_p * len(batch))()
-    for k, item in enumerate(batch):
-        gv, sums = item[0], item[1]
-        sums3 = item[2] if len(item) > 2 else None
-        _check_operand(sums, (n, 8), "sums", dev)
-        _check_operand(sums3, (n,), "sums3", dev)
-        _check_operand(rows[k], (_native.CAMERA_GRADS,), "rows", dev)
-        arr[k].view = gv
-        arr[k].sums = sums.data_ptr()
-        arr[k].sums3 = sums3.data_ptr() if sums3 is not None else None
-        out[k] = rows[k].data_ptr()
+    for k, row in enumerate(rows):
+        _check_operand(row, (_native.CAMERA_GRADS,), "rows", dev)
+        out[k] = row.data_ptr()
     need = int(L.gr_camera_grads_ws_bytes(n, len(batch)))
     if ws is None:
         ws = torch.empty((max(need, 8),), dtype=torch.uint8, device=dev)

@@ -146,6 +146,48 @@ def test_edge_cases_and_argument_errors(pkg, cuda):
         tr.camera_grads_sums_native(m, s, c, o, [(batch[0][0], batch[0][1][:-1])], list(rows[:1]))
 
 
+@pytest.mark.parametrize("depth", [True, False])
+@pytest.mark.parametrize("cd", [3, 12, 48])
+@pytest.mark.parametrize("n", [300, 257])
+def test_backward_camera_equals_a_one_view_batch(pkg, cuda, n, cd, depth):
+    """gr_bwd_camera on the workspace of a view's gr_bwd_fit and a one-view gr_camera_grads_sums on the sums
+    gr_bwd_fit_gather returns for the same arguments: the same 35 floats, bit for bit, with a depth target (depth = 1,
+    the depth sums) and without one (depth = 0, sums3 null).  n = 300: the oracle scene; 257: a second block of one lane."""
+    tr, nat = pkg.torch_renderer, pkg._native
+    L, r = nat.lib(), ctypes.byref
+    W, H = 64, 48
+    sc = orc.synthetic_scene(n, seed=1)
+    colors = sc.colors if cd == 3 else _colors(n, cd, seed=n + cd)
+    t = [torch.from_numpy(np.ascontiguousarray(a)).to(cuda) for a in (sc.means, sc.scales, colors, sc.opacities)]
+    view, proj = orc.orbit_cameras(8, W, H)[1]
+    g = torch.Generator(device=cuda).manual_seed(12)
+    target = torch.rand((H, W, 3), generator=g, device=cuda)
+    mask = (target.mean(dim=2) > 0.5).float().contiguous()
+    dtarget = torch.rand((H, W), generator=g, device=cuda) if depth else None
+    w_sil, w_depth, g_scale = 0.2, 0.05 if depth else 0.0, 0.25
+    gv = tr.make_view(view, proj, W, H, None, depth_grad=depth)
+    _, _, _, st = tr.forward_native(*t, gv, tr.prepare_native(*t, gv))
+    assert st.plan.num_pairs > 0
+    # route A: the view's backward into a workspace kept here, then the one-view entry point on that workspace
+    ws = torch.empty((int(L.gr_bwd_bytes(r(gv), n, r(st.plan))),), dtype=torch.uint8, device=cuda)
+    grads = [torch.empty_like(x) for x in t]
+    loss_a, loss_b = torch.zeros(1, device=cuda), torch.zeros(1, device=cuda)
+    nat.check(L.gr_bwd_fit(r(gv), n, r(st.plan), nat.ptr(t[0]), nat.ptr(t[1]), nat.ptr(t[2]), cd, nat.ptr(t[3]),
+                           nat.ptr(st.geom), nat.ptr(st.bins), nat.ptr(st.saved), nat.ptr(target), nat.ptr(mask),
+                           ctypes.c_float(w_sil), nat.ptr(dtarget), ctypes.c_float(w_depth), ctypes.c_float(g_scale),
+                           nat.ptr(loss_a), *[nat.ptr(x) for x in grads], 0, nat.ptr(ws), ws.numel(),
+                           ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "gr_bwd_fit")
+    row_a = tr.camera_grad_native(*t, st, ws, depth)
+    # route B: the same backward up to its sums, then the batch entry point with one view
+    sums, sums3 = tr.backward_fit_gather_native(st, target, mask, w_sil, dtarget, w_depth, g_scale, loss_b)
+    row_b = torch.full((CG,), float("nan"), device=cuda)
+    tr.camera_grads_sums_native(*t, [(st.gv, sums, sums3) if depth else (st.gv, sums)], [row_b])
+    torch.cuda.synchronize()
+    assert torch.equal(loss_a, loss_b)
+    assert torch.equal(row_a, row_b)
+    assert float(row_a[:16].abs().sum()) > 0.0 and float(row_a[16:32].abs().sum()) > 0.0
+
+
 # ---- through the fused path against the float64 dense reference -------------------------------------------------------
 def _e2e_scene(case):
     if case == "rgb_n300":

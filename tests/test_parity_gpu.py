@@ -291,3 +291,67 @@ def test_prepared_view_matches_direct_render(pkg, cuda):
         res.append([out.detach().cpu().numpy()] + [x.grad.cpu().numpy() for x in t])
     for a, b in zip(*res):
         np.testing.assert_array_equal(a, b)
+
+
+# ---- a view without a pair through the backward -------------------------------------------------------------------------
+@pytest.mark.parametrize("cd", [3, 12, 48])
+@pytest.mark.parametrize("n", [1, 255, 257])
+def test_backward_of_a_view_without_pairs(pkg, cuda, n, cd):
+    """No Gaussian reaches a tile (the scene sits behind the camera): gr_bwd, gr_bwd_indexed and gr_bwd_l1 write exact
+    zeros into every entry of the four gradients (the z column of d_scales included), gr_bwd_l1 with accumulate leaves
+    the buffers bit for bit and returns the background's loss, gr_bwd_camera gives 35 zeros.  n: one partial block of
+    the 256-Gaussian write-out, one block less a lane, and a second block of one lane."""
+    import ctypes
+
+    tr, nat = pkg.torch_renderer, pkg._native
+    L, r = nat.lib(), ctypes.byref
+    W, H = 64, 48
+    view, proj = orc.orbit_cameras(4, W, H)[1]
+    sc = orc.synthetic_scene(n, seed=3, scale=0.08)
+    rng = np.random.default_rng(10 * n + cd)
+    colors = rng.uniform(0.0, 1.0, (n, 3) if cd == 3 else (n, cd // 3, 3)).astype(np.float32)
+    means = sc.means + 2.0 * orc.camera_position(view)
+    t = [torch.from_numpy(np.ascontiguousarray(a)).to(cuda) for a in (means, sc.scales, colors, sc.opacities)]
+    background = np.array([0.1, 0.6, 0.3], np.float32)
+    gv = tr.make_view(view, proj, W, H, background, depth_grad=False)
+    out, alpha, _, st = tr.forward_native(*t, gv)
+    assert st.plan.num_pairs == 0
+    g = torch.Generator(device=cuda).manual_seed(n + cd)
+    g_out = torch.randn((H, W, 3), generator=g, device=cuda)
+    g_alpha = torch.randn((H, W), generator=g, device=cuda)
+    target = torch.rand((H, W, 3), generator=g, device=cuda)
+    mask = (target.mean(dim=2) > 0.5).float().contiguous()
+    index = torch.arange(n - 1, -1, -1, dtype=torch.int32, device=cuda)  # the reverse order: no identity from n = 2
+    ws = torch.empty((max(8, int(L.gr_bwd_bytes(r(gv), n, r(st.plan)))),), dtype=torch.uint8, device=cuda)
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    p = [nat.ptr(t[0]), nat.ptr(t[1]), nat.ptr(t[2]), cd, nat.ptr(t[3]), nat.ptr(st.geom), nat.ptr(st.bins), nat.ptr(st.saved)]
+    w_sil, loss = 0.25, torch.full((1,), float("nan"), device=cuda)
+
+    def run(entry, fill, accumulate=0):
+        grads = [torch.full_like(x, fill) for x in t]
+        d = [nat.ptr(x) for x in grads]
+        if entry == "gr_bwd":
+            st_ = L.gr_bwd(r(gv), n, r(st.plan), *p, nat.ptr(g_out), nat.ptr(g_alpha), None, *d, nat.ptr(ws), ws.numel(), stream)
+        elif entry == "gr_bwd_indexed":
+            st_ = L.gr_bwd_indexed(r(gv), n, r(st.plan), *p, nat.ptr(g_out), nat.ptr(g_alpha), None, nat.ptr(index), *d,
+                                   nat.ptr(ws), ws.numel(), stream)
+        else:
+            st_ = L.gr_bwd_l1(r(gv), n, r(st.plan), *p, nat.ptr(target), nat.ptr(mask), ctypes.c_float(w_sil),
+                              ctypes.c_float(0.5), nat.ptr(loss), *d, accumulate, nat.ptr(ws), ws.numel(), stream)
+        nat.check(st_, entry)
+        torch.cuda.synchronize()
+        return grads
+
+    for entry in ("gr_bwd", "gr_bwd_indexed", "gr_bwd_l1"):
+        for x, name in zip(run(entry, float("nan")), GRAD_KEYS):
+            assert x.shape == t[GRAD_KEYS.index(name)].shape and bool((x == 0.0).all()), (entry, name)
+    for fill in (1.5, -3.25e-7):
+        for x, name in zip(run("gr_bwd_l1", fill, accumulate=1), GRAD_KEYS):
+            assert torch.equal(x, torch.full_like(x, fill)), (fill, name)
+    assert not alpha.any() and torch.equal(out, torch.from_numpy(background).to(cuda).expand(H, W, 3))
+    want = float((out.double() - target.double()).abs().mean() + w_sil * mask.double().mean())
+    assert abs(float(loss) - want) <= 1e-5 * want
+    d_cam = torch.full((nat.CAMERA_GRADS,), float("nan"), device=cuda)
+    nat.check(L.gr_bwd_camera(r(gv), n, r(st.plan), *p[:5], nat.ptr(ws), ws.numel(), 0, nat.ptr(d_cam), stream), "gr_bwd_camera")
+    torch.cuda.synchronize()
+    assert bool((d_cam == 0.0).all())
