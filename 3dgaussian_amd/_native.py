@@ -78,6 +78,10 @@ CAMERA_GRADS = 35  # GR_CAMERA_GRADS: d view (16), d proj (16), d cam_pos (3)
 REDUCE_MAX_VIEWS = 16  # GR_REDUCE_MAX_VIEWS
 PREPARE_MAX_VIEWS = 8  # GR_PREPARE_MAX_VIEWS
 EVAL_METRICS = 3  # GR_EVAL_METRICS: mean|x - y|, mean (x - y)^2, mean SSIM of gr_eval_view
+CC_MOMENTS = 22  # GR_CC_MOMENTS: the 10 + 12 double moments of the colour-correction fit
+CC_TRANSFORM = 12  # GR_CC_TRANSFORM: the affine colour transform E, 3 x 4 row-major
+CC_RIDGE = 1e-6  # GR_CC_RIDGE: the default ridge of gr_cc_fit_view
+EVAL_CC_ROW = 18  # GR_EVAL_CC_ROW: gr_eval_views_cc's row (the 3 metrics, the 3 corrected ones, E)
 
 
 class GrReduceView(ctypes.Structure):
@@ -226,6 +230,11 @@ _SIG = {
     "gr_eval_view": (ctypes.c_int, [_VP, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "gr_eval_views": (ctypes.c_int, [_P, ctypes.POINTER(GrFitConfig), ctypes.c_int, ctypes.POINTER(GrFitTarget), ctypes.c_int,
                                      _P, _P, _P, ctypes.c_int, _P, _P, _P]),
+    "gr_cc_ws_bytes": (ctypes.c_size_t, [_VP]),
+    "gr_cc_fit_view": (ctypes.c_int, [_VP, _P, _P, ctypes.c_float, _P, _P, ctypes.c_size_t, _P]),
+    "gr_eval_view_cc": (ctypes.c_int, [_VP, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "gr_eval_views_cc": (ctypes.c_int, [_P, ctypes.POINTER(GrFitConfig), ctypes.c_int, ctypes.POINTER(GrFitTarget),
+                                        ctypes.c_int, _P, _P, _P, ctypes.c_int, _P, ctypes.c_float, _P, _P]),
     "gr_contrib_ws_bytes": (ctypes.c_size_t, [_VP, ctypes.c_int, _PP]),
     "gr_contrib_view": (ctypes.c_int, [_VP, ctypes.c_int, _PP, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "gr_contrib_views": (ctypes.c_int, [_P, ctypes.POINTER(GrFitConfig), ctypes.c_int, ctypes.POINTER(GrFitTarget),

@@ -15,9 +15,10 @@
 // must grow is replaced after its stream has drained (rare: the first step, a densify).
 // The schedule (streams, preparation groups, reduction batches) is exactly fit_multiview._views_direct's,
 // so both give bit-identical losses and gradients (tests/test_fit_exec_gpu.py).
-// gr_eval_views, gr_contrib_views and gr_error_views are the same schedule without a backward (a render-only pass): per
-// view gr_fwd_render (saved sums only) and the pass's one call (gr_eval_view into the view's row of metrics; gr_contrib_view
-// or gr_error_view, every view into the caller's one buffer), with one pass workspace per render stream; a pass writes
+// gr_eval_views, gr_eval_views_cc, gr_contrib_views and gr_error_views are the same schedule without a backward (a
+// render-only pass): per view gr_fwd_render (saved sums only) and the pass's calls on them (gr_eval_view into the view's row
+// of metrics, for gr_eval_views_cc followed by gr_cc_fit_view and gr_eval_view_cc into the same row; gr_contrib_view or
+// gr_error_view, every view into the caller's one buffer), with one pass workspace per render stream; a pass writes
 // nothing but those workspaces and the caller's output.
 #include <hip/hip_runtime.h>
 
@@ -84,7 +85,7 @@ struct Buf {
 
 struct StreamWs {  // one render stream's buffers
   Buf bins, scratch, ws, saved;
-  Buf pass;                      // a render-only pass's workspace: gr_eval_view's partial sums or the pairs' values
+  Buf pass;                      // a render-only pass's workspace: the metrics' or moments' partial sums, or the pairs' values
   Buf cam;                       // gr_executor_camera_grads: a batch's camera-gradient partials
   std::vector<Buf> sums, sums3;  // one per view of a reduction batch (sums3: the depth-loss path's depth sums)
 };
@@ -125,8 +126,9 @@ struct gr_executor {
 // What is done with each view: the fit (loss, backward, reductions) or a render-only pass (no losses, accumulators or
 // statistics: per view the render and one call that reads its saved sums).
 struct Pass {
-  enum Kind { fit, eval, contrib, error } kind = fit;
-  float* out = nullptr;  // eval: the views' metrics rows; contrib, error: the one per-Gaussian buffer
+  enum Kind { fit, eval, contrib, error, eval_cc } kind = fit;
+  float* out = nullptr;  // eval, eval_cc: the views' rows; contrib, error: the one per-Gaussian buffer
+  float ridge = 0.0f;    // eval_cc: gr_cc_fit_view's
   bool fwd_only() const { return kind != fit; }
 };
 
@@ -284,6 +286,15 @@ gr_status gr_eval_views(gr_executor* ex, const gr_fit_config* cfg, int num_views
                         float* metrics, void* stream) {
   return pass_views_checked("gr_eval_views", {Pass::eval, metrics}, ex, cfg, num_views, views, n, means, scales, colors,
                             color_dim, opacities, stream);
+}
+
+gr_status gr_eval_views_cc(gr_executor* ex, const gr_fit_config* cfg, int num_views, const gr_fit_target* views, int n,
+                           const float* means, const float* scales, const float* colors, int color_dim,
+                           const float* opacities, float ridge, float* rows, void* stream) {
+  if (!(ridge > 0.0f) || !(ridge <= 3.402823466e38f))  // (as gr_cc_fit_view, before anything is enqueued)
+    return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, "gr_eval_views_cc: ridge must be positive and finite");
+  return pass_views_checked("gr_eval_views_cc", {Pass::eval_cc, rows, ridge}, ex, cfg, num_views, views, n, means, scales,
+                            colors, color_dim, opacities, stream);
 }
 
 gr_status gr_contrib_views(gr_executor* ex, const gr_fit_config* cfg, int num_views, const gr_fit_target* views, int n,
@@ -495,9 +506,11 @@ static gr_status enqueue_views(gr_executor* ex, const gr_fit_config* cfg, int nu
     if (!fwd_only) GR_EXEC_TRY(W.ws.fit(ws_bytes, s));
     void *bins = W.bins.p, *scratch = W.scratch.p, *ws = W.ws.p;
     if (fwd_only) {
-      // the saved sums only (no image, no depth output), then the pass's one call on them: the view's metrics, or its
-      // pairs' values into the one per-Gaussian buffer (atomic maxima)
+      // the saved sums only (no image, no depth output), then the pass's calls on them: the view's metrics (eval_cc: its
+      // three calls one after another on this stream, so the workspace is the larger of the two sizes), or its pairs'
+      // values into the one per-Gaussian buffer (atomic maxima)
       const size_t pass_bytes = pass.kind == Pass::eval      ? gr_eval_ws_bytes(&v)
+                                : pass.kind == Pass::eval_cc ? std::max(gr_eval_ws_bytes(&v), gr_cc_ws_bytes(&v))
                                 : pass.kind == Pass::contrib ? gr_contrib_ws_bytes(&v, n, &plan)
                                                              : gr_error_ws_bytes(&v, n, &plan);
       GR_EXEC_TRY(W.saved.fit(gr_saved_floats(&v) * sizeof(float), s));
@@ -507,7 +520,13 @@ static gr_status enqueue_views(gr_executor* ex, const gr_fit_config* cfg, int nu
       const float* saved = (const float*)W.saved.p;
       if (pass.kind == Pass::eval)
         GR_EXEC_CALL(gr_eval_view(&v, saved, views[j].target_rgb, pass.out + (size_t)GR_EVAL_METRICS * j, W.pass.p, W.pass.cap, s));
-      else if (pass.kind == Pass::contrib)
+      else if (pass.kind == Pass::eval_cc) {
+        float* row = pass.out + (size_t)GR_EVAL_CC_ROW * j;
+        float* E = row + 2 * GR_EVAL_METRICS;
+        GR_EXEC_CALL(gr_eval_view(&v, saved, views[j].target_rgb, row, W.pass.p, W.pass.cap, s));
+        GR_EXEC_CALL(gr_cc_fit_view(&v, saved, views[j].target_rgb, pass.ridge, E, W.pass.p, W.pass.cap, s));
+        GR_EXEC_CALL(gr_eval_view_cc(&v, saved, views[j].target_rgb, E, row + GR_EVAL_METRICS, W.pass.p, W.pass.cap, s));
+      } else if (pass.kind == Pass::contrib)
         GR_EXEC_CALL(gr_contrib_view(&v, n, &plan, geom[j], bins, saved, pass.out, W.pass.p, W.pass.cap, s));
       else
         GR_EXEC_CALL(gr_error_view(&v, n, &plan, geom[j], bins, saved, views[j].target_rgb, pass.out, W.pass.p, W.pass.cap, s));

@@ -4778,6 +4778,14 @@ __global__ __launch_bounds__(256) void k_ssim_final(const float* __restrict__ pa
   if (t == 0) *dssim = (float)(1.0 - r[0] / (double)n);
 }
 
+// The affine colour transform of the corrected metrics (include/gr_hip.h): E row-major [3][4], row k the output channel,
+//   y_k = ((E[k][0] x0 + E[k][1] x1) + E[k][2] x2) + E[k][3],
+// every product and sum rounded on its own in that order (what element-wise float32 operations on an image give).
+__device__ __forceinline__ float cc_apply(const float* e, int k, const float x[3]) {
+  return __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(e[4 * k], x[0]), __fmul_rn(e[4 * k + 1], x[1])), __fmul_rn(e[4 * k + 2], x[2])),
+                   e[4 * k + 3]);
+}
+
 // View metrics for held-out evaluation (gr_eval_view): k_ssim_fwd<3, false> of a view's render against its target with
 // the rendered image staged from the saved sums as k_ssim_fwd_saved does (same grid, the same partial sums of m bit for
 // bit, no maps), and from the same two staged windows, without a second global read, the tile's sums of |x - y| and
@@ -4834,6 +4842,190 @@ __global__ __launch_bounds__(256) void k_eval_view(ViewK v, const float4* __rest
     const int tile = blockIdx.y * gridDim.x + blockIdx.x;
     partial[plane + tile] = red[0];
     partial[2 * plane + tile] = red2[0];
+  }
+}
+
+// gr_eval_view_cc: k_eval_view of the colour-corrected render.  The staged render is E (x, 1) (cc_apply, E = 12 device
+// floats read once per workgroup; not clamped) inside the image and, as for any image, zero outside it; everything
+// behind the staging, the grid, the LDS and the partial sums are k_eval_view's, and k_eval_final then gives the three
+// corrected metrics.  A kernel of its own rather than k_eval_view's body as a template over "apply E": moving that body
+// into a function (forced inline or not, the view by reference or by value) made k_eval_view itself compile to other
+// instructions (its background select; 37 -> 44 SGPRs), which a held-out metric that tests pin bit for bit is not worth.
+__global__ __launch_bounds__(256) void k_eval_view_cc(ViewK v, const float4* __restrict__ saved4, const float* __restrict__ y,
+                                                      const float* __restrict__ E, float* __restrict__ partial, int plane) {
+  constexpr int C = 3, TC = ST * C, SP = SE * C;
+  __shared__ float tx[SE * SP], ty[SE * SP];
+  __shared__ float hs[5][SE * TC];
+  __shared__ float red[256];
+  const int H = v.H, W = v.W, WC = W * C;
+  const int t = threadIdx.x;
+  const int y0 = blockIdx.y * ST, x0 = blockIdx.x * ST, v0 = blockIdx.x * TC;
+  float em[GR_CC_TRANSFORM];
+#pragma unroll
+  for (int i = 0; i < GR_CC_TRANSFORM; ++i) em[i] = E[i];
+  for (int e = t; e < SE * SE; e += 256) {
+    const int r = e / SE, c = e - r * SE;
+    const int gy = y0 - SR + r, gx = x0 - SR + c;
+    float px[3] = {0.0f, 0.0f, 0.0f};
+    if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
+      const float4 s = saved4[(int64_t)gy * W + gx];
+      float x[3];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) x[k] = saved_colour(v, s, k);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) px[k] = cc_apply(em, k, x);
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) tx[r * SP + c * C + k] = px[k];
+  }
+  ssim_stage<C>(y, H, WC, y0, v0, ty);
+  __syncthreads();
+  float a1 = 0.0f, a2 = 0.0f;
+  for (int o = t; o < ST * TC; o += 256) {
+    const int r = o / TC, c = o - r * TC;
+    if (y0 + r < H && v0 + c < WC) {
+      const int at = (r + SR) * SP + SR * C + c;
+      const float d = tx[at] - ty[at];
+      a1 += fabsf(d);
+      a2 = fmaf(d, d, a2);
+    }
+  }
+  ssim_fwd_tile<C, false, 2>(tx, ty, hs, red, H, W, partial, nullptr);
+  float* red2 = &hs[0][0];  // (as k_eval_view: hs is free behind ssim_fwd_tile's last barrier)
+  red[t] = a1;
+  red2[t] = a2;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (t < w) {
+      red[t] += red[t + w];
+      red2[t] += red2[t + w];
+    }
+    __syncthreads();
+  }
+  if (t == 0) {
+    const int tile = blockIdx.y * gridDim.x + blockIdx.x;
+    partial[plane + tile] = red[0];
+    partial[2 * plane + tile] = red2[0];
+  }
+}
+
+// The colour-correction moments of a view (gr_cc_fit_view): with u = (x0, x1, x2, 1), x the rendered colour from the saved
+// sums and t the target, the tile's sums over its in-image pixels of the 10 upper-triangle products u_i u_j (row-major)
+// and the 12 products u_j t_k ([j][k]), formed and summed in double (a float x float product is exact in double).  One
+// thread per pixel on k_eval_view's grid; the tile's sum is the wave butterfly and then the four waves in order, as
+// k_camera_grad_views sums its 35 doubles: a fixed order, 704 bytes of LDS.  part[q * tiles + tile].
+__global__ __launch_bounds__(256) void k_cc_moments(ViewK v, const float4* __restrict__ saved4, const float* __restrict__ y,
+                                                    double* __restrict__ part) {
+  __shared__ double row[4][GR_CC_MOMENTS];
+  const int t = threadIdx.x;
+  const int gx = blockIdx.x * ST + (t & (ST - 1)), gy = blockIdx.y * ST + t / ST;
+  double acc[GR_CC_MOMENTS];
+#pragma unroll
+  for (int q = 0; q < GR_CC_MOMENTS; ++q) acc[q] = 0.0;
+  if (gx < v.W && gy < v.H) {
+    const int64_t p = (int64_t)gy * v.W + gx;
+    const float4 s = saved4[p];
+    double u[4], tg[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      u[k] = (double)saved_colour(v, s, k);
+      tg[k] = (double)y[3 * p + k];
+    }
+    u[3] = 1.0;
+    int q = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = i; j < 4; ++j) acc[q++] = u[i] * u[j];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) acc[q++] = u[j] * tg[k];
+  }
+#pragma unroll
+  for (int q = 0; q < GR_CC_MOMENTS; ++q)
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) acc[q] += __shfl_xor(acc[q], m);
+  if ((t & 63) == 0)
+#pragma unroll
+    for (int q = 0; q < GR_CC_MOMENTS; ++q) row[t >> 6][q] = acc[q];
+  __syncthreads();
+  if (t < GR_CC_MOMENTS) {
+    const size_t tiles = (size_t)gridDim.x * gridDim.y, tile = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
+    part[(size_t)t * tiles + tile] = ((row[0][t] + row[1][t]) + row[2][t]) + row[3][t];
+  }
+}
+
+// The transform from the tiles' moments (gr_cc_fit_view), one block: each of the 22 planes summed over the tiles in
+// k_ssim_final's order (stride 256, then the 256-lane tree, in double), then one thread solves, per output channel k,
+//   (A / HW + ridge I) E_k^T = B[:, k] / HW + ridge e_k      (e_k row k of [I | 0])
+// by a Cholesky factorisation in double (positive definite for ridge > 0) and writes the 12 floats, rounded once.
+__global__ __launch_bounds__(256) void k_cc_solve(const double* __restrict__ part, int tiles, double hw, double ridge,
+                                                  float* __restrict__ E) {
+  __shared__ double r[GR_CC_MOMENTS][256];
+  const int t = threadIdx.x;
+  double s[GR_CC_MOMENTS];
+#pragma unroll
+  for (int q = 0; q < GR_CC_MOMENTS; ++q) s[q] = 0.0;
+  for (int i = t; i < tiles; i += 256)
+#pragma unroll
+    for (int q = 0; q < GR_CC_MOMENTS; ++q) s[q] += part[(size_t)q * tiles + i];
+#pragma unroll
+  for (int q = 0; q < GR_CC_MOMENTS; ++q) r[q][t] = s[q];
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (t < w)
+#pragma unroll
+      for (int q = 0; q < GR_CC_MOMENTS; ++q) r[q][t] += r[q][t + w];
+    __syncthreads();
+  }
+  if (t != 0) return;
+  double M[4][4], L[4][4], b[4][3];
+  int q = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = i; j < 4; ++j) {
+      M[i][j] = M[j][i] = r[q++][0] / hw + (i == j ? ridge : 0.0);
+    }
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int k = 0; k < 3; ++k) b[j][k] = r[q++][0] / hw + (j == k ? ridge : 0.0);
+  // M = L L^T (lower L)
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    double d = M[j][j];
+#pragma unroll
+    for (int m = 0; m < j; ++m) d -= L[j][m] * L[j][m];
+    L[j][j] = sqrt(d);
+#pragma unroll
+    for (int i = j + 1; i < 4; ++i) {
+      double o = M[i][j];
+#pragma unroll
+      for (int m = 0; m < j; ++m) o -= L[i][m] * L[j][m];
+      L[i][j] = o / L[j][j];
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    double z[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {  // L z = b
+      double a = b[i][k];
+#pragma unroll
+      for (int m = 0; m < i; ++m) a -= L[i][m] * z[m];
+      z[i] = a / L[i][i];
+    }
+#pragma unroll
+    for (int i = 3; i >= 0; --i) {  // L^T e = z
+      double a = z[i];
+#pragma unroll
+      for (int m = i + 1; m < 4; ++m) a -= L[m][i] * z[m];
+      z[i] = a / L[i][i];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) E[4 * k + j] = (float)z[j];
   }
 }
 
@@ -6976,22 +7168,71 @@ size_t gr_eval_ws_bytes(const gr_view* v) {
   return GR_EVAL_METRICS * ssim_partial_bytes(v->height, v->width);
 }
 
-gr_status gr_eval_view(const gr_view* v, const float* saved, const float* target_rgb, float* metrics, void* ws,
-                       size_t ws_bytes, void* stream) {
+// The refusals of gr_eval_view, gr_cc_fit_view and gr_eval_view_cc (`name` in each message; `io`: the call's other
+// pointers all non-null; `need`: its workspace size).
+static gr_status eval_view_checks(const char* name, const gr_view* v, const float* saved, const float* target_rgb, bool io,
+                                  const void* ws, size_t ws_bytes, size_t need) {
+  const std::string who = name;
   gr_status st = check_view(v);
   if (st != GR_OK) return st;
   if (tile_of(v) != T)
-    return set_error(GR_ERR_INVALID_ARGUMENT, "gr_eval_view: 32-pixel tiles (gr_view.tile = 32): an SSIM tile is a 16-pixel render tile");
-  if (v->rows > 0) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_eval_view: a band of tile rows (gr_view.rows): whole views only");
+    return set_error(GR_ERR_INVALID_ARGUMENT, who + ": 32-pixel tiles (gr_view.tile = 32): an SSIM tile is a 16-pixel render tile");
+  if (v->rows > 0) return set_error(GR_ERR_INVALID_ARGUMENT, who + ": a band of tile rows (gr_view.rows): whole views only");
   if (!ssim_shape_ok(v->height, v->width, 3))
-    return set_error(GR_ERR_INVALID_ARGUMENT, "gr_eval_view: the view exceeds the D-SSIM kernels' 2^30 values");
-  if (!saved || !target_rgb || !metrics || !ws) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_eval_view: null pointer");
-  if (ws_bytes < gr_eval_ws_bytes(v)) return set_error(GR_ERR_WORKSPACE, "gr_eval_view: workspace too small");
+    return set_error(GR_ERR_INVALID_ARGUMENT, who + ": the view exceeds the D-SSIM kernels' 2^30 values");
+  if (!saved || !target_rgb || !io || !ws) return set_error(GR_ERR_INVALID_ARGUMENT, who + ": null pointer");
+  if (ws_bytes < need) return set_error(GR_ERR_WORKSPACE, who + ": workspace too small");
+  return GR_OK;
+}
+
+gr_status gr_eval_view(const gr_view* v, const float* saved, const float* target_rgb, float* metrics, void* ws,
+                       size_t ws_bytes, void* stream) {
+  const gr_status st = eval_view_checks("gr_eval_view", v, saved, target_rgb, metrics != nullptr, ws, ws_bytes, gr_eval_ws_bytes(v));
+  if (st != GR_OK) return st;
   hipStream_t s = (hipStream_t)stream;
   const ViewK vk = make_viewk(v);
   const int plane = (int)(ssim_partial_bytes(v->height, v->width) / sizeof(float));
   hipLaunchKernelGGL(k_eval_view, dim3(vk.tiles_x, vk.tiles_y), dim3(256), 0, s, vk, (const float4*)saved, target_rgb,
                      (float*)ws, plane);
+  GR_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_eval_final, dim3(1), dim3(256), 0, s, (const float*)ws, plane, vk.tiles_x * vk.tiles_y,
+                     (int64_t)v->height * v->width * 3, metrics);
+  GR_HIP_TRY(hipGetLastError());
+  return GR_OK;
+}
+
+// Colour correction: GR_CC_MOMENTS planes of per-tile double partial sums (k_cc_moments).
+size_t gr_cc_ws_bytes(const gr_view* v) {
+  if (!v || !ssim_shape_ok(v->height, v->width, 3)) return 0;
+  return align_up((size_t)GR_CC_MOMENTS * tiles_x_of(v->width, ST) * tiles_y_of(v->height, ST) * sizeof(double));
+}
+
+gr_status gr_cc_fit_view(const gr_view* v, const float* saved, const float* target_rgb, float ridge, float* transform,
+                         void* ws, size_t ws_bytes, void* stream) {
+  const gr_status st = eval_view_checks("gr_cc_fit_view", v, saved, target_rgb, transform != nullptr, ws, ws_bytes, gr_cc_ws_bytes(v));
+  if (st != GR_OK) return st;
+  if (!(ridge > 0.0f) || !std::isfinite(ridge))
+    return set_error(GR_ERR_INVALID_ARGUMENT, "gr_cc_fit_view: ridge must be positive and finite");
+  hipStream_t s = (hipStream_t)stream;
+  const ViewK vk = make_viewk(v);
+  hipLaunchKernelGGL(k_cc_moments, dim3(vk.tiles_x, vk.tiles_y), dim3(256), 0, s, vk, (const float4*)saved, target_rgb,
+                     (double*)ws);
+  GR_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_cc_solve, dim3(1), dim3(256), 0, s, (const double*)ws, vk.tiles_x * vk.tiles_y,
+                     (double)v->height * (double)v->width, (double)ridge, transform);
+  GR_HIP_TRY(hipGetLastError());
+  return GR_OK;
+}
+
+gr_status gr_eval_view_cc(const gr_view* v, const float* saved, const float* target_rgb, const float* transform,
+                          float* metrics, void* ws, size_t ws_bytes, void* stream) {
+  const gr_status st = eval_view_checks("gr_eval_view_cc", v, saved, target_rgb, transform && metrics, ws, ws_bytes, gr_eval_ws_bytes(v));
+  if (st != GR_OK) return st;
+  hipStream_t s = (hipStream_t)stream;
+  const ViewK vk = make_viewk(v);
+  const int plane = (int)(ssim_partial_bytes(v->height, v->width) / sizeof(float));
+  hipLaunchKernelGGL(k_eval_view_cc, dim3(vk.tiles_x, vk.tiles_y), dim3(256), 0, s, vk, (const float4*)saved, target_rgb,
+                     transform, (float*)ws, plane);
   GR_HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(k_eval_final, dim3(1), dim3(256), 0, s, (const float*)ws, plane, vk.tiles_x * vk.tiles_y,
                      (int64_t)v->height * v->width * 3, metrics);

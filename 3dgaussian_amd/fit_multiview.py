@@ -2151,10 +2151,12 @@ class ViewShardedFitter:
             return activations_native(self.params)[:4]
         return tuple(t.detach() for t in activations(self.params))
 
-    def _exec_views(self, fn: str, m, s, c, o, gvs, targets, out) -> None:
+    def _exec_views(self, fn: str, m, s, c, o, gvs, targets, out, extra: tuple = ()) -> None:
         """One native executor call over views that are only rendered: gr_eval_views (the views' metrics against
-        ``targets`` into ``out`` (len(gvs), 3)), gr_contrib_views (targets None: every view's peak blend weights into
-        the one ``out``) or gr_error_views (every view's blend-weighted error against ``targets`` into the one ``out``)."""
+        ``targets`` into ``out`` (len(gvs), 3)), gr_eval_views_cc (the same with the corrected metrics and the transform:
+        ``out`` (len(gvs), 18), ``extra`` its ridge, the argument before ``out``), gr_contrib_views (targets None: every
+        view's peak blend weights into the one ``out``) or gr_error_views (every view's blend-weighted error against
+        ``targets`` into the one ``out``).  ``extra``: the entry's own arguments before ``out``."""
         device = m.device
         arr = (tr._native.GrFitTarget * len(gvs))()
         for j, gv in enumerate(gvs):
@@ -2165,7 +2167,7 @@ class ViewShardedFitter:
         cfg = self._exec_config(device, max(1, min(NUM_STREAMS, len(gvs))))
         tr._native.check(getattr(tr._native.lib(), fn)(
             tr._native.executor(device.index or 0), ctypes.byref(cfg), len(gvs), arr, int(m.shape[0]), tr._native.ptr(m),
-            tr._native.ptr(s), tr._native.ptr(c), tr._color_dim(c), tr._native.ptr(o), tr._native.ptr(out),
+            tr._native.ptr(s), tr._native.ptr(c), tr._color_dim(c), tr._native.ptr(o), *extra, tr._native.ptr(out),
             ctypes_stream(device)), fn)
         self._eval_keep = (m, s, c, o)  # read by the executor's streams until the caller's stream passes them
 
@@ -2179,15 +2181,16 @@ class ViewShardedFitter:
 
         self._view_loop(m.device, len(gvs), self._preparer(m, s, c, o, gvs.__getitem__, len(gvs)), body)
 
-    def _pass_views(self, fn: str, m, s, c, o, gvs, targets, out, view_call: Callable) -> None:
-        """A render-only pass over ``gvs``: the native executor's ``fn`` (_exec_views) where the fit step uses it, else
-        the Python schedule of the same calls (_pass_direct)."""
+    def _pass_views(self, fn: str, m, s, c, o, gvs, targets, out, view_call: Callable, extra: tuple = ()) -> None:
+        """A render-only pass over ``gvs``: the native executor's ``fn`` (_exec_views, ``extra`` its own arguments) where
+        the fit step uses it, else the Python schedule of the same calls (_pass_direct)."""
         if self._native_exec() and GATHER:
-            self._exec_views(fn, m, s, c, o, gvs, targets, out)
+            self._exec_views(fn, m, s, c, o, gvs, targets, out, extra)
         else:
             self._pass_direct(m, s, c, o, gvs, view_call)
 
-    def evaluate(self, cams: Optional[list] = None, targets: Optional[list] = None) -> dict:
+    def evaluate(self, cams: Optional[list] = None, targets: Optional[list] = None, color_correct: bool = False,
+                 ridge: float = losses.CC_RIDGE) -> dict:
         """Per-view metrics of the current Gaussians against target images: float64 numpy arrays ``l1`` (mean|x - y|),
         ``mse``, ``psnr`` (-10 log10 mse, formed on the host in double; inf at zero error) and ``ssim`` in the order of
         the views passed, and their means ``mean_l1`` .. ``mean_ssim``.  Default views: the fitter's own training
@@ -2199,8 +2202,17 @@ class ViewShardedFitter:
         On the HIP device (the HIP render op, float32 parameters and exact-shape float32 targets) the metrics come from
         the saved sums without an image (gr_eval_view), through the native executor (gr_eval_views) where the fit step
         uses it, else a Python schedule of the same calls; otherwise render_fn under no_grad and
-        losses.image_metrics.  Changes nothing of the fit: no gradient, optimizer, density or random state."""
+        losses.image_metrics.  Changes nothing of the fit: no gradient, optimizer, density or random state.
+        color_correct=True: the dict gains ``cc_l1``, ``cc_mse``, ``cc_psnr``, ``cc_ssim`` and their ``mean_cc_*``, the
+        same metrics of each view's render mapped onto its target by the view's best affine colour transform (fitted in
+        closed form with ``ridge`` towards the identity, include/gr_hip.h: a reading that a per-view exposure or white
+        balance of the photos does not move, for training and held-out views alike), and ``cc_transform``, the (V, 3, 4)
+        float64 array of those transforms.  On the HIP device gr_eval_views_cc (else the Python schedule of
+        gr_eval_view, gr_cc_fit_view, gr_eval_view_cc), otherwise losses.image_metrics_cc; the all-reduced tensor is
+        (V, 18).  With False the call, the dict and its bits are as without the argument."""
         self.graph_sync()
+        if color_correct and not (math.isfinite(ridge) and ridge > 0.0):
+            raise ValueError(f"evaluate: ridge must be positive and finite, got {ridge}")
         if (cams is None) != (targets is None):
             raise ValueError("evaluate: pass both cams and targets, or neither (the training views)")
         if cams is None:
@@ -2211,16 +2223,26 @@ class ViewShardedFitter:
         device = self.params["means"].device
         n = int(self.params["means"].shape[0])
         mine = list(range(self.rank, V, self.world))
-        res = torch.zeros((V, tr._native.EVAL_METRICS), dtype=torch.float32, device=device)
+        NM = tr._native.EVAL_METRICS
+        cols = tr._native.EVAL_CC_ROW if color_correct else NM
+        res = torch.zeros((V, cols), dtype=torch.float32, device=device)
         with torch.no_grad():
             means, scales, colors, opacities = self._eval_activations(device)
             if mine and n > 0 and self._eval_native_ok(device, [targets[i] for i in mine]):
                 m, s, c, o = (t.detach().float().contiguous() for t in (means, scales, colors, opacities))
                 gvs = [self._eval_view(cams[i], device) for i in mine]
-                out = torch.empty((len(mine), tr._native.EVAL_METRICS), dtype=torch.float32, device=device)
+                out = torch.empty((len(mine), cols), dtype=torch.float32, device=device)
                 tg = [targets[i] for i in mine]
-                self._pass_views("gr_eval_views", m, s, c, o, gvs, tg, out,
-                                 lambda j, rs, pv: tr.eval_view_native(rs, tg[j], out[j]))
+                if color_correct:
+                    def view_cc(j, rs, pv):  # the executor's three calls on the view's saved sums, into its row
+                        tr.eval_view_native(rs, tg[j], out[j, :NM])
+                        tr.cc_fit_view_native(rs, tg[j], out[j, 2 * NM:], ridge)
+                        tr.eval_view_cc_native(rs, tg[j], out[j, 2 * NM:], out[j, NM:2 * NM])
+
+                    self._pass_views("gr_eval_views_cc", m, s, c, o, gvs, tg, out, view_cc, (ctypes.c_float(ridge),))
+                else:
+                    self._pass_views("gr_eval_views", m, s, c, o, gvs, tg, out,
+                                     lambda j, rs, pv: tr.eval_view_native(rs, tg[j], out[j]))
                 res[mine] = out
             else:
                 for i in mine:
@@ -2228,8 +2250,13 @@ class ViewShardedFitter:
                     pred = self.render_fn(means, scales, colors, opacities, cams[i], self.width, self.height,
                                           self._background(device), **kw)
                     pred = pred[0] if isinstance(pred, tuple) else pred
-                    mt = losses.image_metrics(pred, targets[i].to(device))
-                    res[i] = torch.stack([mt["l1"], mt["mse"], mt["ssim"]]).to(res)
+                    if color_correct:
+                        mt = losses.image_metrics_cc(pred, targets[i].to(device), ridge)
+                        res[i] = torch.cat([torch.stack([mt[p + k] for p in ("", "cc_") for k in ("l1", "mse", "ssim")]),
+                                            mt["cc_transform"].reshape(-1)]).to(res)
+                    else:
+                        mt = losses.image_metrics(pred, targets[i].to(device))
+                        res[i] = torch.stack([mt["l1"], mt["mse"], mt["ssim"]]).to(res)
         if self.world > 1:
             dist.all_reduce(res, group=self.group)
         a = res.double().cpu().numpy()
@@ -2237,8 +2264,16 @@ class ViewShardedFitter:
         with np.errstate(divide="ignore"):
             psnr = -10.0 * np.log10(mse)
         mean = lambda x: float(x.mean()) if V else float("nan")  # noqa: E731
-        return {"l1": l1, "mse": mse, "psnr": psnr, "ssim": ssim, "mean_l1": mean(l1), "mean_mse": mean(mse),
-                "mean_psnr": mean(psnr), "mean_ssim": mean(ssim)}
+        r = {"l1": l1, "mse": mse, "psnr": psnr, "ssim": ssim, "mean_l1": mean(l1), "mean_mse": mean(mse),
+             "mean_psnr": mean(psnr), "mean_ssim": mean(ssim)}
+        if color_correct:
+            cl1, cmse, cssim = a[:, NM].copy(), a[:, NM + 1].copy(), a[:, NM + 2].copy()
+            with np.errstate(divide="ignore"):
+                cpsnr = -10.0 * np.log10(cmse)
+            r.update({"cc_l1": cl1, "cc_mse": cmse, "cc_psnr": cpsnr, "cc_ssim": cssim, "mean_cc_l1": mean(cl1),
+                      "mean_cc_mse": mean(cmse), "mean_cc_psnr": mean(cpsnr), "mean_cc_ssim": mean(cssim),
+                      "cc_transform": a[:, 2 * NM:].reshape(V, 3, 4).copy()})
+        return r
 
     # ---- contribution (peak blend weight per Gaussian) ----------------------------------------------------------
     def contribution_state(self, cams: Optional[list] = None) -> torch.Tensor:
@@ -2525,6 +2560,13 @@ def main(argv=None) -> None:
                     help="M > 0: evaluate every M iterations and after the last (the held-out views, or without "
                          "--holdout_every the training views); 0 (default): once after the last iteration, and only "
                          "with --holdout_every")
+    ap.add_argument("--eval_color_correct", action="store_true",
+                    help="with an evaluation (--holdout_every / --eval_interval): also the colour-corrected metrics, "
+                         "PSNR / SSIM / L1 of each view's render mapped onto its target by the view's best affine colour "
+                         "transform (closed form; the cc_* keys of eval.json): a reading that per-view exposure and "
+                         "white balance of the photos do not move")
+    ap.add_argument("--eval_ridge", type=float, default=losses.CC_RIDGE,
+                    help="with --eval_color_correct: the ridge that pulls the fitted transform towards the identity")
     ap.add_argument("--refine_cameras", action="store_true",
                     help="fit the training views' poses with the Gaussians (a 6-vector per view, pose_view) and write "
                          "cameras_refined.npz (the --camera_npz schema)")
@@ -2539,7 +2581,7 @@ def main(argv=None) -> None:
                          "identity; the photometric term compares the transformed render with the target) and write "
                          "exposures.npz; host tensors only (--device cpu); held-out metrics (--holdout_every) are taken "
                          "without exposure: held-out views have none, and the metric is of the image rendered from the "
-                         "saved Gaussians")
+                         "saved Gaussians; --eval_color_correct is the way to judge held-out views of such photo sets")
     ap.add_argument("--exposure_lr", type=float, default=1e-3,
                     help="with --exposure: Adam's learning rate of the exposure matrices")
     ap.add_argument("--exposure_fix", default="0",
@@ -2642,14 +2684,22 @@ def main(argv=None) -> None:
             pending = []
         if do_eval and ((args.eval_interval > 0 and (it + 1) % args.eval_interval == 0) or it + 1 == args.iters):
             # a collective (every rank); the held-out views if there are any, else the training views
-            r = fitter.evaluate(eval_cams, eval_targets) if hold else fitter.evaluate()
+            cc = dict(color_correct=True, ridge=args.eval_ridge) if args.eval_color_correct else {}
+            r = fitter.evaluate(eval_cams, eval_targets, **cc) if hold else fitter.evaluate(**cc)
             n_now = int(fitter.params["means"].shape[0])
             eval_log.append({"iter": it + 1, "n": n_now, "views": hold if hold else list(range(len(targets))),
                              "psnr": r["psnr"].tolist(), "ssim": r["ssim"].tolist(), "l1": r["l1"].tolist(),
                              "mean_psnr": r["mean_psnr"], "mean_ssim": r["mean_ssim"], "mean_l1": r["mean_l1"]})
+            if cc:
+                for k in ("psnr", "ssim", "l1"):
+                    eval_log[-1].update({"cc_" + k: r["cc_" + k].tolist(), "mean_cc_" + k: r["mean_cc_" + k]})
+                eval_log[-1]["cc_transform"] = r["cc_transform"].tolist()
             if rank == 0:
                 print(f"eval iter {it+1:4d}  N={n_now}  PSNR={r['mean_psnr']:.3f} dB  SSIM={r['mean_ssim']:.5f}  "
                       f"L1={r['mean_l1']:.6f}  ({'held-out' if hold else 'training'} views: {len(r['psnr'])})")
+                if cc:
+                    print(f"eval iter {it+1:4d}  colour-corrected: PSNR={r['mean_cc_psnr']:.3f} dB  "
+                          f"SSIM={r['mean_cc_ssim']:.5f}  L1={r['mean_cc_l1']:.6f}")
         if (it + 1) % args.prune_interval == 0 or (it + 1) % args.densify_interval == 0:
             fitter.densify_and_prune(args.max_gaussians,
                                      args.densify_ratio if (it + 1) % args.densify_interval == 0 else 0.0,

@@ -17,6 +17,7 @@ torch ops, so that a ``--device cpu`` fit works (tests/test_ssim_gpu.py, tests/t
 from __future__ import annotations
 
 import ctypes
+import math
 from typing import Optional
 
 import torch
@@ -171,4 +172,54 @@ def image_metrics(pred: torch.Tensor, target: torch.Tensor) -> dict:
         return {"l1": torch.mean(torch.abs(d)), "mse": torch.mean(d * d), "psnr": psnr(x, y), "ssim": ssim(x, y)}
 
 
-__all__ = ["l1_loss", "dssim_loss", "ssim", "psnr", "image_metrics"]
+CC_RIDGE = 1e-6  # GR_CC_RIDGE (include/gr_hip.h)
+
+
+def apply_color_transform(img: torch.Tensor, E: torch.Tensor) -> torch.Tensor:
+    """The colour-corrected image of include/gr_hip.h: ``y_k = ((E[k][0] x0 + E[k][1] x1) + E[k][2] x2) + E[k][3]`` of an
+    (..., 3) image and a 3 x 4 transform (or its 12 values row-major), element-wise in float32, every product and sum
+    rounded on its own in that order (the bits k_eval_view_cc stages); not clamped.  Any device."""
+    x = img.float()
+    if x.shape[-1] != 3 or E.numel() != 12:
+        raise ValueError(f"apply_color_transform: an (..., 3) image and a 3 x 4 transform, got {tuple(img.shape)}, {tuple(E.shape)}")
+    e = E.detach().to(device=x.device, dtype=torch.float32).reshape(3, 4)
+    x0, x1, x2 = x[..., 0], x[..., 1], x[..., 2]
+    return torch.stack([((e[k, 0] * x0 + e[k, 1] * x1) + e[k, 2] * x2) + e[k, 3] for k in range(3)], dim=-1)
+
+
+def color_correct(pred: torch.Tensor, target: torch.Tensor, ridge: float = CC_RIDGE) -> torch.Tensor:
+    """The affine colour transform E (3 x 4 float32 on pred's device, row k the output channel) that best maps the
+    (H, W, 3) image ``pred`` onto ``target``: row k minimises ``sum_p (E_k . (x, 1) - t_k)^2 + ridge HW |E_k - e_k|^2``,
+    e_k row k of [I | 0] (include/gr_hip.h; the ridge makes images of one colour or one pixel well defined and gives the
+    identity when target = pred).  The moments in float64 with torch on the images' device, the 4 x 4 Cholesky solve in
+    float64 on the host (22 numbers cross; not every device build has a solver), rounded to float32 once.  No gradient."""
+    if not (math.isfinite(ridge) and ridge > 0.0):
+        raise ValueError(f"color_correct: ridge must be positive and finite, got {ridge}")
+    with torch.no_grad():
+        x, y = _ssim_args("color_correct", pred.detach(), target)
+        if x.shape[2] != 3:
+            raise ValueError(f"color_correct: images are (H, W, 3), got {tuple(x.shape)}")
+        hw = x.shape[0] * x.shape[1]
+        u = torch.cat([x.double().reshape(hw, 3), torch.ones((hw, 1), dtype=torch.float64, device=x.device)], dim=1)
+        A = (u.t() @ u).cpu() / hw + ridge * torch.eye(4, dtype=torch.float64)
+        B = (u.t() @ y.double().reshape(hw, 3)).cpu() / hw + ridge * torch.eye(4, 3, dtype=torch.float64)
+        sol = torch.cholesky_solve(B, torch.linalg.cholesky(A))  # (4, 3): column k is E_k
+        return sol.t().contiguous().float().to(x.device)
+
+
+def image_metrics_cc(pred: torch.Tensor, target: torch.Tensor, ridge: float = CC_RIDGE) -> dict:
+    """image_metrics plus the colour-corrected metrics, composed from existing ops (the reference route of
+    ViewShardedFitter.evaluate(color_correct=True), and what it uses off the HIP device): ``cc_transform`` =
+    color_correct(pred, target, ridge) and ``cc_l1``, ``cc_mse``, ``cc_psnr``, ``cc_ssim`` = image_metrics of
+    apply_color_transform(pred, cc_transform) against target.  No gradient."""
+    with torch.no_grad():
+        out = image_metrics(pred, target)
+        E = color_correct(pred, target, ridge)
+        cc = image_metrics(apply_color_transform(pred.detach(), E), target)
+        out.update({"cc_" + k: v for k, v in cc.items()})
+        out["cc_transform"] = E
+        return out
+
+
+__all__ = ["l1_loss", "dssim_loss", "ssim", "psnr", "image_metrics", "apply_color_transform", "color_correct",
+           "image_metrics_cc"]

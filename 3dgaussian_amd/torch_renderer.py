@@ -898,6 +898,34 @@ def eval_view_native(st: RenderState, target, metrics_out) -> None:
                                  _native.ptr(ws), ws.numel(), _stream(dev)), "gr_eval_view")
 
 
+def cc_fit_view_native(st: RenderState, target, transform_out, ridge: float = _native.CC_RIDGE) -> None:
+    """gr_cc_fit_view on the current stream: ``transform_out`` (``_native.CC_TRANSFORM`` float32 on the device) receives
+    the affine colour transform E (3 x 4 row-major, row k the output channel) that best maps the view's render, formed
+    from the state's saved sums, onto ``target`` (H, W, 3): moments in double in a fixed order, a ridge towards [I | 0]
+    (include/gr_hip.h).  Deterministic."""
+    L = _native.lib()
+    dev = st.saved.device
+    _check_operand(target, (st.gv.height, st.gv.width, 3), "target", dev)
+    _check_operand(transform_out, (_native.CC_TRANSFORM,), "transform_out", dev)
+    ws = torch.empty((int(L.gr_cc_ws_bytes(ctypes.byref(st.gv))),), dtype=torch.uint8, device=dev)
+    _native.check(L.gr_cc_fit_view(ctypes.byref(st.gv), _native.ptr(st.saved), _native.ptr(target), ctypes.c_float(ridge),
+                                   _native.ptr(transform_out), _native.ptr(ws), ws.numel(), _stream(dev)), "gr_cc_fit_view")
+
+
+def eval_view_cc_native(st: RenderState, target, transform, metrics_out) -> None:
+    """gr_eval_view_cc on the current stream: eval_view_native's three metrics of the colour-corrected render
+    E (out, 1) against ``target``, ``transform`` being E (``_native.CC_TRANSFORM`` float32 on the device, as
+    cc_fit_view_native writes it), applied while the render is staged from the saved sums."""
+    L = _native.lib()
+    dev = st.saved.device
+    _check_operand(target, (st.gv.height, st.gv.width, 3), "target", dev)
+    _check_operand(transform, (_native.CC_TRANSFORM,), "transform", dev)
+    _check_operand(metrics_out, (_native.EVAL_METRICS,), "metrics_out", dev)
+    ws = torch.empty((int(L.gr_eval_ws_bytes(ctypes.byref(st.gv))),), dtype=torch.uint8, device=dev)
+    _native.check(L.gr_eval_view_cc(ctypes.byref(st.gv), _native.ptr(st.saved), _native.ptr(target), _native.ptr(transform),
+                                    _native.ptr(metrics_out), _native.ptr(ws), ws.numel(), _stream(dev)), "gr_eval_view_cc")
+
+
 def contrib_view_native(rs: RenderState, pv: Prepared, peak) -> None:
     """gr_contrib_view on the current stream: ``peak`` ((n,) float32 on the device, zeroed by the caller) takes, per
     Gaussian, the maximum of its value and the Gaussian's largest blend weight w / (1 + W) over the pixels of its kept
@@ -1305,5 +1333,5 @@ __all__ = ["Camera", "get_default_device", "perspective", "look_at", "render_gau
            "make_view", "prepare_view", "prepare_native", "Prepared", "forward_native", "backward_native",
            "backward_l1_native", "backward_fit_native", "backward_fit_gather_native", "forward_l1_native", "backward_splat_native", "reduce_views_native",
            "gather_view_native", "reduce_sums_native", "density_stats_native", "camera_grads_sums_native", "eval_view_native",
-           "contrib_view_native", "error_view_native",
+           "cc_fit_view_native", "eval_view_cc_native", "contrib_view_native", "error_view_native",
            "DEFAULT_CUTOFF", "DEPTH_GRAD_CUTOFF", "DEFAULT_CORE_CUTOFF", "FIT_CUTOFF", "default_cutoff"]

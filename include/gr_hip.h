@@ -507,6 +507,53 @@ gr_status gr_eval_views(gr_executor* executor, const gr_fit_config* config, int 
                         const float* colors, int color_dim, const float* opacities,
                         float* metrics /* device [num_views][GR_EVAL_METRICS] */, void* stream);
 
+/* Colour-corrected view metrics (an extension): real photo sets differ per view in exposure and white balance, and a
+ * held-out view has no fitted exposure, so beside gr_eval_view's metrics the same three are taken of the render mapped
+ * onto the target by the view's own best affine colour transform, fitted in closed form.  Per view, with
+ * x(p) = clamp((bg + C) / (1 + W), 0, 1) the colour gr_eval_view compares (from `saved`), t(p) = target_rgb and
+ * u = (x0, x1, x2, 1):
+ *   moments   A = sum_p u u^T (4 x 4 symmetric: its 10 upper-triangle entries, row-major) and B = sum_p u t^T (4 x 3,
+ *             12 entries row-major [j][k]) over all H*W pixels: GR_CC_MOMENTS = 22 doubles.  Products and sums in
+ *             double (a float x float product is exact in double), in a fixed order: a fixed tree per 16 x 16 tile,
+ *             then the tiles in the order gr_ssim_fwd sums its partials.  Required, not a nicety: the ridge below
+ *             amplifies moment noise by 1 / ridge in rank-deficient directions (float32 sums move E by whole units on a
+ *             view of one colour; float64 sums in any order by at most 1e-9)
+ *   transform E, 3 x 4 float32 row-major, row k the output channel: row k minimises
+ *               sum_p (E_k . u - t_k)^2 + ridge HW |E_k - e_k|^2,   e_k row k of [I | 0],
+ *             the solution of (A / HW + ridge I) E_k^T = B[:, k] / HW + ridge e_k, by Cholesky in double (positive
+ *             definite for ridge > 0), rounded to float32 once.  The ridge makes a view without pairs (rank 1), a grey
+ *             render (rank 2) and a 1 x 1 image well defined and gives E = [I | 0] when target = render; the identity
+ *             being feasible, the corrected squared error never exceeds the plain one in exact arithmetic
+ *   image     y_k = ((E[k][0] x0 + E[k][1] x1) + E[k][2] x2) + E[k][3], every product and sum rounded to float32 on
+ *             its own in that order (element-wise float32 operations on the image give the same bits); y is not
+ *             clamped; outside the image the SSIM window sees zeros, as for any image, not E (0, 1)
+ *   metrics   gr_eval_view's three of y against t (the corrected PSNR is formed by the caller, as the plain one)
+ * gr_cc_fit_view: one launch per 16 x 16 tile (one pixel per thread) writes 22 double partials per tile into ws, one
+ * single-block launch sums them, solves and writes transform (device, GR_CC_TRANSFORM floats).  ridge <= 0 or not
+ * finite: GR_ERR_INVALID_ARGUMENT.  gr_eval_view_cc: gr_eval_view with E read from the device and applied while the
+ * render is staged; ws of gr_eval_ws_bytes.
+ *   - refusals as gr_eval_view's (tile = 32, rows > 0, null pointers: GR_ERR_INVALID_ARGUMENT; ws shorter than
+ *     gr_cc_ws_bytes / gr_eval_ws_bytes: GR_ERR_WORKSPACE; nothing is launched)
+ *   - stream-ordered, no allocation, no atomics, deterministic */
+#define GR_CC_MOMENTS 22
+#define GR_CC_TRANSFORM 12
+#define GR_CC_RIDGE 1e-6f
+#define GR_EVAL_CC_ROW 18 /* gr_eval_view's 3 metrics, the 3 corrected ones, E row-major */
+size_t gr_cc_ws_bytes(const gr_view* v);
+gr_status gr_cc_fit_view(const gr_view* v, const float* saved, const float* target_rgb, float ridge,
+                         float* transform /* device, GR_CC_TRANSFORM floats */, void* ws, size_t ws_bytes, void* stream);
+gr_status gr_eval_view_cc(const gr_view* v, const float* saved, const float* target_rgb,
+                          const float* transform /* device, GR_CC_TRANSFORM floats */,
+                          float* metrics /* device, GR_EVAL_METRICS floats */, void* ws, size_t ws_bytes, void* stream);
+/* gr_eval_views with the corrected metrics: the same schedule, per view gr_fwd_render keeping the saved sums only,
+ * then gr_eval_view into rows[j][0..2], gr_cc_fit_view into rows[j][6..17] and gr_eval_view_cc into rows[j][3..5], all
+ * on the view's render stream in the stream's one pass workspace (the larger of the two sizes: the calls follow one
+ * another).  Checks, ordering and guarantees as gr_eval_views; bit-identical to the per-view calls. */
+gr_status gr_eval_views_cc(gr_executor* executor, const gr_fit_config* config, int num_views,
+                           const gr_fit_target* views, int n, const float* means, const float* scales,
+                           const float* colors, int color_dim, const float* opacities, float ridge,
+                           float* rows /* device [num_views][GR_EVAL_CC_ROW] */, void* stream);
+
 /* Peak blend weight per Gaussian, for contribution-based pruning (an extension: the reference prunes by opacity).
  * Compositing is out = clamp((bg + sum w c) / (1 + W)), so a Gaussian's share of pixel p is its blend weight
  * b = w(p) / (1 + W(p)); removing the Gaussian moves no channel of that pixel by more than b / (1 - b).

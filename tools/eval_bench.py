@@ -11,9 +11,12 @@
 3. --kernel-loop: only a loop of gr_eval_view and gr_bwd_fit_ssim_gather calls on one view, for a kernel trace
    (rocprofv3 --kernel-trace --stats -- python tools/eval_bench.py --kernel-loop; tools/kstats.py): k_eval_view
    beside k_ssim_fwd_saved, in alternating order.
+4. --color_correct: instead of 1 and 2, evaluate(color_correct=True) against evaluate() of the same fitter, through the
+   executor (gr_eval_views_cc / gr_eval_views) and the Python schedule, in alternating windows; with --kernel-loop a
+   loop of the three per-view calls (gr_eval_view, gr_cc_fit_view, gr_eval_view_cc) for a kernel trace.
 
     python tools/eval_bench.py [--gaussians 1000000 --views 50 --res 800] [--reps 3] [--windows 5] [--label C4]
-                               [--out FILE (appended)] [--kernel-loop]
+                               [--out FILE (appended)] [--kernel-loop] [--color_correct]
 """
 import argparse
 import importlib
@@ -111,6 +114,58 @@ def kernel_loop(n, R, calls, dev):
     print(f"kernel loop: {calls} x (gr_eval_view, gr_bwd_fit_ssim_gather) at {R}x{R}, {n} Gaussians")
 
 
+def cc_kernel_loop(n, R, calls, dev):
+    """--color_correct --kernel-loop: the three per-view calls of gr_eval_views_cc, for a kernel trace (k_cc_moments,
+    k_cc_solve and k_eval_view_cc beside k_eval_view)."""
+    _, st = view_state(n, R, dev)
+    target = torch.rand((R, R, 3), device=dev)
+    row = torch.zeros(18, device=dev)
+    for _ in range(calls):
+        tr.eval_view_native(st, target, row[:3])
+        tr.cc_fit_view_native(st, target, row[6:])
+        tr.eval_view_cc_native(st, target, row[6:], row[3:6])
+    torch.cuda.synchronize()
+    print(f"kernel loop: {calls} x (gr_eval_view, gr_cc_fit_view, gr_eval_view_cc) at {R}x{R}, {n} Gaussians")
+
+
+def cc_lines(fit, args, R):
+    """--color_correct: evaluate(color_correct=True) against evaluate() of the same fitter, the executor and the Python
+    schedule, in alternating windows."""
+    def evaluate(native, cc):
+        saved = fm.NATIVE_EXEC
+        fm.NATIVE_EXEC = native
+        try:
+            return fit.evaluate(color_correct=cc)
+        finally:
+            fm.NATIVE_EXEC = saved
+
+    ways = {"executor, plain": lambda: evaluate("1", False), "executor, color_correct": lambda: evaluate("1", True),
+            "Python schedule, plain": lambda: evaluate("0", False), "Python schedule, color_correct": lambda: evaluate("0", True)}
+    res = {k: f() for k, f in ways.items()}  # warm-up, and the agreement
+    a, b = res["executor, color_correct"], res["Python schedule, color_correct"]
+    same = all((a[k] == b[k]).all() for k in a if hasattr(a[k], "all"))
+    plain_same = all((a[k] == res["executor, plain"][k]).all() for k in ("l1", "mse", "ssim"))
+    times = {k: [] for k in ways}
+    for _ in range(args.windows):
+        for k, f in ways.items():
+            times[k].append(timed(f, args.reps))
+    med = {k: statistics.median(v) for k, v in times.items()}
+    lines = [f"{args.label + ': ' if args.label else ''}{args.gaussians} Gaussians, {args.views} views, {R}x{R}, "
+             f"{torch.cuda.get_device_name(0)}; {args.windows} alternating windows of {args.reps} evaluations after one warm-up "
+             "each, median ms per evaluate() over all views [min .. max]"]
+    for k in ways:
+        lines.append(f"  {k:32s}: {med[k]:9.3f} ms  [{min(times[k]):.3f} .. {max(times[k]):.3f}]  "
+                     f"{1e3 * med[k] / args.views:.1f} us per view")
+    for w in ("executor", "Python schedule"):
+        d = med[w + ", color_correct"] - med[w + ", plain"]
+        lines.append(f"  {w}: color_correct adds {1e3 * d / args.views:.1f} us per view "
+                     f"({med[w + ', color_correct'] / med[w + ', plain']:.3f}x)")
+    lines.append(f"  executor and Python schedule {'bit-identical' if same else 'DIFFER'}; plain keys "
+                 f"{'unchanged by the argument' if plain_same else 'DIFFER'}; mean PSNR {a['mean_psnr']:.3f} dB, corrected "
+                 f"{a['mean_cc_psnr']:.3f} dB")
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gaussians", type=int, default=1_000_000)
@@ -124,13 +179,16 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--kernel-loop", action="store_true")
     ap.add_argument("--no-kernel", action="store_true", help="skip part 2")
+    ap.add_argument("--color_correct", action="store_true",
+                    help="instead of parts 1 and 2: evaluate(color_correct=True) against evaluate() (executor and Python "
+                         "schedule); with --kernel-loop: the three per-view calls of gr_eval_views_cc")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("eval_bench: no HIP device (timings are taken on the GPU only)")
     dev = torch.device("cuda", 0)
     R = args.res
     if args.kernel_loop:
-        return kernel_loop(args.gaussians, R, 20, dev)
+        return (cc_kernel_loop if args.color_correct else kernel_loop)(args.gaussians, R, 20, dev)
     cams = fm.orbit_cameras(args.views, R, R, dev)
     g = torch.Generator(device=dev).manual_seed(3)
     targets = [torch.rand((R, R, 3), generator=g, device=dev) for _ in cams]
@@ -139,6 +197,14 @@ def main():
     for _ in range(3):
         fit.step()
     fit.graph_sync()
+    if args.color_correct:
+        text = "\n".join(cc_lines(fit, args, R)) + "\n"
+        print(text)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "a") as f:
+                f.write(text)
+        return
 
     def evaluate(native):
         saved = fm.NATIVE_EXEC
