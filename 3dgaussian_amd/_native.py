@@ -82,6 +82,7 @@ CC_MOMENTS = 22  # GR_CC_MOMENTS: the 10 + 12 double moments of the colour-corre
 CC_TRANSFORM = 12  # GR_CC_TRANSFORM: the affine colour transform E, 3 x 4 row-major
 CC_RIDGE = 1e-6  # GR_CC_RIDGE: the default ridge of gr_cc_fit_view
 EVAL_CC_ROW = 18  # GR_EVAL_CC_ROW: gr_eval_views_cc's row (the 3 metrics, the 3 corrected ones, E)
+EVAL_MASK_METRICS = 6  # GR_EVAL_MASK_METRICS: fg_fraction, fg_l1, fg_mse, fg_ssim, sil_l1, sil_iou of gr_eval_view_masked
 
 
 class GrReduceView(ctypes.Structure):
@@ -235,6 +236,10 @@ _SIG = {
     "gr_eval_view_cc": (ctypes.c_int, [_VP, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "gr_eval_views_cc": (ctypes.c_int, [_P, ctypes.POINTER(GrFitConfig), ctypes.c_int, ctypes.POINTER(GrFitTarget),
                                         ctypes.c_int, _P, _P, _P, ctypes.c_int, _P, ctypes.c_float, _P, _P]),
+    "gr_eval_mask_ws_bytes": (ctypes.c_size_t, [_VP]),
+    "gr_eval_view_masked": (ctypes.c_int, [_VP, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "gr_eval_views_masked": (ctypes.c_int, [_P, ctypes.POINTER(GrFitConfig), ctypes.c_int, ctypes.POINTER(GrFitTarget),
+                                            ctypes.c_int, _P, _P, _P, ctypes.c_int, _P, _P, _P]),
     "gr_contrib_ws_bytes": (ctypes.c_size_t, [_VP, ctypes.c_int, _PP]),
     "gr_contrib_view": (ctypes.c_int, [_VP, ctypes.c_int, _PP, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "gr_contrib_views": (ctypes.c_int, [_P, ctypes.POINTER(GrFitConfig), ctypes.c_int, ctypes.POINTER(GrFitTarget),

@@ -15,9 +15,10 @@
 // must grow is replaced after its stream has drained (rare: the first step, a densify).
 // The schedule (streams, preparation groups, reduction batches) is exactly fit_multiview._views_direct's,
 // so both give bit-identical losses and gradients (tests/test_fit_exec_gpu.py).
-// gr_eval_views, gr_eval_views_cc, gr_contrib_views and gr_error_views are the same schedule without a backward (a
-// render-only pass): per view gr_fwd_render (saved sums only) and the pass's calls on them (gr_eval_view into the view's row
-// of metrics, for gr_eval_views_cc followed by gr_cc_fit_view and gr_eval_view_cc into the same row; gr_contrib_view or
+// gr_eval_views, gr_eval_views_cc, gr_eval_views_masked, gr_contrib_views and gr_error_views are the same schedule without
+// a backward (a render-only pass): per view gr_fwd_render (saved sums only) and the pass's calls on them (gr_eval_view into
+// the view's row of metrics, for gr_eval_views_cc followed by gr_cc_fit_view and gr_eval_view_cc, for gr_eval_views_masked
+// by gr_eval_view_masked, into the same row; gr_contrib_view or
 // gr_error_view, every view into the caller's one buffer), with one pass workspace per render stream; a pass writes
 // nothing but those workspaces and the caller's output.
 #include <hip/hip_runtime.h>
@@ -126,8 +127,8 @@ struct gr_executor {
 // What is done with each view: the fit (loss, backward, reductions) or a render-only pass (no losses, accumulators or
 // statistics: per view the render and one call that reads its saved sums).
 struct Pass {
-  enum Kind { fit, eval, contrib, error, eval_cc } kind = fit;
-  float* out = nullptr;  // eval, eval_cc: the views' rows; contrib, error: the one per-Gaussian buffer
+  enum Kind { fit, eval, contrib, error, eval_cc, eval_masked } kind = fit;
+  float* out = nullptr;  // eval, eval_cc, eval_masked: the views' rows; contrib, error: the one per-Gaussian buffer
   float ridge = 0.0f;    // eval_cc: gr_cc_fit_view's
   bool fwd_only() const { return kind != fit; }
 };
@@ -269,6 +270,8 @@ static gr_status pass_views_checked(const char* name, Pass pass, gr_executor* ex
   if (num_views <= 0 || n <= 0) return GR_OK;
   for (int j = 0; pass.kind != Pass::contrib && j < num_views; ++j)
     if (!views[j].target_rgb) return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, (who + ": null target").c_str());
+  for (int j = 0; pass.kind == Pass::eval_masked && j < num_views; ++j)
+    if (!views[j].target_mask) return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, (who + ": null mask").c_str());
   gr_fit_config c = *cfg;  // no reductions: the batch settings are ignored
   c.reduce_batch = 1;
   c.reduce_tail = 0;
@@ -294,6 +297,13 @@ gr_status gr_eval_views_cc(gr_executor* ex, const gr_fit_config* cfg, int num_vi
   if (!(ridge > 0.0f) || !(ridge <= 3.402823466e38f))  // (as gr_cc_fit_view, before anything is enqueued)
     return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, "gr_eval_views_cc: ridge must be positive and finite");
   return pass_views_checked("gr_eval_views_cc", {Pass::eval_cc, rows, ridge}, ex, cfg, num_views, views, n, means, scales,
+                            colors, color_dim, opacities, stream);
+}
+
+gr_status gr_eval_views_masked(gr_executor* ex, const gr_fit_config* cfg, int num_views, const gr_fit_target* views, int n,
+                               const float* means, const float* scales, const float* colors, int color_dim,
+                               const float* opacities, float* metrics, void* stream) {
+  return pass_views_checked("gr_eval_views_masked", {Pass::eval_masked, metrics}, ex, cfg, num_views, views, n, means, scales,
                             colors, color_dim, opacities, stream);
 }
 
@@ -506,11 +516,12 @@ static gr_status enqueue_views(gr_executor* ex, const gr_fit_config* cfg, int nu
     if (!fwd_only) GR_EXEC_TRY(W.ws.fit(ws_bytes, s));
     void *bins = W.bins.p, *scratch = W.scratch.p, *ws = W.ws.p;
     if (fwd_only) {
-      // the saved sums only (no image, no depth output), then the pass's calls on them: the view's metrics (eval_cc: its
-      // three calls one after another on this stream, so the workspace is the larger of the two sizes), or its pairs'
-      // values into the one per-Gaussian buffer (atomic maxima)
+      // the saved sums only (no image, no depth output), then the pass's calls on them: the view's metrics (eval_cc,
+      // eval_masked: their calls one after another on this stream, so the workspace is the largest of their sizes), or
+      // its pairs' values into the one per-Gaussian buffer (atomic maxima)
       const size_t pass_bytes = pass.kind == Pass::eval      ? gr_eval_ws_bytes(&v)
                                 : pass.kind == Pass::eval_cc ? std::max(gr_eval_ws_bytes(&v), gr_cc_ws_bytes(&v))
+                                : pass.kind == Pass::eval_masked ? std::max(gr_eval_ws_bytes(&v), gr_eval_mask_ws_bytes(&v))
                                 : pass.kind == Pass::contrib ? gr_contrib_ws_bytes(&v, n, &plan)
                                                              : gr_error_ws_bytes(&v, n, &plan);
       GR_EXEC_TRY(W.saved.fit(gr_saved_floats(&v) * sizeof(float), s));
@@ -526,6 +537,11 @@ static gr_status enqueue_views(gr_executor* ex, const gr_fit_config* cfg, int nu
         GR_EXEC_CALL(gr_eval_view(&v, saved, views[j].target_rgb, row, W.pass.p, W.pass.cap, s));
         GR_EXEC_CALL(gr_cc_fit_view(&v, saved, views[j].target_rgb, pass.ridge, E, W.pass.p, W.pass.cap, s));
         GR_EXEC_CALL(gr_eval_view_cc(&v, saved, views[j].target_rgb, E, row + GR_EVAL_METRICS, W.pass.p, W.pass.cap, s));
+      } else if (pass.kind == Pass::eval_masked) {
+        float* row = pass.out + (size_t)(GR_EVAL_METRICS + GR_EVAL_MASK_METRICS) * j;
+        GR_EXEC_CALL(gr_eval_view(&v, saved, views[j].target_rgb, row, W.pass.p, W.pass.cap, s));
+        GR_EXEC_CALL(gr_eval_view_masked(&v, saved, views[j].target_rgb, views[j].target_mask, row + GR_EVAL_METRICS, W.pass.p,
+                                         W.pass.cap, s));
       } else if (pass.kind == Pass::contrib)
         GR_EXEC_CALL(gr_contrib_view(&v, n, &plan, geom[j], bins, saved, pass.out, W.pass.p, W.pass.cap, s));
       else

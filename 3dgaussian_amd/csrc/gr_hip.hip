@@ -5058,6 +5058,189 @@ __global__ __launch_bounds__(256) void k_eval_final(const float* __restrict__ pa
   }
 }
 
+// The alpha of a pixel from its saved sums s = (W, ...), exactly as write_pixel wrote it.
+__device__ __forceinline__ float saved_alpha(float4 s) {
+  const float den = 1.0f + s.x;
+  return clamp01(s.x / den);
+}
+
+// ssim_fwd_tile<3, false> with every value's m weighted by its pixel's mask value (tm: the tile's own 16 x 16 mask values,
+// no halo: the windows are not masked): the same separable sums, the same thread-strided accumulation (acc = fma(w, m, acc):
+// acc + m bit for bit where w = 1) and the same tree, into partial[tile].  A function of its own, not a form of
+// ssim_fwd_tile: the existing kernels' instructions stay what they are whatever happens here.
+__device__ __forceinline__ void ssim_fwd_tile_masked(const float* tx, const float* ty, const float* tm, float (*hs)[SE * ST * 3],
+                                                     float* red, int H, int W, float* __restrict__ partial) {
+  constexpr int C = 3, TC = ST * C, SP = SE * C;
+  const int t = threadIdx.x;
+  const int WC = W * C;
+  const int y0 = blockIdx.y * ST, v0 = blockIdx.x * TC;
+  for (int o = t; o < SE * TC; o += 256) {
+    const int r = o / TC, c = o - r * TC;
+    const float* px = tx + r * SP + c;
+    const float* py = ty + r * SP + c;
+    float a = 0.0f, b = 0.0f, aa = 0.0f, bb = 0.0f, ab = 0.0f;
+#pragma unroll
+    for (int k = 0; k <= 2 * SR; ++k) {
+      const float g = SSIM_G[k], u = px[k * C], v = py[k * C];
+      a = fmaf(g, u, a);
+      b = fmaf(g, v, b);
+      aa = fmaf(g, u * u, aa);
+      bb = fmaf(g, v * v, bb);
+      ab = fmaf(g, u * v, ab);
+    }
+    hs[0][o] = a;
+    hs[1][o] = b;
+    hs[2][o] = aa;
+    hs[3][o] = bb;
+    hs[4][o] = ab;
+  }
+  __syncthreads();
+  float acc = 0.0f;
+  for (int o = t; o < ST * TC; o += 256) {
+    const int r = o / TC, c = o - r * TC;
+    float mx = 0.0f, my = 0.0f, exx = 0.0f, eyy = 0.0f, exy = 0.0f;
+#pragma unroll
+    for (int k = 0; k <= 2 * SR; ++k) {
+      const float g = SSIM_G[k];
+      mx = fmaf(g, hs[0][o + k * TC], mx);
+      my = fmaf(g, hs[1][o + k * TC], my);
+      exx = fmaf(g, hs[2][o + k * TC], exx);
+      eyy = fmaf(g, hs[3][o + k * TC], eyy);
+      exy = fmaf(g, hs[4][o + k * TC], exy);
+    }
+    if (y0 + r < H && v0 + c < WC) {
+      const float sx = fmaf(-mx, mx, exx), sy = fmaf(-my, my, eyy), sxy = fmaf(-mx, my, exy);
+      const float A1 = fmaf(2.0f * mx, my, SSIM_C1), A2 = fmaf(2.0f, sxy, SSIM_C2);
+      const float B1 = fmaf(mx, mx, fmaf(my, my, SSIM_C1)), B2 = sx + sy + SSIM_C2;
+      const float rr = 1.0f / (B1 * B2);
+      const float m = (A1 * A2) * rr;
+      acc = fmaf(tm[r * ST + c / C], m, acc);
+    }
+  }
+  red[t] = acc;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (t < w) red[t] += red[t + w];
+    __syncthreads();
+  }
+  if (t == 0) partial[blockIdx.y * gridDim.x + blockIdx.x] = red[0];
+}
+
+// Masked view metrics (gr_eval_view_masked): k_eval_view's grid, staging and LDS, plus the tile's own 256 mask values and
+// alphas (saved_alpha of the staged sums; no halo, 2 KiB: three workgroups per CU still).  With m the mask, d = x - y per
+// value and a the alpha, the tile's sums over its in-image pixels, each by k_eval_view's thread-strided accumulation (one
+// pixel, or three values, per thread) and fixed tree: partial[q * plane + tile], q = 0 sum m, 1 sum m |d|, 2 sum m d^2,
+// 3 sum m s (s the SSIM map), 4 sum |a - m|, 5 #{a > 0.5 and m > 0.5}, 6 #{a > 0.5 or m > 0.5} (counts of at most 256:
+// exact in float).  Where m = 1 the weighted terms are k_eval_view's own, bit for bit (fma(1, |d|, a1) = a1 + |d|;
+// (1 d) d = d d).
+__global__ __launch_bounds__(256) void k_eval_view_masked(ViewK v, const float4* __restrict__ saved4,
+                                                          const float* __restrict__ y, const float* __restrict__ mask,
+                                                          float* __restrict__ partial, int plane) {
+  constexpr int C = 3, TC = ST * C, SP = SE * C;
+  __shared__ float tx[SE * SP], ty[SE * SP];
+  __shared__ float hs[5][SE * TC];
+  __shared__ float red[256];
+  __shared__ float tm[ST * ST], ta[ST * ST];
+  const int H = v.H, W = v.W, WC = W * C;
+  const int t = threadIdx.x;
+  const int y0 = blockIdx.y * ST, x0 = blockIdx.x * ST, v0 = blockIdx.x * TC;
+  const int ty0 = y0 + t / ST, tx0 = x0 + (t & (ST - 1));  // this thread's pixel of the tile
+  const bool pin = ty0 < H && tx0 < W;
+  tm[t] = pin ? mask[(int64_t)ty0 * W + tx0] : 0.0f;
+  for (int e = t; e < SE * SE; e += 256) {
+    const int r = e / SE, c = e - r * SE;
+    const int gy = y0 - SR + r, gx = x0 - SR + c;
+    float px[3] = {0.0f, 0.0f, 0.0f};
+    float al = 0.0f;
+    if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
+      const float4 s = saved4[(int64_t)gy * W + gx];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) px[k] = saved_colour(v, s, k);
+      al = saved_alpha(s);
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) tx[r * SP + c * C + k] = px[k];
+    if (r >= SR && r < SR + ST && c >= SR && c < SR + ST) ta[(r - SR) * ST + (c - SR)] = al;  // (each tile pixel once)
+  }
+  ssim_stage<C>(y, H, WC, y0, v0, ty);
+  __syncthreads();
+  float a1 = 0.0f, a2 = 0.0f;
+  for (int o = t; o < ST * TC; o += 256) {
+    const int r = o / TC, c = o - r * TC;
+    if (y0 + r < H && v0 + c < WC) {
+      const int at = (r + SR) * SP + SR * C + c;
+      const float d = tx[at] - ty[at], m = tm[r * ST + c / C];
+      a1 = fmaf(m, fabsf(d), a1);
+      a2 = fmaf(m * d, d, a2);
+    }
+  }
+  float sm = 0.0f, sa = 0.0f, ni = 0.0f, nu = 0.0f;
+  if (pin) {
+    const float m = tm[t], a = ta[t];
+    const bool fa = a > 0.5f, fm = m > 0.5f;
+    sm = m;
+    sa = fabsf(a - m);
+    ni = (fa && fm) ? 1.0f : 0.0f;
+    nu = (fa || fm) ? 1.0f : 0.0f;
+  }
+  ssim_fwd_tile_masked(tx, ty, tm, hs, red, H, W, partial + 3 * (size_t)plane);
+  // behind the tile function's last barrier nothing reads hs any more (as k_eval_view): the six other trees run there
+  float* rd = &hs[0][0];
+  rd[t] = sm;
+  rd[256 + t] = a1;
+  rd[512 + t] = a2;
+  rd[768 + t] = sa;
+  rd[1024 + t] = ni;
+  rd[1280 + t] = nu;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (t < w)
+#pragma unroll
+      for (int q = 0; q < 6; ++q) rd[256 * q + t] += rd[256 * q + t + w];
+    __syncthreads();
+  }
+  if (t < 6) {  // (plane 3 is the tile function's)
+    const int tile = blockIdx.y * gridDim.x + blockIdx.x;
+    partial[(size_t)(t < 3 ? t : t + 1) * plane + tile] = rd[256 * t];
+  }
+}
+
+// The six masked metrics (include/gr_hip.h) from k_eval_view_masked's seven planes, one block: each plane summed over the
+// tiles in double in k_eval_final's order.  The masked SSIM is formed as k_eval_final forms the plain one (1 - the float
+// dssim), so that a mask of ones gives gr_eval_view's three metrics bit for bit; an empty mask (M = 0) gives 0 in rows
+// 1..3, an empty union an IoU of 1.
+__global__ __launch_bounds__(256) void k_eval_masked_final(const float* __restrict__ partial, int plane, int blocks, double hw,
+                                                           float* __restrict__ metrics) {
+  constexpr int Q = 7;
+  __shared__ double r[Q][256];
+  const int t = threadIdx.x;
+  double s[Q];
+#pragma unroll
+  for (int q = 0; q < Q; ++q) s[q] = 0.0;
+  for (int i = t; i < blocks; i += 256)
+#pragma unroll
+    for (int q = 0; q < Q; ++q) s[q] += (double)partial[(size_t)q * plane + i];
+#pragma unroll
+  for (int q = 0; q < Q; ++q) r[q][t] = s[q];
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (t < w)
+#pragma unroll
+      for (int q = 0; q < Q; ++q) r[q][t] += r[q][t + w];
+    __syncthreads();
+  }
+  if (t == 0) {
+    const double M = r[0][0], n = 3.0 * M;
+    const bool any = M > 0.0;
+    metrics[0] = (float)(M / hw);
+    metrics[1] = any ? (float)(r[1][0] / n) : 0.0f;
+    metrics[2] = any ? (float)(r[2][0] / n) : 0.0f;
+    metrics[3] = any ? 1.0f - (float)(1.0 - r[3][0] / n) : 0.0f;
+    metrics[4] = (float)(r[4][0] / hw);
+    metrics[5] = r[6][0] > 0.0 ? (float)(r[5][0] / r[6][0]) : 1.0f;
+  }
+}
+
 // d dssim / d x, the same tiling: the three maps are convolved with the window (symmetric, zero padding: the
 // transposed convolution is the convolution itself) and
 //   g_x = -(g / (H W C)) (conv(maps[0]) + 2 x conv(maps[1]) + y conv(maps[2])),  g = *g_loss.
@@ -7236,6 +7419,29 @@ gr_status gr_eval_view_cc(const gr_view* v, const float* saved, const float* tar
   GR_HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(k_eval_final, dim3(1), dim3(256), 0, s, (const float*)ws, plane, vk.tiles_x * vk.tiles_y,
                      (int64_t)v->height * v->width * 3, metrics);
+  GR_HIP_TRY(hipGetLastError());
+  return GR_OK;
+}
+
+// Masked metrics: seven planes of per-tile float partial sums (k_eval_view_masked).
+size_t gr_eval_mask_ws_bytes(const gr_view* v) {
+  if (!v || !ssim_shape_ok(v->height, v->width, 3)) return 0;
+  return 7 * ssim_partial_bytes(v->height, v->width);
+}
+
+gr_status gr_eval_view_masked(const gr_view* v, const float* saved, const float* target_rgb, const float* target_mask,
+                              float* metrics, void* ws, size_t ws_bytes, void* stream) {
+  const gr_status st = eval_view_checks("gr_eval_view_masked", v, saved, target_rgb, target_mask && metrics, ws, ws_bytes,
+                                        gr_eval_mask_ws_bytes(v));
+  if (st != GR_OK) return st;
+  hipStream_t s = (hipStream_t)stream;
+  const ViewK vk = make_viewk(v);
+  const int plane = (int)(ssim_partial_bytes(v->height, v->width) / sizeof(float));
+  hipLaunchKernelGGL(k_eval_view_masked, dim3(vk.tiles_x, vk.tiles_y), dim3(256), 0, s, vk, (const float4*)saved, target_rgb,
+                     target_mask, (float*)ws, plane);
+  GR_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_eval_masked_final, dim3(1), dim3(256), 0, s, (const float*)ws, plane, vk.tiles_x * vk.tiles_y,
+                     (double)v->height * (double)v->width, metrics);
   GR_HIP_TRY(hipGetLastError());
   return GR_OK;
 }

@@ -489,6 +489,10 @@ def bucketed_all_reduce(buckets: list, assemble: Callable[[int], None], finish: 
         finish(b)
 
 
+# The row of the masked view metrics (gr_eval_view_masked; fg_psnr is formed from fg_mse on the host)
+MASK_KEYS = ("fg_fraction", "fg_l1", "fg_mse", "fg_ssim", "sil_l1", "sil_iou")
+
+
 def hip_render(means, scales, colors, opacities, cam, width, height, background, prepared=None, depth_grad=True):
     return tr.render_gaussians_torch(means, scales, colors, opacities, cam, width=width, height=height,
                                      background=background, max_gaussians=max(10000, int(means.shape[0])), return_aux=True,
@@ -2151,18 +2155,19 @@ class ViewShardedFitter:
             return activations_native(self.params)[:4]
         return tuple(t.detach() for t in activations(self.params))
 
-    def _exec_views(self, fn: str, m, s, c, o, gvs, targets, out, extra: tuple = ()) -> None:
+    def _exec_views(self, fn: str, m, s, c, o, gvs, targets, out, extra: tuple = (), masks=None) -> None:
         """One native executor call over views that are only rendered: gr_eval_views (the views' metrics against
         ``targets`` into ``out`` (len(gvs), 3)), gr_eval_views_cc (the same with the corrected metrics and the transform:
         ``out`` (len(gvs), 18), ``extra`` its ridge, the argument before ``out``), gr_contrib_views (targets None: every
         view's peak blend weights into the one ``out``) or gr_error_views (every view's blend-weighted error against
-        ``targets`` into the one ``out``).  ``extra``: the entry's own arguments before ``out``."""
+        ``targets`` into the one ``out``).  ``extra``: the entry's own arguments before ``out``.  gr_eval_views_masked:
+        ``masks`` the views' (H, W) masks, ``out`` (len(gvs), 9): the 3 metrics and the 6 masked ones."""
         device = m.device
         arr = (tr._native.GrFitTarget * len(gvs))()
         for j, gv in enumerate(gvs):
             arr[j].view = gv
             arr[j].target_rgb = targets[j].data_ptr() if targets is not None else None
-            arr[j].target_mask = None
+            arr[j].target_mask = masks[j].data_ptr() if masks is not None else None
             arr[j].target_depth = None
         cfg = self._exec_config(device, max(1, min(NUM_STREAMS, len(gvs))))
         tr._native.check(getattr(tr._native.lib(), fn)(
@@ -2181,16 +2186,17 @@ class ViewShardedFitter:
 
         self._view_loop(m.device, len(gvs), self._preparer(m, s, c, o, gvs.__getitem__, len(gvs)), body)
 
-    def _pass_views(self, fn: str, m, s, c, o, gvs, targets, out, view_call: Callable, extra: tuple = ()) -> None:
-        """A render-only pass over ``gvs``: the native executor's ``fn`` (_exec_views, ``extra`` its own arguments) where
-        the fit step uses it, else the Python schedule of the same calls (_pass_direct)."""
+    def _pass_views(self, fn: str, m, s, c, o, gvs, targets, out, view_call: Callable, extra: tuple = (), masks=None) -> None:
+        """A render-only pass over ``gvs``: the native executor's ``fn`` (_exec_views, ``extra`` its own arguments, ``masks``
+        the views' masks where it reads them) where the fit step uses it, else the Python schedule of the same calls
+        (_pass_direct)."""
         if self._native_exec() and GATHER:
-            self._exec_views(fn, m, s, c, o, gvs, targets, out, extra)
+            self._exec_views(fn, m, s, c, o, gvs, targets, out, extra, masks)
         else:
             self._pass_direct(m, s, c, o, gvs, view_call)
 
     def evaluate(self, cams: Optional[list] = None, targets: Optional[list] = None, color_correct: bool = False,
-                 ridge: float = losses.CC_RIDGE) -> dict:
+                 ridge: float = losses.CC_RIDGE, masks=None) -> dict:
         """Per-view metrics of the current Gaussians against target images: float64 numpy arrays ``l1`` (mean|x - y|),
         ``mse``, ``psnr`` (-10 log10 mse, formed on the host in double; inf at zero error) and ``ssim`` in the order of
         the views passed, and their means ``mean_l1`` .. ``mean_ssim``.  Default views: the fitter's own training
@@ -2209,7 +2215,18 @@ class ViewShardedFitter:
         balance of the photos does not move, for training and held-out views alike), and ``cc_transform``, the (V, 3, 4)
         float64 array of those transforms.  On the HIP device gr_eval_views_cc (else the Python schedule of
         gr_eval_view, gr_cc_fit_view, gr_eval_view_cc), otherwise losses.image_metrics_cc; the all-reduced tensor is
-        (V, 18).  With False the call, the dict and its bits are as without the argument."""
+        (V, 18).  With False the call, the dict and its bits are as without the argument.
+        masks: a list of (H, W) masks, one per evaluated view (values as weights, expected in [0, 1]), or True for the
+        fitter's own training masks (the default views only).  The dict gains ``fg_fraction`` (the mask's mean),
+        ``fg_l1``, ``fg_mse``, ``fg_psnr``, ``fg_ssim`` (the metrics weighted by the mask, over its sum: the object, not
+        the background; NaN for a view whose mask is empty), ``sil_l1`` (mean|alpha - mask|, the fit's silhouette term
+        unweighted) and ``sil_iou`` (alpha and mask thresholded at 0.5), include/gr_hip.h, and their ``mean_*``: the
+        ``mean_fg_*`` over the views with a non-empty mask (NaN if there is none), the ``mean_sil_*`` over all views.  On
+        the HIP device, with exact-shape float32 contiguous masks there, gr_eval_views_masked (else the Python schedule
+        of gr_eval_view and gr_eval_view_masked, one render serving both); otherwise render_fn's image and alpha and
+        losses.image_metrics_masked.  Six more columns of the one all-reduced tensor.  With color_correct=True the two
+        passes run one after the other, each with its own render.  The plain keys keep their bits; None: as without
+        the argument."""
         self.graph_sync()
         if color_correct and not (math.isfinite(ridge) and ridge > 0.0):
             raise ValueError(f"evaluate: ridge must be positive and finite, got {ridge}")
@@ -2219,44 +2236,78 @@ class ViewShardedFitter:
             cams, targets = self.cams, self.targets
         if len(cams) != len(targets):
             raise ValueError(f"evaluate: {len(cams)} cameras for {len(targets)} targets")
+        if masks is True:
+            if cams is not self.cams:
+                raise ValueError("evaluate: masks=True means the training views' masks; pass the masks of other views")
+            if self.masks is None:
+                raise ValueError("evaluate: masks=True, but the fitter has no masks")
+            masks = self.masks
+        if masks is not None:
+            if not isinstance(masks, (list, tuple)) or len(masks) != len(targets):
+                raise ValueError(f"evaluate: masks is a list of one (H, W) mask per view ({len(targets)}), or True")
+            for k in masks:
+                if not isinstance(k, torch.Tensor) or tuple(k.shape) != (self.height, self.width):
+                    raise ValueError(f"evaluate: a mask is a ({self.height}, {self.width}) tensor, got "
+                                     f"{tuple(k.shape) if isinstance(k, torch.Tensor) else type(k)}")
         V = len(targets)
         device = self.params["means"].device
         n = int(self.params["means"].shape[0])
         mine = list(range(self.rank, V, self.world))
         NM = tr._native.EVAL_METRICS
         cols = tr._native.EVAL_CC_ROW if color_correct else NM
-        res = torch.zeros((V, cols), dtype=torch.float32, device=device)
+        NK = tr._native.EVAL_MASK_METRICS if masks is not None else 0  # the masked metrics: the row's last columns
+        res = torch.zeros((V, cols + NK), dtype=torch.float32, device=device)
         with torch.no_grad():
             means, scales, colors, opacities = self._eval_activations(device)
-            if mine and n > 0 and self._eval_native_ok(device, [targets[i] for i in mine]):
+            if (mine and n > 0 and self._eval_native_ok(device, [targets[i] for i in mine])
+                    and (masks is None or all(k.dtype == torch.float32 and k.is_contiguous() and k.device == device
+                                              for k in (masks[i] for i in mine)))):
                 m, s, c, o = (t.detach().float().contiguous() for t in (means, scales, colors, opacities))
                 gvs = [self._eval_view(cams[i], device) for i in mine]
-                out = torch.empty((len(mine), cols), dtype=torch.float32, device=device)
                 tg = [targets[i] for i in mine]
-                if color_correct:
-                    def view_cc(j, rs, pv):  # the executor's three calls on the view's saved sums, into its row
-                        tr.eval_view_native(rs, tg[j], out[j, :NM])
-                        tr.cc_fit_view_native(rs, tg[j], out[j, 2 * NM:], ridge)
-                        tr.eval_view_cc_native(rs, tg[j], out[j, 2 * NM:], out[j, NM:2 * NM])
+                if color_correct or masks is None:
+                    out = torch.empty((len(mine), cols), dtype=torch.float32, device=device)
+                    if color_correct:
+                        def view_cc(j, rs, pv):  # the executor's three calls on the view's saved sums, into its row
+                            tr.eval_view_native(rs, tg[j], out[j, :NM])
+                            tr.cc_fit_view_native(rs, tg[j], out[j, 2 * NM:], ridge)
+                            tr.eval_view_cc_native(rs, tg[j], out[j, 2 * NM:], out[j, NM:2 * NM])
 
-                    self._pass_views("gr_eval_views_cc", m, s, c, o, gvs, tg, out, view_cc, (ctypes.c_float(ridge),))
-                else:
-                    self._pass_views("gr_eval_views", m, s, c, o, gvs, tg, out,
-                                     lambda j, rs, pv: tr.eval_view_native(rs, tg[j], out[j]))
-                res[mine] = out
+                        self._pass_views("gr_eval_views_cc", m, s, c, o, gvs, tg, out, view_cc, (ctypes.c_float(ridge),))
+                    else:
+                        self._pass_views("gr_eval_views", m, s, c, o, gvs, tg, out,
+                                         lambda j, rs, pv: tr.eval_view_native(rs, tg[j], out[j]))
+                    res[mine, :cols] = out
+                if masks is not None:  # (beside color_correct: a pass of its own, with its own render)
+                    mk = [masks[i] for i in mine]
+                    outm = torch.empty((len(mine), NM + NK), dtype=torch.float32, device=device)
+
+                    def view_masked(j, rs, pv):  # the executor's two calls on the view's saved sums, into its row
+                        tr.eval_view_native(rs, tg[j], outm[j, :NM])
+                        tr.eval_view_masked_native(rs, tg[j], mk[j], outm[j, NM:])
+
+                    self._pass_views("gr_eval_views_masked", m, s, c, o, gvs, tg, outm, view_masked, masks=mk)
+                    if not color_correct:
+                        res[mine, :NM] = outm[:, :NM]
+                    res[mine, cols:] = outm[:, NM:]
             else:
                 for i in mine:
                     kw = {"depth_grad": False} if self.render_fn is hip_render else {}
                     pred = self.render_fn(means, scales, colors, opacities, cams[i], self.width, self.height,
                                           self._background(device), **kw)
+                    if masks is not None:
+                        if not (isinstance(pred, tuple) and len(pred) >= 2):
+                            raise ValueError("evaluate: masks need a render_fn that returns the alpha beside the image")
+                        mm = losses.image_metrics_masked(pred[0], pred[1], targets[i].to(device), masks[i].to(device))
+                        res[i, cols:] = torch.stack([torch.nan_to_num(mm[k], nan=0.0) for k in MASK_KEYS]).to(res)
                     pred = pred[0] if isinstance(pred, tuple) else pred
                     if color_correct:
                         mt = losses.image_metrics_cc(pred, targets[i].to(device), ridge)
-                        res[i] = torch.cat([torch.stack([mt[p + k] for p in ("", "cc_") for k in ("l1", "mse", "ssim")]),
-                                            mt["cc_transform"].reshape(-1)]).to(res)
+                        res[i, :cols] = torch.cat([torch.stack([mt[p + k] for p in ("", "cc_") for k in ("l1", "mse", "ssim")]),
+                                                   mt["cc_transform"].reshape(-1)]).to(res)
                     else:
                         mt = losses.image_metrics(pred, targets[i].to(device))
-                        res[i] = torch.stack([mt["l1"], mt["mse"], mt["ssim"]]).to(res)
+                        res[i, :cols] = torch.stack([mt["l1"], mt["mse"], mt["ssim"]]).to(res)
         if self.world > 1:
             dist.all_reduce(res, group=self.group)
         a = res.double().cpu().numpy()
@@ -2272,7 +2323,18 @@ class ViewShardedFitter:
                 cpsnr = -10.0 * np.log10(cmse)
             r.update({"cc_l1": cl1, "cc_mse": cmse, "cc_psnr": cpsnr, "cc_ssim": cssim, "mean_cc_l1": mean(cl1),
                       "mean_cc_mse": mean(cmse), "mean_cc_psnr": mean(cpsnr), "mean_cc_ssim": mean(cssim),
-                      "cc_transform": a[:, 2 * NM:].reshape(V, 3, 4).copy()})
+                      "cc_transform": a[:, 2 * NM:2 * NM + tr._native.CC_TRANSFORM].reshape(V, 3, 4).copy()})
+        if masks is not None:
+            k = {name: a[:, cols + q].copy() for q, name in enumerate(MASK_KEYS)}
+            some = k["fg_fraction"] > 0.0  # (an empty mask: the row holds zeros there)
+            for name in ("fg_l1", "fg_mse", "fg_ssim"):
+                k[name][~some] = np.nan
+            with np.errstate(divide="ignore"):
+                k["fg_psnr"] = -10.0 * np.log10(k["fg_mse"])
+            for name in ("fg_fraction", "fg_l1", "fg_mse", "fg_psnr", "fg_ssim", "sil_l1", "sil_iou"):
+                r[name] = k[name]
+                over = k[name][some] if name.startswith("fg_") and name != "fg_fraction" else k[name]
+                r["mean_" + name] = float(over.mean()) if len(over) else float("nan")
         return r
 
     # ---- contribution (peak blend weight per Gaussian) ----------------------------------------------------------
@@ -2567,6 +2629,11 @@ def main(argv=None) -> None:
                          "white balance of the photos do not move")
     ap.add_argument("--eval_ridge", type=float, default=losses.CC_RIDGE,
                     help="with --eval_color_correct: the ridge that pulls the fitted transform towards the identity")
+    ap.add_argument("--eval_masked", action="store_true",
+                    help="with an evaluation (--holdout_every / --eval_interval): also the masked metrics, PSNR / SSIM / "
+                         "L1 weighted by each evaluated view's mask (the object, not the background) and the silhouette's "
+                         "L1 and IoU against it (the fg_* and sil_* keys of eval.json); needs masks: --masks_dir, or the "
+                         "--mask_thresh rule with --silhouette_weight > 0")
     ap.add_argument("--refine_cameras", action="store_true",
                     help="fit the training views' poses with the Gaussians (a 6-vector per view, pose_view) and write "
                          "cameras_refined.npz (the --camera_npz schema)")
@@ -2616,6 +2683,9 @@ def main(argv=None) -> None:
             masks = [torch.from_numpy(_load_image(c, args.width, args.height, gray=True)).to(device) for c in cand]
     if masks is None and args.silhouette_weight > 0.0:
         masks = [(t.mean(dim=2) > args.mask_thresh).to(torch.float32) for t in targets]
+    if args.eval_masked and masks is None:
+        raise ValueError("--eval_masked needs masks: --masks_dir with a mask per target, or --silhouette_weight > 0 (the "
+                         "--mask_thresh rule)")
     depths = None
     if args.depth_dir:
         cand = [Path(args.depth_dir) / f"{p.stem}.png" for p in paths]
@@ -2645,6 +2715,7 @@ def main(argv=None) -> None:
         if not train:
             raise ValueError(f"--holdout_every {args.holdout_every} leaves no training view of {len(targets)}")
         eval_cams, eval_targets = [cams[i] for i in hold], [targets[i] for i in hold]
+        eval_masks = [masks[i] for i in hold] if args.eval_masked else None
         pick = lambda xs: None if xs is None else [xs[i] for i in train]  # noqa: E731
         targets, masks, depths, cams = pick(targets), pick(masks), pick(depths), pick(cams)
     do_eval = args.holdout_every > 0 or args.eval_interval > 0
@@ -2685,21 +2756,29 @@ def main(argv=None) -> None:
         if do_eval and ((args.eval_interval > 0 and (it + 1) % args.eval_interval == 0) or it + 1 == args.iters):
             # a collective (every rank); the held-out views if there are any, else the training views
             cc = dict(color_correct=True, ridge=args.eval_ridge) if args.eval_color_correct else {}
+            if args.eval_masked:  # (the held-out views' own masks; the training views' are the fitter's)
+                cc["masks"] = eval_masks if hold else True
             r = fitter.evaluate(eval_cams, eval_targets, **cc) if hold else fitter.evaluate(**cc)
             n_now = int(fitter.params["means"].shape[0])
             eval_log.append({"iter": it + 1, "n": n_now, "views": hold if hold else list(range(len(targets))),
                              "psnr": r["psnr"].tolist(), "ssim": r["ssim"].tolist(), "l1": r["l1"].tolist(),
                              "mean_psnr": r["mean_psnr"], "mean_ssim": r["mean_ssim"], "mean_l1": r["mean_l1"]})
-            if cc:
+            if args.eval_color_correct:
                 for k in ("psnr", "ssim", "l1"):
                     eval_log[-1].update({"cc_" + k: r["cc_" + k].tolist(), "mean_cc_" + k: r["mean_cc_" + k]})
                 eval_log[-1]["cc_transform"] = r["cc_transform"].tolist()
+            if args.eval_masked:
+                for k in ("fg_fraction", "fg_psnr", "fg_ssim", "fg_l1", "sil_l1", "sil_iou"):
+                    eval_log[-1].update({k: r[k].tolist(), "mean_" + k: r["mean_" + k]})
             if rank == 0:
                 print(f"eval iter {it+1:4d}  N={n_now}  PSNR={r['mean_psnr']:.3f} dB  SSIM={r['mean_ssim']:.5f}  "
                       f"L1={r['mean_l1']:.6f}  ({'held-out' if hold else 'training'} views: {len(r['psnr'])})")
-                if cc:
+                if args.eval_color_correct:
                     print(f"eval iter {it+1:4d}  colour-corrected: PSNR={r['mean_cc_psnr']:.3f} dB  "
                           f"SSIM={r['mean_cc_ssim']:.5f}  L1={r['mean_cc_l1']:.6f}")
+                if args.eval_masked:
+                    print(f"eval iter {it+1:4d}  masked: PSNR={r['mean_fg_psnr']:.3f} dB  SSIM={r['mean_fg_ssim']:.5f}  "
+                          f"L1={r['mean_fg_l1']:.6f}  silhouette L1={r['mean_sil_l1']:.6f}  IoU={r['mean_sil_iou']:.5f}")
         if (it + 1) % args.prune_interval == 0 or (it + 1) % args.densify_interval == 0:
             fitter.densify_and_prune(args.max_gaussians,
                                      args.densify_ratio if (it + 1) % args.densify_interval == 0 else 0.0,

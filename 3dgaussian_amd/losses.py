@@ -75,8 +75,8 @@ def l1_loss(a: torch.Tensor, b: torch.Tensor, c: Optional[torch.Tensor] = None, 
 SSIM_WINDOW, SSIM_SIGMA, SSIM_C1, SSIM_C2 = 11, 1.5, 1e-4, 9e-4
 
 
-def _ssim_mean_torch(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
-    """mean SSIM of two (H, W, C) images with torch ops (the CPU path): the definition of include/gr_hip.h."""
+def _ssim_map_torch(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """The SSIM map (1, C, H, W) of two (H, W, C) images with torch ops: the definition of include/gr_hip.h."""
     C = x.shape[2]
     r = SSIM_WINDOW // 2
     g = torch.exp(-(torch.arange(SSIM_WINDOW, dtype=torch.float64) - r) ** 2 / (2.0 * SSIM_SIGMA ** 2))
@@ -90,7 +90,12 @@ def _ssim_mean_torch(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
     mx, my = conv(X), conv(Y)
     sx, sy, sxy = conv(X * X) - mx * mx, conv(Y * Y) - my * my, conv(X * Y) - mx * my
     m = ((2.0 * mx * my + SSIM_C1) * (2.0 * sxy + SSIM_C2)) / ((mx * mx + my * my + SSIM_C1) * (sx + sy + SSIM_C2))
-    return m.mean()
+    return m
+
+
+def _ssim_mean_torch(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """mean SSIM of two (H, W, C) images with torch ops (the CPU path)."""
+    return _ssim_map_torch(x, y).mean()
 
 
 class _DSSIMLoss(torch.autograd.Function):
@@ -172,6 +177,36 @@ def image_metrics(pred: torch.Tensor, target: torch.Tensor) -> dict:
         return {"l1": torch.mean(torch.abs(d)), "mse": torch.mean(d * d), "psnr": psnr(x, y), "ssim": ssim(x, y)}
 
 
+def image_metrics_masked(pred: torch.Tensor, alpha: torch.Tensor, target: torch.Tensor, mask: torch.Tensor) -> dict:
+    """The masked view metrics of include/gr_hip.h (gr_eval_view_masked) from a rendered (H, W, 3) image, its (H, W)
+    alpha, the target and an (H, W) mask whose values are weights as given (expected in [0, 1]), composed from torch ops
+    (the reference route of ViewShardedFitter.evaluate(masks=...), and what it uses off the HIP device).  0-d tensors:
+    ``fg_fraction`` = M / HW with M = sum mask, ``fg_l1``, ``fg_mse``, ``fg_ssim`` = the mask-weighted sums of |pred -
+    target|, its square and the SSIM map (whole images: the windows are not masked) over 3 M, ``fg_psnr`` = -10 log10
+    fg_mse (those four NaN for M = 0), ``sil_l1`` = mean|alpha - mask| and ``sil_iou`` of alpha > 0.5 and mask > 0.5 (1 for
+    an empty union).  Element-wise in float32, the sums in float64.  No gradient."""
+    with torch.no_grad():
+        x, y = _ssim_args("image_metrics_masked", pred.detach(), target)
+        H, W = x.shape[:2]
+        if x.shape[2] != 3 or tuple(alpha.shape) != (H, W) or tuple(mask.shape) != (H, W):
+            raise ValueError(f"image_metrics_masked: an (H, W, 3) image with (H, W) alpha and mask, got {tuple(x.shape)}, "
+                             f"{tuple(alpha.shape)}, {tuple(mask.shape)}")
+        a, m = alpha.detach().float().to(x.device), mask.detach().float().to(x.device)
+        f64 = dict(dtype=torch.float64)
+        d = x - y
+        w = m[:, :, None]
+        M = m.sum(**f64)
+        n = 3.0 * M  # (0 / 0 = NaN for an empty mask)
+        fg_mse = (w * d * d).sum(**f64) / n
+        fa, fm = a > 0.5, m > 0.5
+        union = (fa | fm).sum(**f64)
+        return {"fg_fraction": M / (H * W), "fg_l1": (w * d.abs()).sum(**f64) / n, "fg_mse": fg_mse,
+                "fg_psnr": -10.0 * torch.log10(fg_mse),
+                "fg_ssim": (w * _ssim_map_torch(x, y)[0].permute(1, 2, 0)).sum(**f64) / n,
+                "sil_l1": (a - m).abs().sum(**f64) / (H * W),
+                "sil_iou": torch.where(union > 0, (fa & fm).sum(**f64) / union.clamp(min=1.0), torch.ones_like(union))}
+
+
 CC_RIDGE = 1e-6  # GR_CC_RIDGE (include/gr_hip.h)
 
 
@@ -221,5 +256,5 @@ def image_metrics_cc(pred: torch.Tensor, target: torch.Tensor, ridge: float = CC
         return out
 
 
-__all__ = ["l1_loss", "dssim_loss", "ssim", "psnr", "image_metrics", "apply_color_transform", "color_correct",
-           "image_metrics_cc"]
+__all__ = ["l1_loss", "dssim_loss", "ssim", "psnr", "image_metrics", "image_metrics_masked", "apply_color_transform",
+           "color_correct", "image_metrics_cc"]

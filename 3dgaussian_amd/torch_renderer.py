@@ -926,6 +926,25 @@ def eval_view_cc_native(st: RenderState, target, transform, metrics_out) -> None
                                     _native.ptr(metrics_out), _native.ptr(ws), ws.numel(), _stream(dev)), "gr_eval_view_cc")
 
 
+def eval_view_masked_native(st: RenderState, target, mask, metrics_out) -> None:
+    """gr_eval_view_masked on the current stream: ``metrics_out`` (``_native.EVAL_MASK_METRICS`` float32 on the device)
+    receives fg_fraction, fg_l1, fg_mse, fg_ssim (the view's metrics weighted by ``mask``, (H, W) float32, over its sum;
+    0 for an empty mask), sil_l1 (mean |alpha - mask|) and sil_iou (alpha and mask thresholded at 0.5) of the view's
+    render and alpha, formed from the state's saved sums, against ``target`` (H, W, 3) (include/gr_hip.h).  A mask of
+    ones gives eval_view_native's three metrics bit for bit.  Deterministic."""
+    L = _native.lib()
+    dev = st.saved.device
+    _check_operand(target, (st.gv.height, st.gv.width, 3), "target", dev)
+    if mask is None:
+        raise ValueError("mask: expected an (H, W) float32 tensor, got None")
+    _check_operand(mask, (st.gv.height, st.gv.width), "mask", dev)
+    _check_operand(metrics_out, (_native.EVAL_MASK_METRICS,), "metrics_out", dev)
+    ws = torch.empty((int(L.gr_eval_mask_ws_bytes(ctypes.byref(st.gv))),), dtype=torch.uint8, device=dev)
+    _native.check(L.gr_eval_view_masked(ctypes.byref(st.gv), _native.ptr(st.saved), _native.ptr(target), _native.ptr(mask),
+                                        _native.ptr(metrics_out), _native.ptr(ws), ws.numel(), _stream(dev)),
+                  "gr_eval_view_masked")
+
+
 def contrib_view_native(rs: RenderState, pv: Prepared, peak) -> None:
     """gr_contrib_view on the current stream: ``peak`` ((n,) float32 on the device, zeroed by the caller) takes, per
     Gaussian, the maximum of its value and the Gaussian's largest blend weight w / (1 + W) over the pixels of its kept
@@ -1333,5 +1352,5 @@ __all__ = ["Camera", "get_default_device", "perspective", "look_at", "render_gau
            "make_view", "prepare_view", "prepare_native", "Prepared", "forward_native", "backward_native",
            "backward_l1_native", "backward_fit_native", "backward_fit_gather_native", "forward_l1_native", "backward_splat_native", "reduce_views_native",
            "gather_view_native", "reduce_sums_native", "density_stats_native", "camera_grads_sums_native", "eval_view_native",
-           "cc_fit_view_native", "eval_view_cc_native", "contrib_view_native", "error_view_native",
+           "cc_fit_view_native", "eval_view_cc_native", "eval_view_masked_native", "contrib_view_native", "error_view_native",
            "DEFAULT_CUTOFF", "DEPTH_GRAD_CUTOFF", "DEFAULT_CORE_CUTOFF", "FIT_CUTOFF", "default_cutoff"]

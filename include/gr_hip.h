@@ -554,6 +554,40 @@ gr_status gr_eval_views_cc(gr_executor* executor, const gr_fit_config* config, i
                            const float* colors, int color_dim, const float* opacities, float ridge,
                            float* rows /* device [num_views][GR_EVAL_CC_ROW] */, void* stream);
 
+/* Masked view metrics (an extension): on an object in front of a background the whole-image metrics are dominated by
+ * the background, and the fit's silhouette term has no held-out reading.  Per view, with x_k(p) the colour gr_eval_view
+ * compares, a(p) = clamp(W / (1 + W), 0, 1) the alpha gr_fwd_render composes (both from `saved`), t = target_rgb,
+ * m = target_mask ((H,W) float32 device; its values are weights as given, expected in [0, 1]), M = sum_p m(p) and s_k(p)
+ * the SSIM map of gr_ssim_fwd on the whole images (the windows are not masked):
+ *   metrics[0] fg_fraction = M / HW
+ *   metrics[1] fg_l1       = sum_p m sum_k |x_k - t_k| / (3 M)
+ *   metrics[2] fg_mse      = sum_p m sum_k (x_k - t_k)^2 / (3 M)       (the caller forms the PSNR, as for gr_eval_view)
+ *   metrics[3] fg_ssim     = sum_p m sum_k s_k / (3 M), as 1 - the float dssim = 1 - that, the way gr_eval_view forms its own
+ *   metrics[4] sil_l1      = sum_p |a - m| / HW                        (the fit's silhouette term, unweighted)
+ *   metrics[5] sil_iou     = #{a > 0.5 and m > 0.5} / #{a > 0.5 or m > 0.5}, strict comparisons; an empty union gives 1
+ * M = 0 (an empty mask) gives 0 in metrics[1..3].  With m = 1 everywhere metrics[1..3] are gr_eval_view's three bit for
+ * bit.  One launch on gr_eval_view's grid writes seven float partial sums per 16 x 16 tile into ws (planes as
+ * gr_eval_view's: sum m, sum m|d|, sum m d^2, sum m s, sum |a - m|, the two counts), one single-block launch sums them in
+ * double and writes the six floats.
+ *   - refusals as gr_eval_view's (tile = 32, rows > 0, null pointers, target_mask among them: GR_ERR_INVALID_ARGUMENT;
+ *     ws shorter than gr_eval_mask_ws_bytes: GR_ERR_WORKSPACE; nothing is launched)
+ *   - stream-ordered, no allocation, no atomics, deterministic */
+#define GR_EVAL_MASK_METRICS 6
+size_t gr_eval_mask_ws_bytes(const gr_view* v);
+gr_status gr_eval_view_masked(const gr_view* v, const float* saved, const float* target_rgb, const float* target_mask,
+                              float* metrics /* device, GR_EVAL_MASK_METRICS floats */, void* ws, size_t ws_bytes,
+                              void* stream);
+/* gr_eval_views with the masked metrics: the same schedule, per view gr_fwd_render keeping the saved sums only, then
+ * gr_eval_view into metrics[j][0..2] and gr_eval_view_masked into metrics[j][3..8] on the same saved sums (one render
+ * serves both), in the stream's one pass workspace (gr_eval_mask_ws_bytes, the larger: the calls follow one another).
+ * target_mask, which gr_eval_views ignores, is read here: NULL in any view gives GR_ERR_INVALID_ARGUMENT before anything
+ * is enqueued.  Checks, ordering and guarantees as gr_eval_views; bit-identical to the per-view calls. */
+gr_status gr_eval_views_masked(gr_executor* executor, const gr_fit_config* config, int num_views,
+                               const gr_fit_target* views, int n, const float* means, const float* scales,
+                               const float* colors, int color_dim, const float* opacities,
+                               float* metrics /* device [num_views][GR_EVAL_METRICS + GR_EVAL_MASK_METRICS] */,
+                               void* stream);
+
 /* Peak blend weight per Gaussian, for contribution-based pruning (an extension: the reference prunes by opacity).
  * Compositing is out = clamp((bg + sum w c) / (1 + W)), so a Gaussian's share of pixel p is its blend weight
  * b = w(p) / (1 + W(p)); removing the Gaussian moves no channel of that pixel by more than b / (1 - b).

@@ -14,9 +14,11 @@
 4. --color_correct: instead of 1 and 2, evaluate(color_correct=True) against evaluate() of the same fitter, through the
    executor (gr_eval_views_cc / gr_eval_views) and the Python schedule, in alternating windows; with --kernel-loop a
    loop of the three per-view calls (gr_eval_view, gr_cc_fit_view, gr_eval_view_cc) for a kernel trace.
+5. --masked: the same for evaluate(masks=True) (gr_eval_views_masked / gr_eval_views); with --kernel-loop a loop of the two
+   per-view calls (gr_eval_view, gr_eval_view_masked): k_eval_view_masked beside k_eval_view.
 
     python tools/eval_bench.py [--gaussians 1000000 --views 50 --res 800] [--reps 3] [--windows 5] [--label C4]
-                               [--out FILE (appended)] [--kernel-loop] [--color_correct]
+                               [--out FILE (appended)] [--kernel-loop] [--color_correct | --masked]
 """
 import argparse
 import importlib
@@ -128,21 +130,35 @@ def cc_kernel_loop(n, R, calls, dev):
     print(f"kernel loop: {calls} x (gr_eval_view, gr_cc_fit_view, gr_eval_view_cc) at {R}x{R}, {n} Gaussians")
 
 
-def cc_lines(fit, args, R):
-    """--color_correct: evaluate(color_correct=True) against evaluate() of the same fitter, the executor and the Python
-    schedule, in alternating windows."""
-    def evaluate(native, cc):
+def masked_kernel_loop(n, R, calls, dev):
+    """--masked --kernel-loop: the two per-view calls of gr_eval_views_masked, for a kernel trace (k_eval_view_masked and
+    k_eval_masked_final beside k_eval_view and k_eval_final)."""
+    _, st = view_state(n, R, dev)
+    target = torch.rand((R, R, 3), device=dev)
+    mask = (target.mean(dim=2) > 0.5).float()
+    row = torch.zeros(9, device=dev)
+    for _ in range(calls):
+        tr.eval_view_native(st, target, row[:3])
+        tr.eval_view_masked_native(st, target, mask, row[3:])
+    torch.cuda.synchronize()
+    print(f"kernel loop: {calls} x (gr_eval_view, gr_eval_view_masked) at {R}x{R}, {n} Gaussians")
+
+
+def option_lines(fit, args, R, name, kw, tail):
+    """--color_correct, --masked: evaluate(**kw) (``name`` in the lines) against evaluate() of the same fitter, the
+    executor and the Python schedule, in alternating windows; ``tail(result)``: the end of the last line."""
+    def evaluate(native, on):
         saved = fm.NATIVE_EXEC
         fm.NATIVE_EXEC = native
         try:
-            return fit.evaluate(color_correct=cc)
+            return fit.evaluate(**(kw if on else {}))
         finally:
             fm.NATIVE_EXEC = saved
 
-    ways = {"executor, plain": lambda: evaluate("1", False), "executor, color_correct": lambda: evaluate("1", True),
-            "Python schedule, plain": lambda: evaluate("0", False), "Python schedule, color_correct": lambda: evaluate("0", True)}
+    ways = {"executor, plain": lambda: evaluate("1", False), f"executor, {name}": lambda: evaluate("1", True),
+            "Python schedule, plain": lambda: evaluate("0", False), f"Python schedule, {name}": lambda: evaluate("0", True)}
     res = {k: f() for k, f in ways.items()}  # warm-up, and the agreement
-    a, b = res["executor, color_correct"], res["Python schedule, color_correct"]
+    a, b = res[f"executor, {name}"], res[f"Python schedule, {name}"]
     same = all((a[k] == b[k]).all() for k in a if hasattr(a[k], "all"))
     plain_same = all((a[k] == res["executor, plain"][k]).all() for k in ("l1", "mse", "ssim"))
     times = {k: [] for k in ways}
@@ -157,12 +173,11 @@ def cc_lines(fit, args, R):
         lines.append(f"  {k:32s}: {med[k]:9.3f} ms  [{min(times[k]):.3f} .. {max(times[k]):.3f}]  "
                      f"{1e3 * med[k] / args.views:.1f} us per view")
     for w in ("executor", "Python schedule"):
-        d = med[w + ", color_correct"] - med[w + ", plain"]
-        lines.append(f"  {w}: color_correct adds {1e3 * d / args.views:.1f} us per view "
-                     f"({med[w + ', color_correct'] / med[w + ', plain']:.3f}x)")
+        d = med[f"{w}, {name}"] - med[w + ", plain"]
+        lines.append(f"  {w}: {name} adds {1e3 * d / args.views:.1f} us per view "
+                     f"({med[f'{w}, {name}'] / med[w + ', plain']:.3f}x)")
     lines.append(f"  executor and Python schedule {'bit-identical' if same else 'DIFFER'}; plain keys "
-                 f"{'unchanged by the argument' if plain_same else 'DIFFER'}; mean PSNR {a['mean_psnr']:.3f} dB, corrected "
-                 f"{a['mean_cc_psnr']:.3f} dB")
+                 f"{'unchanged by the argument' if plain_same else 'DIFFER'}; mean PSNR {a['mean_psnr']:.3f} dB, {tail(a)}")
     return lines
 
 
@@ -182,13 +197,17 @@ def main():
     ap.add_argument("--color_correct", action="store_true",
                     help="instead of parts 1 and 2: evaluate(color_correct=True) against evaluate() (executor and Python "
                          "schedule); with --kernel-loop: the three per-view calls of gr_eval_views_cc")
+    ap.add_argument("--masked", action="store_true",
+                    help="instead of parts 1 and 2: evaluate(masks=True) against evaluate() (executor and Python schedule); "
+                         "with --kernel-loop: the two per-view calls of gr_eval_views_masked")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("eval_bench: no HIP device (timings are taken on the GPU only)")
     dev = torch.device("cuda", 0)
     R = args.res
     if args.kernel_loop:
-        return (cc_kernel_loop if args.color_correct else kernel_loop)(args.gaussians, R, 20, dev)
+        loop = cc_kernel_loop if args.color_correct else masked_kernel_loop if args.masked else kernel_loop
+        return loop(args.gaussians, R, 20, dev)
     cams = fm.orbit_cameras(args.views, R, R, dev)
     g = torch.Generator(device=dev).manual_seed(3)
     targets = [torch.rand((R, R, 3), generator=g, device=dev) for _ in cams]
@@ -197,8 +216,14 @@ def main():
     for _ in range(3):
         fit.step()
     fit.graph_sync()
-    if args.color_correct:
-        text = "\n".join(cc_lines(fit, args, R)) + "\n"
+    if args.color_correct or args.masked:
+        if args.color_correct:
+            lines = option_lines(fit, args, R, "color_correct", dict(color_correct=True),
+                                 lambda a: f"corrected {a['mean_cc_psnr']:.3f} dB")
+        else:
+            lines = option_lines(fit, args, R, "masked", dict(masks=True),
+                                 lambda a: f"masked {a['mean_fg_psnr']:.3f} dB, silhouette IoU {a['mean_sil_iou']:.4f}")
+        text = "\n".join(lines) + "\n"
         print(text)
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
