@@ -131,6 +131,45 @@ struct Pass {
   float* out = nullptr;  // eval, eval_cc, eval_masked: the views' rows; contrib, error: the one per-Gaussian buffer
   float ridge = 0.0f;    // eval_cc: gr_cc_fit_view's
   bool fwd_only() const { return kind != fit; }
+
+  // A render-only pass, stated once per kind.  The floats of a view's row in `out` (0: the one per-Gaussian buffer):
+  int row_width() const {
+    switch (kind) {
+      case eval: return GR_EVAL_METRICS;
+      case eval_cc: return GR_EVAL_CC_ROW;
+      case eval_masked: return GR_EVAL_METRICS + GR_EVAL_MASK_METRICS;
+      default: return 0;
+    }
+  }
+  // the workspace of a view's calls (one after another on the view's stream, so the largest of their sizes):
+  size_t ws_bytes(const gr_view* v, int n, const gr_plan* plan) const {
+    switch (kind) {
+      case eval_cc: return std::max(gr_eval_ws_bytes(v), gr_cc_ws_bytes(v));
+      case eval_masked: return std::max(gr_eval_ws_bytes(v), gr_eval_mask_ws_bytes(v));
+      case contrib: return gr_contrib_ws_bytes(v, n, plan);
+      case error: return gr_error_ws_bytes(v, n, plan);
+      default: return gr_eval_ws_bytes(v);
+    }
+  }
+  // and the calls on view j's saved sums (W.saved, in W.pass): a metric pass begins with gr_eval_view into the row's
+  // first three columns, then the kind's own into the columns behind; contrib, error: atomic maxima into `out`.
+  gr_status on_saved(int j, const gr_fit_target& t, int n, const gr_plan* plan, const void* geom, const void* bins,
+                     const StreamWs& W, void* s) const {
+    const gr_view* v = &t.view;
+    const float* saved = (const float*)W.saved.p;
+    float* row = out + (size_t)row_width() * j;
+    float* own = row + GR_EVAL_METRICS;
+    if (row_width() > 0) GR_EXEC_CALL(gr_eval_view(v, saved, t.target_rgb, row, W.pass.p, W.pass.cap, s));
+    switch (kind) {
+      case eval_cc:  // (the transform behind the corrected metrics)
+        GR_EXEC_CALL(gr_cc_fit_view(v, saved, t.target_rgb, ridge, own + GR_EVAL_METRICS, W.pass.p, W.pass.cap, s));
+        return gr_eval_view_cc(v, saved, t.target_rgb, own + GR_EVAL_METRICS, own, W.pass.p, W.pass.cap, s);
+      case eval_masked: return gr_eval_view_masked(v, saved, t.target_rgb, t.target_mask, own, W.pass.p, W.pass.cap, s);
+      case contrib: return gr_contrib_view(v, n, plan, geom, bins, saved, out, W.pass.p, W.pass.cap, s);
+      case error: return gr_error_view(v, n, plan, geom, bins, saved, t.target_rgb, out, W.pass.p, W.pass.cap, s);
+      default: return GR_OK;
+    }
+  }
 };
 
 static gr_status fit_views_on_device(gr_executor* ex, const gr_fit_config* cfg, int num_views, const gr_fit_target* views,
@@ -516,36 +555,12 @@ static gr_status enqueue_views(gr_executor* ex, const gr_fit_config* cfg, int nu
     if (!fwd_only) GR_EXEC_TRY(W.ws.fit(ws_bytes, s));
     void *bins = W.bins.p, *scratch = W.scratch.p, *ws = W.ws.p;
     if (fwd_only) {
-      // the saved sums only (no image, no depth output), then the pass's calls on them: the view's metrics (eval_cc,
-      // eval_masked: their calls one after another on this stream, so the workspace is the largest of their sizes), or
-      // its pairs' values into the one per-Gaussian buffer (atomic maxima)
-      const size_t pass_bytes = pass.kind == Pass::eval      ? gr_eval_ws_bytes(&v)
-                                : pass.kind == Pass::eval_cc ? std::max(gr_eval_ws_bytes(&v), gr_cc_ws_bytes(&v))
-                                : pass.kind == Pass::eval_masked ? std::max(gr_eval_ws_bytes(&v), gr_eval_mask_ws_bytes(&v))
-                                : pass.kind == Pass::contrib ? gr_contrib_ws_bytes(&v, n, &plan)
-                                                             : gr_error_ws_bytes(&v, n, &plan);
+      // the saved sums only (no image, no depth output), then the pass's calls on them
       GR_EXEC_TRY(W.saved.fit(gr_saved_floats(&v) * sizeof(float), s));
-      GR_EXEC_TRY(W.pass.fit(pass_bytes, s));
+      GR_EXEC_TRY(W.pass.fit(pass.ws_bytes(&v, n, &plan), s));
       GR_EXEC_CALL(gr_fwd_render(&v, n, &plan, geom[j], bins, W.bins.cap, scratch, W.scratch.cap, nullptr, nullptr,
                                  nullptr, (float*)W.saved.p, s));
-      const float* saved = (const float*)W.saved.p;
-      if (pass.kind == Pass::eval)
-        GR_EXEC_CALL(gr_eval_view(&v, saved, views[j].target_rgb, pass.out + (size_t)GR_EVAL_METRICS * j, W.pass.p, W.pass.cap, s));
-      else if (pass.kind == Pass::eval_cc) {
-        float* row = pass.out + (size_t)GR_EVAL_CC_ROW * j;
-        float* E = row + 2 * GR_EVAL_METRICS;
-        GR_EXEC_CALL(gr_eval_view(&v, saved, views[j].target_rgb, row, W.pass.p, W.pass.cap, s));
-        GR_EXEC_CALL(gr_cc_fit_view(&v, saved, views[j].target_rgb, pass.ridge, E, W.pass.p, W.pass.cap, s));
-        GR_EXEC_CALL(gr_eval_view_cc(&v, saved, views[j].target_rgb, E, row + GR_EVAL_METRICS, W.pass.p, W.pass.cap, s));
-      } else if (pass.kind == Pass::eval_masked) {
-        float* row = pass.out + (size_t)(GR_EVAL_METRICS + GR_EVAL_MASK_METRICS) * j;
-        GR_EXEC_CALL(gr_eval_view(&v, saved, views[j].target_rgb, row, W.pass.p, W.pass.cap, s));
-        GR_EXEC_CALL(gr_eval_view_masked(&v, saved, views[j].target_rgb, views[j].target_mask, row + GR_EVAL_METRICS, W.pass.p,
-                                         W.pass.cap, s));
-      } else if (pass.kind == Pass::contrib)
-        GR_EXEC_CALL(gr_contrib_view(&v, n, &plan, geom[j], bins, saved, pass.out, W.pass.p, W.pass.cap, s));
-      else
-        GR_EXEC_CALL(gr_error_view(&v, n, &plan, geom[j], bins, saved, views[j].target_rgb, pass.out, W.pass.p, W.pass.cap, s));
+      GR_EXEC_CALL(pass.on_saved(j, views[j], n, &plan, geom[j], bins, W, s));
     } else if (ssim) {
       // the saved sums only (no image: the D-SSIM forward stages the colours from them); sums3 with a depth target
       GR_EXEC_TRY(W.saved.fit(gr_saved_floats(&v) * sizeof(float), s));

@@ -4640,16 +4640,47 @@ __device__ __forceinline__ void ssim_stage(const float* __restrict__ src, int H,
   }
 }
 
+// The weight hook of a tile's sums over its values (r, c: the row and the value of the tile): `add` adds a term to a sum,
+// `mul` weights the first factor of a product that is then added by an fma; `channels`: the values per pixel the hook
+// indexes by (0: any).  NoWeight takes every term as it is.
+struct NoWeight {
+  static constexpr int channels = 0;
+  __device__ __forceinline__ float add(float acc, float x, int, int) const { return acc + x; }
+  __device__ __forceinline__ float mul(float x, int, int) const { return x; }
+};
+// Every term weighted by its pixel's mask value (tm: the tile's own 16 x 16 mask values of a three-channel image, no halo:
+// the windows are not masked).  Where the mask is 1 the sums are NoWeight's bit for bit (fma(1, x, acc) = acc + x; 1 x = x).
+struct TileMask {
+  static constexpr int channels = 3;
+  const float* tm;
+  __device__ __forceinline__ float w(int r, int c) const { return tm[r * ST + c / channels]; }
+  __device__ __forceinline__ float add(float acc, float x, int r, int c) const { return fmaf(w(r, c), x, acc); }
+  __device__ __forceinline__ float mul(float x, int r, int c) const { return w(r, c) * x; }
+};
+
+// The fixed tree of a tile's sums on K columns of 256 floats, column q at rd + 256 q (one value per thread, not yet
+// published): the sums end in rd[256 q], published by the last barrier.
+template <int K>
+__device__ __forceinline__ void tile_tree(float* rd) {
+  const int t = threadIdx.x;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (t < w)
+#pragma unroll
+      for (int q = 0; q < K; ++q) rd[256 * q + t] += rd[256 * q + t + w];
+    __syncthreads();
+  }
+}
+
 // GRAD: also writes, per value, the three maps the backward convolves (planes of H*W*C floats):
 //   maps[0] = dm/dmx with sx and sxy expressed through mx: 2 (my (A2 - A1) - mx m (B2 - B1)) / (B1 B2)
 //   maps[1] = dm/dsx = -m / B2            maps[2] = dm/dsxy = 2 A1 / (B1 B2)
 // The forward of one tile from its two staged windows tx, ty (published by a barrier): the separable sums, the tile's
-// sum of m into partial[tile] and (GRAD) the three maps.
-// FORM: the caller's own instantiation, the same code (k_eval_view passes 1: sharing k_ssim_fwd<3, false>'s instantiation
-// made that kernel's last tree step compile to other, equivalent instructions).
-template <int C, bool GRAD, int FORM = 0>
+// sum of m (each m added through the weight hook `wt`) into partial[tile] and (GRAD) the three maps.
+template <int C, bool GRAD, class Wt>
 __device__ __forceinline__ void ssim_fwd_tile(const float* tx, const float* ty, float (*hs)[SE * ST * C], float* red, int H,
-                                              int W, float* __restrict__ partial, float* __restrict__ maps) {
+                                              int W, float* __restrict__ partial, float* __restrict__ maps, const Wt& wt) {
+  static_assert(Wt::channels == 0 || Wt::channels == C, "the weight hook indexes pixels of another channel count");
   constexpr int TC = ST * C, SP = SE * C;
   const int t = threadIdx.x;
   const int WC = W * C;
@@ -4696,7 +4727,7 @@ __device__ __forceinline__ void ssim_fwd_tile(const float* tx, const float* ty, 
       const float B1 = fmaf(mx, mx, fmaf(my, my, SSIM_C1)), B2 = sx + sy + SSIM_C2;
       const float rr = 1.0f / (B1 * B2);
       const float m = (A1 * A2) * rr;
-      acc += m;
+      acc = wt.add(acc, m, r, c);
       if (GRAD) {
         const int64_t off = (int64_t)gy * WC + gv;
         maps[off] = 2.0f * rr * (my * (A2 - A1) - mx * m * (B2 - B1));
@@ -4706,11 +4737,7 @@ __device__ __forceinline__ void ssim_fwd_tile(const float* tx, const float* ty, 
     }
   }
   red[t] = acc;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (t < w) red[t] += red[t + w];
-    __syncthreads();
-  }
+  tile_tree<1>(red);
   if (t == 0) partial[blockIdx.y * gridDim.x + blockIdx.x] = red[0];
 }
 
@@ -4725,13 +4752,99 @@ __global__ __launch_bounds__(256) void k_ssim_fwd(const float* __restrict__ x, c
   ssim_stage<C>(x, H, W * C, y0, v0, tx);
   ssim_stage<C>(y, H, W * C, y0, v0, ty);
   __syncthreads();
-  ssim_fwd_tile<C, GRAD>(tx, ty, hs, red, H, W, partial, maps);
+  ssim_fwd_tile<C, GRAD>(tx, ty, hs, red, H, W, partial, maps, NoWeight());
 }
 
 // The rendered colour of a pixel from its saved sums s = (W, C_r, C_g, C_b), exactly as write_pixel wrote it.
 __device__ __forceinline__ float saved_colour(const ViewK& v, float4 s, int k) {
   const float den = 1.0f + s.x;
   return clamp01((view_bg(v, k) + (k == 0 ? s.y : (k == 1 ? s.z : s.w))) / den);
+}
+
+// The alpha of a pixel from its saved sums s = (W, ...), exactly as write_pixel wrote it.
+__device__ __forceinline__ float saved_alpha(float4 s) {
+  const float den = 1.0f + s.x;
+  return clamp01(s.x / den);
+}
+
+// The affine colour transform of the corrected metrics (include/gr_hip.h): E row-major [3][4], row k the output channel,
+//   y_k = ((E[k][0] x0 + E[k][1] x1) + E[k][2] x2) + E[k][3],
+// every product and sum rounded on its own in that order (what element-wise float32 operations on an image give).
+__device__ __forceinline__ float cc_apply(const float* e, int k, const float x[3]) {
+  return __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(e[4 * k], x[0]), __fmul_rn(e[4 * k + 1], x[1])), __fmul_rn(e[4 * k + 2], x[2])),
+                   e[4 * k + 3]);
+}
+
+// The staging hooks of stage_saved, called once per staged pixel inside the image (s its saved sums, r, c its row and
+// column of the staged window, x its rendered colour, which the hook may replace).  StageRender leaves the render as it is.
+struct StageRender {
+  __device__ __forceinline__ void operator()(float4, int, int, float*) const {}
+};
+// The colour-corrected render E (x, 1) (not clamped); E's 12 device floats are read once per workgroup.
+struct StageCorrected {
+  float em[GR_CC_TRANSFORM];
+  __device__ __forceinline__ explicit StageCorrected(const float* __restrict__ E) {
+#pragma unroll
+    for (int i = 0; i < GR_CC_TRANSFORM; ++i) em[i] = E[i];
+  }
+  __device__ __forceinline__ void operator()(float4, int, int, float* x) const {
+    const float u[3] = {x[0], x[1], x[2]};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) x[k] = cc_apply(em, k, u);
+  }
+};
+// The render as it is, and the alpha of the tile's own 256 pixels into ta (no halo; each tile pixel is staged by one
+// thread; a tile pixel outside the image is not written, and not read either).
+struct StageAlpha {
+  float* ta;
+  __device__ __forceinline__ void operator()(float4 s, int r, int c, float*) const {
+    if (r >= SR && r < SR + ST && c >= SR && c < SR + ST) ta[(r - SR) * ST + (c - SR)] = saved_alpha(s);
+  }
+};
+
+// Stages the tile + halo of a view's render from the saved sums of gr_fwd_render instead of an image, as ssim_stage<3>
+// stages one: tx[r * SE * 3 + 3 c + k] = channel k of pixel (r, c) of the staged window, saved_colour passed through the
+// staging hook inside the image, 0 outside it.
+template <class S>
+__device__ __forceinline__ void stage_saved(const ViewK& v, const float4* __restrict__ saved4, float* tx, const S& hook) {
+  constexpr int C = 3, SP = SE * C;
+  const int y0 = blockIdx.y * ST, x0 = blockIdx.x * ST;
+  for (int e = threadIdx.x; e < SE * SE; e += 256) {
+    const int r = e / SE, c = e - r * SE;
+    const int gy = y0 - SR + r, gx = x0 - SR + c;
+    float px[3] = {0.0f, 0.0f, 0.0f};
+    if (gy >= 0 && gy < v.H && gx >= 0 && gx < v.W) {
+      const float4 s = saved4[(int64_t)gy * v.W + gx];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) px[k] = saved_colour(v, s, k);
+      hook(s, r, c, px);
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) tx[r * SP + c * C + k] = px[k];
+  }
+}
+
+// Q planes of per-tile partial sums (plane q at part + q * plane), each summed over the tiles in double in one fixed
+// order: per thread at stride 256, then the 256-lane tree w = 128 .. 1.  One block of 256 threads; the totals end in
+// r[q][0], published by the last barrier.
+template <int Q, class T>
+__device__ __forceinline__ void plane_sums(const T* __restrict__ part, size_t plane, int blocks, double (*r)[256]) {
+  const int t = threadIdx.x;
+  double s[Q];  // (the Q planes' loads of a tile in flight together)
+#pragma unroll
+  for (int q = 0; q < Q; ++q) s[q] = 0.0;
+  for (int i = t; i < blocks; i += 256)
+#pragma unroll
+    for (int q = 0; q < Q; ++q) s[q] += (double)part[q * plane + i];
+#pragma unroll
+  for (int q = 0; q < Q; ++q) r[q][t] = s[q];
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (t < w)
+#pragma unroll
+      for (int q = 0; q < Q; ++q) r[q][t] += r[q][t + w];
+    __syncthreads();
+  }
 }
 
 // k_ssim_fwd<3, true> of a view's render against its target, the rendered image x staged from the saved sums of
@@ -4744,169 +4857,71 @@ __global__ __launch_bounds__(256) void k_ssim_fwd_saved(ViewK v, const float4* _
   __shared__ float tx[SE * SP], ty[SE * SP];
   __shared__ float hs[5][SE * TC];
   __shared__ float red[256];
-  const int H = v.H, W = v.W;
-  const int y0 = blockIdx.y * ST, x0 = blockIdx.x * ST;
-  for (int e = threadIdx.x; e < SE * SE; e += 256) {
-    const int r = e / SE, c = e - r * SE;
-    const int gy = y0 - SR + r, gx = x0 - SR + c;
-    float px[3] = {0.0f, 0.0f, 0.0f};
-    if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
-      const float4 s = saved4[(int64_t)gy * W + gx];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) px[k] = saved_colour(v, s, k);
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) tx[r * SP + c * C + k] = px[k];
-  }
-  ssim_stage<C>(y, H, W * C, y0, blockIdx.x * TC, ty);
+  stage_saved(v, saved4, tx, StageRender());
+  ssim_stage<C>(y, v.H, v.W * C, blockIdx.y * ST, blockIdx.x * TC, ty);
   __syncthreads();
-  ssim_fwd_tile<C, true>(tx, ty, hs, red, H, W, partial, maps);
+  ssim_fwd_tile<C, true>(tx, ty, hs, red, v.H, v.W, partial, maps, NoWeight());
 }
 
 __global__ __launch_bounds__(256) void k_ssim_final(const float* __restrict__ partial, int blocks, int64_t n,
                                                     float* __restrict__ dssim) {
-  __shared__ double r[256];
-  const int t = threadIdx.x;
-  double s = 0.0;
-  for (int i = t; i < blocks; i += 256) s += (double)partial[i];
-  r[t] = s;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (t < w) r[t] += r[t + w];
-    __syncthreads();
+  __shared__ double r[1][256];
+  plane_sums<1>(partial, 0, blocks, r);
+  if (threadIdx.x == 0) *dssim = (float)(1.0 - r[0][0] / (double)n);
+}
+
+// How a view metric is built (gr_eval_view, gr_eval_view_cc, gr_eval_view_masked): one workgroup per render tile stages
+// the render from the saved sums (stage_saved, the metric's staging hook) and the target (ssim_stage), takes the tile's
+// sums from the two staged windows without a second global read (diff_sums and ssim_fwd_tile, the metric's weight hook;
+// the trees behind the SSIM sum run in hs, which nothing reads behind ssim_fwd_tile's last barrier) and writes one float
+// per sum and tile, partial[q * plane + tile]; a final kernel of one block sums the planes (plane_sums) and thread 0
+// forms the metrics (the metric's epilogue).  LDS as the D-SSIM forward's: three workgroups per CU.
+
+// The tile's sums a1 of |d| and a2 of d^2, d = x - y, over its in-image values (three values per thread), each term
+// through the weight hook.
+template <class Wt>
+__device__ __forceinline__ void diff_sums(const float* tx, const float* ty, int H, int WC, const Wt& wt, float& a1, float& a2) {
+  constexpr int C = 3, TC = ST * C, SP = SE * C;
+  static_assert(Wt::channels == 0 || Wt::channels == C, "the weight hook indexes pixels of another channel count");
+  const int y0 = blockIdx.y * ST, v0 = blockIdx.x * TC;
+  a1 = a2 = 0.0f;
+  for (int o = threadIdx.x; o < ST * TC; o += 256) {
+    const int r = o / TC, c = o - r * TC;
+    if (y0 + r < H && v0 + c < WC) {
+      const int at = (r + SR) * SP + SR * C + c;
+      const float d = tx[at] - ty[at];
+      a1 = wt.add(a1, fabsf(d), r, c);
+      a2 = fmaf(wt.mul(d, r, c), d, a2);
+    }
   }
-  if (t == 0) *dssim = (float)(1.0 - r[0] / (double)n);
 }
 
-// The affine colour transform of the corrected metrics (include/gr_hip.h): E row-major [3][4], row k the output channel,
-//   y_k = ((E[k][0] x0 + E[k][1] x1) + E[k][2] x2) + E[k][3],
-// every product and sum rounded on its own in that order (what element-wise float32 operations on an image give).
-__device__ __forceinline__ float cc_apply(const float* e, int k, const float x[3]) {
-  return __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(e[4 * k], x[0]), __fmul_rn(e[4 * k + 1], x[1])), __fmul_rn(e[4 * k + 2], x[2])),
-                   e[4 * k + 3]);
-}
-
-// View metrics for held-out evaluation (gr_eval_view): k_ssim_fwd<3, false> of a view's render against its target with
-// the rendered image staged from the saved sums as k_ssim_fwd_saved does (same grid, the same partial sums of m bit for
-// bit, no maps), and from the same two staged windows, without a second global read, the tile's sums of |x - y| and
-// (x - y)^2 over its in-image values (three values per thread, then the fixed tree of the SSIM sum).  Three float
-// partials per tile: partial[q * plane + tile], q = 0 the SSIM sum, 1 the absolute, 2 the squared differences.
-// LDS as the forward's (the second tree runs in hs, free by then): three workgroups per CU.
+// gr_eval_view (CC = false) and gr_eval_view_cc (CC = true: of the colour-corrected render E (x, 1), E unused otherwise):
+// k_ssim_fwd<3, false> of the staged render against the target (k_ssim_fwd_saved's grid and partial sums of m bit for bit
+// where CC = false, no maps) and the sums of |x - y| and (x - y)^2.  Three planes: q = 0 the SSIM sum, 1 the absolute, 2
+// the squared differences; k_eval_final gives the three metrics.
+template <bool CC>
 __global__ __launch_bounds__(256) void k_eval_view(ViewK v, const float4* __restrict__ saved4, const float* __restrict__ y,
-                                                   float* __restrict__ partial, int plane) {
+                                                   const float* __restrict__ E, float* __restrict__ partial, int plane) {
   constexpr int C = 3, TC = ST * C, SP = SE * C;
   __shared__ float tx[SE * SP], ty[SE * SP];
   __shared__ float hs[5][SE * TC];
   __shared__ float red[256];
-  const int H = v.H, W = v.W, WC = W * C;
   const int t = threadIdx.x;
-  const int y0 = blockIdx.y * ST, x0 = blockIdx.x * ST, v0 = blockIdx.x * TC;
-  for (int e = t; e < SE * SE; e += 256) {
-    const int r = e / SE, c = e - r * SE;
-    const int gy = y0 - SR + r, gx = x0 - SR + c;
-    float px[3] = {0.0f, 0.0f, 0.0f};
-    if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
-      const float4 s = saved4[(int64_t)gy * W + gx];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) px[k] = saved_colour(v, s, k);
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) tx[r * SP + c * C + k] = px[k];
-  }
-  ssim_stage<C>(y, H, WC, y0, v0, ty);
+  if constexpr (CC)
+    stage_saved(v, saved4, tx, StageCorrected(E));
+  else
+    stage_saved(v, saved4, tx, StageRender());
+  ssim_stage<C>(y, v.H, v.W * C, blockIdx.y * ST, blockIdx.x * TC, ty);
   __syncthreads();
-  float a1 = 0.0f, a2 = 0.0f;
-  for (int o = t; o < ST * TC; o += 256) {
-    const int r = o / TC, c = o - r * TC;
-    if (y0 + r < H && v0 + c < WC) {
-      const int at = (r + SR) * SP + SR * C + c;
-      const float d = tx[at] - ty[at];
-      a1 += fabsf(d);
-      a2 = fmaf(d, d, a2);
-    }
-  }
-  ssim_fwd_tile<C, false, 1>(tx, ty, hs, red, H, W, partial, nullptr);
-  // behind ssim_fwd_tile's last barrier nothing reads hs any more, and red[0] only thread 0 (which rewrites it itself)
-  float* red2 = &hs[0][0];
-  red[t] = a1;
-  red2[t] = a2;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (t < w) {
-      red[t] += red[t + w];
-      red2[t] += red2[t + w];
-    }
-    __syncthreads();
-  }
-  if (t == 0) {
-    const int tile = blockIdx.y * gridDim.x + blockIdx.x;
-    partial[plane + tile] = red[0];
-    partial[2 * plane + tile] = red2[0];
-  }
-}
-
-// gr_eval_view_cc: k_eval_view of the colour-corrected render.  The staged render is E (x, 1) (cc_apply, E = 12 device
-// floats read once per workgroup; not clamped) inside the image and, as for any image, zero outside it; everything
-// behind the staging, the grid, the LDS and the partial sums are k_eval_view's, and k_eval_final then gives the three
-// corrected metrics.  A kernel of its own rather than k_eval_view's body as a template over "apply E": moving that body
-// into a function (forced inline or not, the view by reference or by value) made k_eval_view itself compile to other
-// instructions (its background select; 37 -> 44 SGPRs), which a held-out metric that tests pin bit for bit is not worth.
-__global__ __launch_bounds__(256) void k_eval_view_cc(ViewK v, const float4* __restrict__ saved4, const float* __restrict__ y,
-                                                      const float* __restrict__ E, float* __restrict__ partial, int plane) {
-  constexpr int C = 3, TC = ST * C, SP = SE * C;
-  __shared__ float tx[SE * SP], ty[SE * SP];
-  __shared__ float hs[5][SE * TC];
-  __shared__ float red[256];
-  const int H = v.H, W = v.W, WC = W * C;
-  const int t = threadIdx.x;
-  const int y0 = blockIdx.y * ST, x0 = blockIdx.x * ST, v0 = blockIdx.x * TC;
-  float em[GR_CC_TRANSFORM];
-#pragma unroll
-  for (int i = 0; i < GR_CC_TRANSFORM; ++i) em[i] = E[i];
-  for (int e = t; e < SE * SE; e += 256) {
-    const int r = e / SE, c = e - r * SE;
-    const int gy = y0 - SR + r, gx = x0 - SR + c;
-    float px[3] = {0.0f, 0.0f, 0.0f};
-    if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
-      const float4 s = saved4[(int64_t)gy * W + gx];
-      float x[3];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) x[k] = saved_colour(v, s, k);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) px[k] = cc_apply(em, k, x);
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) tx[r * SP + c * C + k] = px[k];
-  }
-  ssim_stage<C>(y, H, WC, y0, v0, ty);
-  __syncthreads();
-  float a1 = 0.0f, a2 = 0.0f;
-  for (int o = t; o < ST * TC; o += 256) {
-    const int r = o / TC, c = o - r * TC;
-    if (y0 + r < H && v0 + c < WC) {
-      const int at = (r + SR) * SP + SR * C + c;
-      const float d = tx[at] - ty[at];
-      a1 += fabsf(d);
-      a2 = fmaf(d, d, a2);
-    }
-  }
-  ssim_fwd_tile<C, false, 2>(tx, ty, hs, red, H, W, partial, nullptr);
-  float* red2 = &hs[0][0];  // (as k_eval_view: hs is free behind ssim_fwd_tile's last barrier)
-  red[t] = a1;
-  red2[t] = a2;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (t < w) {
-      red[t] += red[t + w];
-      red2[t] += red2[t + w];
-    }
-    __syncthreads();
-  }
-  if (t == 0) {
-    const int tile = blockIdx.y * gridDim.x + blockIdx.x;
-    partial[plane + tile] = red[0];
-    partial[2 * plane + tile] = red2[0];
-  }
+  float a1, a2;
+  diff_sums(tx, ty, v.H, v.W * C, NoWeight(), a1, a2);
+  ssim_fwd_tile<C, false>(tx, ty, hs, red, v.H, v.W, partial, nullptr, NoWeight());
+  float* rd = &hs[0][0];
+  rd[t] = a1;
+  rd[256 + t] = a2;
+  tile_tree<2>(rd);
+  if (t < 2) partial[(size_t)(t + 1) * plane + blockIdx.y * gridDim.x + blockIdx.x] = rd[256 * t];
 }
 
 // The colour-correction moments of a view (gr_cc_fit_view): with u = (x0, x1, x2, 1), x the rendered colour from the saved
@@ -4956,30 +4971,15 @@ __global__ __launch_bounds__(256) void k_cc_moments(ViewK v, const float4* __res
   }
 }
 
-// The transform from the tiles' moments (gr_cc_fit_view), one block: each of the 22 planes summed over the tiles in
-// k_ssim_final's order (stride 256, then the 256-lane tree, in double), then one thread solves, per output channel k,
+// The transform from the tiles' moments (gr_cc_fit_view), one block: each of the 22 planes summed over the tiles
+// (plane_sums), then one thread solves, per output channel k,
 //   (A / HW + ridge I) E_k^T = B[:, k] / HW + ridge e_k      (e_k row k of [I | 0])
 // by a Cholesky factorisation in double (positive definite for ridge > 0) and writes the 12 floats, rounded once.
 __global__ __launch_bounds__(256) void k_cc_solve(const double* __restrict__ part, int tiles, double hw, double ridge,
                                                   float* __restrict__ E) {
   __shared__ double r[GR_CC_MOMENTS][256];
-  const int t = threadIdx.x;
-  double s[GR_CC_MOMENTS];
-#pragma unroll
-  for (int q = 0; q < GR_CC_MOMENTS; ++q) s[q] = 0.0;
-  for (int i = t; i < tiles; i += 256)
-#pragma unroll
-    for (int q = 0; q < GR_CC_MOMENTS; ++q) s[q] += part[(size_t)q * tiles + i];
-#pragma unroll
-  for (int q = 0; q < GR_CC_MOMENTS; ++q) r[q][t] = s[q];
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (t < w)
-#pragma unroll
-      for (int q = 0; q < GR_CC_MOMENTS; ++q) r[q][t] += r[q][t + w];
-    __syncthreads();
-  }
-  if (t != 0) return;
+  plane_sums<GR_CC_MOMENTS>(part, tiles, tiles, r);
+  if (threadIdx.x != 0) return;
   double M[4][4], L[4][4], b[4][3];
   int q = 0;
 #pragma unroll
@@ -5029,28 +5029,13 @@ __global__ __launch_bounds__(256) void k_cc_solve(const double* __restrict__ par
   }
 }
 
-// The three means of gr_eval_view from k_eval_view's partials, each column summed in double in k_ssim_final's order;
-// the SSIM metric is 1 - gr_ssim_fwd's dssim, formed as a caller holding that float would form it.
+// The three means of gr_eval_view from k_eval_view's planes; the SSIM metric is 1 - gr_ssim_fwd's dssim, formed as a
+// caller holding that float would form it.
 __global__ __launch_bounds__(256) void k_eval_final(const float* __restrict__ partial, int plane, int blocks, int64_t n,
                                                     float* __restrict__ metrics) {
   __shared__ double r[3][256];
-  const int t = threadIdx.x;
-  double s0 = 0.0, s1 = 0.0, s2 = 0.0;  // (the three columns' loads of a tile in flight together)
-  for (int i = t; i < blocks; i += 256) {
-    s0 += (double)partial[i];
-    s1 += (double)partial[plane + i];
-    s2 += (double)partial[2 * plane + i];
-  }
-  r[0][t] = s0;
-  r[1][t] = s1;
-  r[2][t] = s2;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (t < w)
-      for (int q = 0; q < 3; ++q) r[q][t] += r[q][t + w];
-    __syncthreads();
-  }
-  if (t == 0) {
+  plane_sums<3>(partial, plane, blocks, r);
+  if (threadIdx.x == 0) {
     const float dssim = (float)(1.0 - r[0][0] / (double)n);
     metrics[0] = (float)(r[1][0] / (double)n);
     metrics[1] = (float)(r[2][0] / (double)n);
@@ -5058,81 +5043,12 @@ __global__ __launch_bounds__(256) void k_eval_final(const float* __restrict__ pa
   }
 }
 
-// The alpha of a pixel from its saved sums s = (W, ...), exactly as write_pixel wrote it.
-__device__ __forceinline__ float saved_alpha(float4 s) {
-  const float den = 1.0f + s.x;
-  return clamp01(s.x / den);
-}
-
-// ssim_fwd_tile<3, false> with every value's m weighted by its pixel's mask value (tm: the tile's own 16 x 16 mask values,
-// no halo: the windows are not masked): the same separable sums, the same thread-strided accumulation (acc = fma(w, m, acc):
-// acc + m bit for bit where w = 1) and the same tree, into partial[tile].  A function of its own, not a form of
-// ssim_fwd_tile: the existing kernels' instructions stay what they are whatever happens here.
-__device__ __forceinline__ void ssim_fwd_tile_masked(const float* tx, const float* ty, const float* tm, float (*hs)[SE * ST * 3],
-                                                     float* red, int H, int W, float* __restrict__ partial) {
-  constexpr int C = 3, TC = ST * C, SP = SE * C;
-  const int t = threadIdx.x;
-  const int WC = W * C;
-  const int y0 = blockIdx.y * ST, v0 = blockIdx.x * TC;
-  for (int o = t; o < SE * TC; o += 256) {
-    const int r = o / TC, c = o - r * TC;
-    const float* px = tx + r * SP + c;
-    const float* py = ty + r * SP + c;
-    float a = 0.0f, b = 0.0f, aa = 0.0f, bb = 0.0f, ab = 0.0f;
-#pragma unroll
-    for (int k = 0; k <= 2 * SR; ++k) {
-      const float g = SSIM_G[k], u = px[k * C], v = py[k * C];
-      a = fmaf(g, u, a);
-      b = fmaf(g, v, b);
-      aa = fmaf(g, u * u, aa);
-      bb = fmaf(g, v * v, bb);
-      ab = fmaf(g, u * v, ab);
-    }
-    hs[0][o] = a;
-    hs[1][o] = b;
-    hs[2][o] = aa;
-    hs[3][o] = bb;
-    hs[4][o] = ab;
-  }
-  __syncthreads();
-  float acc = 0.0f;
-  for (int o = t; o < ST * TC; o += 256) {
-    const int r = o / TC, c = o - r * TC;
-    float mx = 0.0f, my = 0.0f, exx = 0.0f, eyy = 0.0f, exy = 0.0f;
-#pragma unroll
-    for (int k = 0; k <= 2 * SR; ++k) {
-      const float g = SSIM_G[k];
-      mx = fmaf(g, hs[0][o + k * TC], mx);
-      my = fmaf(g, hs[1][o + k * TC], my);
-      exx = fmaf(g, hs[2][o + k * TC], exx);
-      eyy = fmaf(g, hs[3][o + k * TC], eyy);
-      exy = fmaf(g, hs[4][o + k * TC], exy);
-    }
-    if (y0 + r < H && v0 + c < WC) {
-      const float sx = fmaf(-mx, mx, exx), sy = fmaf(-my, my, eyy), sxy = fmaf(-mx, my, exy);
-      const float A1 = fmaf(2.0f * mx, my, SSIM_C1), A2 = fmaf(2.0f, sxy, SSIM_C2);
-      const float B1 = fmaf(mx, mx, fmaf(my, my, SSIM_C1)), B2 = sx + sy + SSIM_C2;
-      const float rr = 1.0f / (B1 * B2);
-      const float m = (A1 * A2) * rr;
-      acc = fmaf(tm[r * ST + c / C], m, acc);
-    }
-  }
-  red[t] = acc;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (t < w) red[t] += red[t + w];
-    __syncthreads();
-  }
-  if (t == 0) partial[blockIdx.y * gridDim.x + blockIdx.x] = red[0];
-}
-
 // Masked view metrics (gr_eval_view_masked): k_eval_view's grid, staging and LDS, plus the tile's own 256 mask values and
-// alphas (saved_alpha of the staged sums; no halo, 2 KiB: three workgroups per CU still).  With m the mask, d = x - y per
-// value and a the alpha, the tile's sums over its in-image pixels, each by k_eval_view's thread-strided accumulation (one
-// pixel, or three values, per thread) and fixed tree: partial[q * plane + tile], q = 0 sum m, 1 sum m |d|, 2 sum m d^2,
-// 3 sum m s (s the SSIM map), 4 sum |a - m|, 5 #{a > 0.5 and m > 0.5}, 6 #{a > 0.5 or m > 0.5} (counts of at most 256:
-// exact in float).  Where m = 1 the weighted terms are k_eval_view's own, bit for bit (fma(1, |d|, a1) = a1 + |d|;
-// (1 d) d = d d).
+// alphas (StageAlpha; no halo, 2 KiB: three workgroups per CU still), and TileMask as the weight hook.  With m the mask,
+// d = x - y per value and a the alpha, the tile's sums over its in-image pixels (one pixel, or three values, per thread):
+// partial[q * plane + tile], q = 0 sum m, 1 sum m |d|, 2 sum m d^2, 3 sum m s (s the SSIM map), 4 sum |a - m|,
+// 5 #{a > 0.5 and m > 0.5}, 6 #{a > 0.5 or m > 0.5} (counts of at most 256: exact in float).  Where m = 1 planes 1..3 are
+// k_eval_view's own, bit for bit (TileMask).
 __global__ __launch_bounds__(256) void k_eval_view_masked(ViewK v, const float4* __restrict__ saved4,
                                                           const float* __restrict__ y, const float* __restrict__ mask,
                                                           float* __restrict__ partial, int plane) {
@@ -5141,39 +5057,16 @@ __global__ __launch_bounds__(256) void k_eval_view_masked(ViewK v, const float4*
   __shared__ float hs[5][SE * TC];
   __shared__ float red[256];
   __shared__ float tm[ST * ST], ta[ST * ST];
-  const int H = v.H, W = v.W, WC = W * C;
   const int t = threadIdx.x;
-  const int y0 = blockIdx.y * ST, x0 = blockIdx.x * ST, v0 = blockIdx.x * TC;
-  const int ty0 = y0 + t / ST, tx0 = x0 + (t & (ST - 1));  // this thread's pixel of the tile
-  const bool pin = ty0 < H && tx0 < W;
-  tm[t] = pin ? mask[(int64_t)ty0 * W + tx0] : 0.0f;
-  for (int e = t; e < SE * SE; e += 256) {
-    const int r = e / SE, c = e - r * SE;
-    const int gy = y0 - SR + r, gx = x0 - SR + c;
-    float px[3] = {0.0f, 0.0f, 0.0f};
-    float al = 0.0f;
-    if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
-      const float4 s = saved4[(int64_t)gy * W + gx];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) px[k] = saved_colour(v, s, k);
-      al = saved_alpha(s);
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) tx[r * SP + c * C + k] = px[k];
-    if (r >= SR && r < SR + ST && c >= SR && c < SR + ST) ta[(r - SR) * ST + (c - SR)] = al;  // (each tile pixel once)
-  }
-  ssim_stage<C>(y, H, WC, y0, v0, ty);
+  const int ty0 = blockIdx.y * ST + t / ST, tx0 = blockIdx.x * ST + (t & (ST - 1));  // this thread's pixel of the tile
+  const bool pin = ty0 < v.H && tx0 < v.W;
+  tm[t] = pin ? mask[(int64_t)ty0 * v.W + tx0] : 0.0f;
+  stage_saved(v, saved4, tx, StageAlpha{ta});
+  ssim_stage<C>(y, v.H, v.W * C, blockIdx.y * ST, blockIdx.x * TC, ty);
   __syncthreads();
-  float a1 = 0.0f, a2 = 0.0f;
-  for (int o = t; o < ST * TC; o += 256) {
-    const int r = o / TC, c = o - r * TC;
-    if (y0 + r < H && v0 + c < WC) {
-      const int at = (r + SR) * SP + SR * C + c;
-      const float d = tx[at] - ty[at], m = tm[r * ST + c / C];
-      a1 = fmaf(m, fabsf(d), a1);
-      a2 = fmaf(m * d, d, a2);
-    }
-  }
+  const TileMask wt{tm};
+  float a1, a2;
+  diff_sums(tx, ty, v.H, v.W * C, wt, a1, a2);
   float sm = 0.0f, sa = 0.0f, ni = 0.0f, nu = 0.0f;
   if (pin) {
     const float m = tm[t], a = ta[t];
@@ -5183,8 +5076,7 @@ __global__ __launch_bounds__(256) void k_eval_view_masked(ViewK v, const float4*
     ni = (fa && fm) ? 1.0f : 0.0f;
     nu = (fa || fm) ? 1.0f : 0.0f;
   }
-  ssim_fwd_tile_masked(tx, ty, tm, hs, red, H, W, partial + 3 * (size_t)plane);
-  // behind the tile function's last barrier nothing reads hs any more (as k_eval_view): the six other trees run there
+  ssim_fwd_tile<C, false>(tx, ty, hs, red, v.H, v.W, partial + 3 * (size_t)plane, nullptr, wt);
   float* rd = &hs[0][0];
   rd[t] = sm;
   rd[256 + t] = a1;
@@ -5192,44 +5084,19 @@ __global__ __launch_bounds__(256) void k_eval_view_masked(ViewK v, const float4*
   rd[768 + t] = sa;
   rd[1024 + t] = ni;
   rd[1280 + t] = nu;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (t < w)
-#pragma unroll
-      for (int q = 0; q < 6; ++q) rd[256 * q + t] += rd[256 * q + t + w];
-    __syncthreads();
-  }
-  if (t < 6) {  // (plane 3 is the tile function's)
-    const int tile = blockIdx.y * gridDim.x + blockIdx.x;
-    partial[(size_t)(t < 3 ? t : t + 1) * plane + tile] = rd[256 * t];
-  }
+  tile_tree<6>(rd);
+  if (t < 6)  // (plane 3 is the tile function's)
+    partial[(size_t)(t < 3 ? t : t + 1) * plane + blockIdx.y * gridDim.x + blockIdx.x] = rd[256 * t];
 }
 
-// The six masked metrics (include/gr_hip.h) from k_eval_view_masked's seven planes, one block: each plane summed over the
-// tiles in double in k_eval_final's order.  The masked SSIM is formed as k_eval_final forms the plain one (1 - the float
-// dssim), so that a mask of ones gives gr_eval_view's three metrics bit for bit; an empty mask (M = 0) gives 0 in rows
-// 1..3, an empty union an IoU of 1.
+// The six masked metrics (include/gr_hip.h) from k_eval_view_masked's seven planes.  The masked SSIM is formed as
+// k_eval_final forms the plain one (1 - the float dssim), so that a mask of ones gives gr_eval_view's three metrics bit
+// for bit; an empty mask (M = 0) gives 0 in rows 1..3, an empty union an IoU of 1.
 __global__ __launch_bounds__(256) void k_eval_masked_final(const float* __restrict__ partial, int plane, int blocks, double hw,
                                                            float* __restrict__ metrics) {
-  constexpr int Q = 7;
-  __shared__ double r[Q][256];
-  const int t = threadIdx.x;
-  double s[Q];
-#pragma unroll
-  for (int q = 0; q < Q; ++q) s[q] = 0.0;
-  for (int i = t; i < blocks; i += 256)
-#pragma unroll
-    for (int q = 0; q < Q; ++q) s[q] += (double)partial[(size_t)q * plane + i];
-#pragma unroll
-  for (int q = 0; q < Q; ++q) r[q][t] = s[q];
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (t < w)
-#pragma unroll
-      for (int q = 0; q < Q; ++q) r[q][t] += r[q][t + w];
-    __syncthreads();
-  }
-  if (t == 0) {
+  __shared__ double r[7][256];
+  plane_sums<7>(partial, plane, blocks, r);
+  if (threadIdx.x == 0) {
     const double M = r[0][0], n = 3.0 * M;
     const bool any = M > 0.0;
     metrics[0] = (float)(M / hw);
@@ -7351,8 +7218,8 @@ size_t gr_eval_ws_bytes(const gr_view* v) {
   return GR_EVAL_METRICS * ssim_partial_bytes(v->height, v->width);
 }
 
-// The refusals of gr_eval_view, gr_cc_fit_view and gr_eval_view_cc (`name` in each message; `io`: the call's other
-// pointers all non-null; `need`: its workspace size).
+// The refusals of the view metrics' calls and gr_cc_fit_view (`name` in each message; `io`: the call's other pointers all
+// non-null; `need`: its workspace size).
 static gr_status eval_view_checks(const char* name, const gr_view* v, const float* saved, const float* target_rgb, bool io,
                                   const void* ws, size_t ws_bytes, size_t need) {
   const std::string who = name;
@@ -7368,26 +7235,63 @@ static gr_status eval_view_checks(const char* name, const gr_view* v, const floa
   return GR_OK;
 }
 
-gr_status gr_eval_view(const gr_view* v, const float* saved, const float* target_rgb, float* metrics, void* ws,
-                       size_t ws_bytes, void* stream) {
-  const gr_status st = eval_view_checks("gr_eval_view", v, saved, target_rgb, metrics != nullptr, ws, ws_bytes, gr_eval_ws_bytes(v));
-  if (st != GR_OK) return st;
-  hipStream_t s = (hipStream_t)stream;
-  const ViewK vk = make_viewk(v);
-  const int plane = (int)(ssim_partial_bytes(v->height, v->width) / sizeof(float));
-  hipLaunchKernelGGL(k_eval_view, dim3(vk.tiles_x, vk.tiles_y), dim3(256), 0, s, vk, (const float4*)saved, target_rgb,
-                     (float*)ws, plane);
-  GR_HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_eval_final, dim3(1), dim3(256), 0, s, (const float*)ws, plane, vk.tiles_x * vk.tiles_y,
-                     (int64_t)v->height * v->width * 3, metrics);
-  GR_HIP_TRY(hipGetLastError());
-  return GR_OK;
-}
-
 // Colour correction: GR_CC_MOMENTS planes of per-tile double partial sums (k_cc_moments).
 size_t gr_cc_ws_bytes(const gr_view* v) {
   if (!v || !ssim_shape_ok(v->height, v->width, 3)) return 0;
   return align_up((size_t)GR_CC_MOMENTS * tiles_x_of(v->width, ST) * tiles_y_of(v->height, ST) * sizeof(double));
+}
+
+// Masked metrics: seven planes of per-tile float partial sums (k_eval_view_masked).
+size_t gr_eval_mask_ws_bytes(const gr_view* v) {
+  if (!v || !ssim_shape_ok(v->height, v->width, 3)) return 0;
+  return 7 * ssim_partial_bytes(v->height, v->width);
+}
+
+// gr_eval_view, gr_eval_view_cc and gr_eval_view_masked: the checks, the metric's tile kernel and its final kernel.
+// `extra`: the transform (cc) or the mask (masked).
+enum class EvalMetric { plain, cc, masked };
+static gr_status eval_view_host(const char* name, EvalMetric metric, const gr_view* v, const float* saved,
+                                const float* target_rgb, const float* extra, float* metrics, void* ws, size_t ws_bytes,
+                                void* stream) {
+  const bool masked = metric == EvalMetric::masked;
+  const gr_status st = eval_view_checks(name, v, saved, target_rgb, (metric == EvalMetric::plain || extra) && metrics, ws,
+                                        ws_bytes, masked ? gr_eval_mask_ws_bytes(v) : gr_eval_ws_bytes(v));
+  if (st != GR_OK) return st;
+  hipStream_t s = (hipStream_t)stream;
+  const ViewK vk = make_viewk(v);
+  const dim3 grid(vk.tiles_x, vk.tiles_y);
+  const int plane = (int)(ssim_partial_bytes(v->height, v->width) / sizeof(float)), tiles = vk.tiles_x * vk.tiles_y;
+  if (masked)
+    hipLaunchKernelGGL(k_eval_view_masked, grid, dim3(256), 0, s, vk, (const float4*)saved, target_rgb, extra, (float*)ws, plane);
+  else if (metric == EvalMetric::cc)
+    hipLaunchKernelGGL(k_eval_view<true>, grid, dim3(256), 0, s, vk, (const float4*)saved, target_rgb, extra, (float*)ws, plane);
+  else
+    hipLaunchKernelGGL(k_eval_view<false>, grid, dim3(256), 0, s, vk, (const float4*)saved, target_rgb, extra, (float*)ws, plane);
+  GR_HIP_TRY(hipGetLastError());
+  if (masked)
+    hipLaunchKernelGGL(k_eval_masked_final, dim3(1), dim3(256), 0, s, (const float*)ws, plane, tiles,
+                       (double)v->height * (double)v->width, metrics);
+  else
+    hipLaunchKernelGGL(k_eval_final, dim3(1), dim3(256), 0, s, (const float*)ws, plane, tiles,
+                       (int64_t)v->height * v->width * 3, metrics);
+  GR_HIP_TRY(hipGetLastError());
+  return GR_OK;
+}
+
+gr_status gr_eval_view(const gr_view* v, const float* saved, const float* target_rgb, float* metrics, void* ws,
+                       size_t ws_bytes, void* stream) {
+  return eval_view_host("gr_eval_view", EvalMetric::plain, v, saved, target_rgb, nullptr, metrics, ws, ws_bytes, stream);
+}
+
+gr_status gr_eval_view_cc(const gr_view* v, const float* saved, const float* target_rgb, const float* transform,
+                          float* metrics, void* ws, size_t ws_bytes, void* stream) {
+  return eval_view_host("gr_eval_view_cc", EvalMetric::cc, v, saved, target_rgb, transform, metrics, ws, ws_bytes, stream);
+}
+
+gr_status gr_eval_view_masked(const gr_view* v, const float* saved, const float* target_rgb, const float* target_mask,
+                              float* metrics, void* ws, size_t ws_bytes, void* stream) {
+  return eval_view_host("gr_eval_view_masked", EvalMetric::masked, v, saved, target_rgb, target_mask, metrics, ws, ws_bytes,
+                        stream);
 }
 
 gr_status gr_cc_fit_view(const gr_view* v, const float* saved, const float* target_rgb, float ridge, float* transform,
@@ -7403,45 +7307,6 @@ gr_status gr_cc_fit_view(const gr_view* v, const float* saved, const float* targ
   GR_HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(k_cc_solve, dim3(1), dim3(256), 0, s, (const double*)ws, vk.tiles_x * vk.tiles_y,
                      (double)v->height * (double)v->width, (double)ridge, transform);
-  GR_HIP_TRY(hipGetLastError());
-  return GR_OK;
-}
-
-gr_status gr_eval_view_cc(const gr_view* v, const float* saved, const float* target_rgb, const float* transform,
-                          float* metrics, void* ws, size_t ws_bytes, void* stream) {
-  const gr_status st = eval_view_checks("gr_eval_view_cc", v, saved, target_rgb, transform && metrics, ws, ws_bytes, gr_eval_ws_bytes(v));
-  if (st != GR_OK) return st;
-  hipStream_t s = (hipStream_t)stream;
-  const ViewK vk = make_viewk(v);
-  const int plane = (int)(ssim_partial_bytes(v->height, v->width) / sizeof(float));
-  hipLaunchKernelGGL(k_eval_view_cc, dim3(vk.tiles_x, vk.tiles_y), dim3(256), 0, s, vk, (const float4*)saved, target_rgb,
-                     transform, (float*)ws, plane);
-  GR_HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_eval_final, dim3(1), dim3(256), 0, s, (const float*)ws, plane, vk.tiles_x * vk.tiles_y,
-                     (int64_t)v->height * v->width * 3, metrics);
-  GR_HIP_TRY(hipGetLastError());
-  return GR_OK;
-}
-
-// Masked metrics: seven planes of per-tile float partial sums (k_eval_view_masked).
-size_t gr_eval_mask_ws_bytes(const gr_view* v) {
-  if (!v || !ssim_shape_ok(v->height, v->width, 3)) return 0;
-  return 7 * ssim_partial_bytes(v->height, v->width);
-}
-
-gr_status gr_eval_view_masked(const gr_view* v, const float* saved, const float* target_rgb, const float* target_mask,
-                              float* metrics, void* ws, size_t ws_bytes, void* stream) {
-  const gr_status st = eval_view_checks("gr_eval_view_masked", v, saved, target_rgb, target_mask && metrics, ws, ws_bytes,
-                                        gr_eval_mask_ws_bytes(v));
-  if (st != GR_OK) return st;
-  hipStream_t s = (hipStream_t)stream;
-  const ViewK vk = make_viewk(v);
-  const int plane = (int)(ssim_partial_bytes(v->height, v->width) / sizeof(float));
-  hipLaunchKernelGGL(k_eval_view_masked, dim3(vk.tiles_x, vk.tiles_y), dim3(256), 0, s, vk, (const float4*)saved, target_rgb,
-                     target_mask, (float*)ws, plane);
-  GR_HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_eval_masked_final, dim3(1), dim3(256), 0, s, (const float*)ws, plane, vk.tiles_x * vk.tiles_y,
-                     (double)v->height * (double)v->width, metrics);
   GR_HIP_TRY(hipGetLastError());
   return GR_OK;
 }

@@ -213,7 +213,7 @@ CC_RIDGE = 1e-6  # GR_CC_RIDGE (include/gr_hip.h)
 def apply_color_transform(img: torch.Tensor, E: torch.Tensor) -> torch.Tensor:
     """The colour-corrected image of include/gr_hip.h: ``y_k = ((E[k][0] x0 + E[k][1] x1) + E[k][2] x2) + E[k][3]`` of an
     (..., 3) image and a 3 x 4 transform (or its 12 values row-major), element-wise in float32, every product and sum
-    rounded on its own in that order (the bits k_eval_view_cc stages); not clamped.  Any device."""
+    rounded on its own in that order (the bits k_eval_view<true> stages); not clamped.  Any device."""
     x = img.float()
     if x.shape[-1] != 3 or E.numel() != 12:
         raise ValueError(f"apply_color_transform: an (..., 3) image and a 3 x 4 transform, got {tuple(img.shape)}, {tuple(E.shape)}")

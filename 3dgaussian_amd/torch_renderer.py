@@ -884,18 +884,33 @@ def camera_grads_sums_native(means, scales, colors, opacities, batch, rows, ws=N
                                          _stream(dev)), "gr_camera_grads_sums")
 
 
+def _saved_view_call(entry: str, ws_entry: str, st: RenderState, target, *operands) -> None:
+    """``entry`` of the C ABI on the current stream, on the state's view and saved sums with a fresh ``ws_entry``
+    workspace: ``target`` (H, W, 3), then the call's own arguments in its order, each a checked ``(tensor, shape, name)``
+    (with a fourth entry, what was expected, None is refused here with it) or a ctypes value.  The view-metric wrappers
+    below."""
+    L = _native.lib()
+    dev = st.saved.device
+    _check_operand(target, (st.gv.height, st.gv.width, 3), "target", dev)
+    args = []
+    for op in operands:
+        if isinstance(op, tuple):
+            if op[0] is None and len(op) > 3:
+                raise ValueError(f"{op[2]}: expected {op[3]}, got None")
+            _check_operand(*op[:3], dev)
+            op = _native.ptr(op[0])
+        args.append(op)
+    ws = torch.empty((int(getattr(L, ws_entry)(ctypes.byref(st.gv))),), dtype=torch.uint8, device=dev)
+    _native.check(getattr(L, entry)(ctypes.byref(st.gv), _native.ptr(st.saved), _native.ptr(target), *args, _native.ptr(ws),
+                                    ws.numel(), _stream(dev)), entry)
+
+
 def eval_view_native(st: RenderState, target, metrics_out) -> None:
     """gr_eval_view on the current stream: ``metrics_out`` (``_native.EVAL_METRICS`` float32 on the device) receives
     mean|out - target|, mean (out - target)^2 and the mean SSIM of the view's render against ``target`` (H, W, 3), the
     rendered colours formed from the state's saved sums (no image read or written; a ``forward_native`` state with
     or without images, 16-pixel tiles, a whole view)."""
-    L = _native.lib()
-    dev = st.saved.device
-    _check_operand(target, (st.gv.height, st.gv.width, 3), "target", dev)
-    _check_operand(metrics_out, (_native.EVAL_METRICS,), "metrics_out", dev)
-    ws = torch.empty((int(L.gr_eval_ws_bytes(ctypes.byref(st.gv))),), dtype=torch.uint8, device=dev)
-    _native.check(L.gr_eval_view(ctypes.byref(st.gv), _native.ptr(st.saved), _native.ptr(target), _native.ptr(metrics_out),
-                                 _native.ptr(ws), ws.numel(), _stream(dev)), "gr_eval_view")
+    _saved_view_call("gr_eval_view", "gr_eval_ws_bytes", st, target, (metrics_out, (_native.EVAL_METRICS,), "metrics_out"))
 
 
 def cc_fit_view_native(st: RenderState, target, transform_out, ridge: float = _native.CC_RIDGE) -> None:
@@ -903,27 +918,16 @@ def cc_fit_view_native(st: RenderState, target, transform_out, ridge: float = _n
     the affine colour transform E (3 x 4 row-major, row k the output channel) that best maps the view's render, formed
     from the state's saved sums, onto ``target`` (H, W, 3): moments in double in a fixed order, a ridge towards [I | 0]
     (include/gr_hip.h).  Deterministic."""
-    L = _native.lib()
-    dev = st.saved.device
-    _check_operand(target, (st.gv.height, st.gv.width, 3), "target", dev)
-    _check_operand(transform_out, (_native.CC_TRANSFORM,), "transform_out", dev)
-    ws = torch.empty((int(L.gr_cc_ws_bytes(ctypes.byref(st.gv))),), dtype=torch.uint8, device=dev)
-    _native.check(L.gr_cc_fit_view(ctypes.byref(st.gv), _native.ptr(st.saved), _native.ptr(target), ctypes.c_float(ridge),
-                                   _native.ptr(transform_out), _native.ptr(ws), ws.numel(), _stream(dev)), "gr_cc_fit_view")
+    _saved_view_call("gr_cc_fit_view", "gr_cc_ws_bytes", st, target, ctypes.c_float(ridge),
+                     (transform_out, (_native.CC_TRANSFORM,), "transform_out"))
 
 
 def eval_view_cc_native(st: RenderState, target, transform, metrics_out) -> None:
     """gr_eval_view_cc on the current stream: eval_view_native's three metrics of the colour-corrected render
     E (out, 1) against ``target``, ``transform`` being E (``_native.CC_TRANSFORM`` float32 on the device, as
     cc_fit_view_native writes it), applied while the render is staged from the saved sums."""
-    L = _native.lib()
-    dev = st.saved.device
-    _check_operand(target, (st.gv.height, st.gv.width, 3), "target", dev)
-    _check_operand(transform, (_native.CC_TRANSFORM,), "transform", dev)
-    _check_operand(metrics_out, (_native.EVAL_METRICS,), "metrics_out", dev)
-    ws = torch.empty((int(L.gr_eval_ws_bytes(ctypes.byref(st.gv))),), dtype=torch.uint8, device=dev)
-    _native.check(L.gr_eval_view_cc(ctypes.byref(st.gv), _native.ptr(st.saved), _native.ptr(target), _native.ptr(transform),
-                                    _native.ptr(metrics_out), _native.ptr(ws), ws.numel(), _stream(dev)), "gr_eval_view_cc")
+    _saved_view_call("gr_eval_view_cc", "gr_eval_ws_bytes", st, target, (transform, (_native.CC_TRANSFORM,), "transform"),
+                     (metrics_out, (_native.EVAL_METRICS,), "metrics_out"))
 
 
 def eval_view_masked_native(st: RenderState, target, mask, metrics_out) -> None:
@@ -932,17 +936,9 @@ def eval_view_masked_native(st: RenderState, target, mask, metrics_out) -> None:
     0 for an empty mask), sil_l1 (mean |alpha - mask|) and sil_iou (alpha and mask thresholded at 0.5) of the view's
     render and alpha, formed from the state's saved sums, against ``target`` (H, W, 3) (include/gr_hip.h).  A mask of
     ones gives eval_view_native's three metrics bit for bit.  Deterministic."""
-    L = _native.lib()
-    dev = st.saved.device
-    _check_operand(target, (st.gv.height, st.gv.width, 3), "target", dev)
-    if mask is None:
-        raise ValueError("mask: expected an (H, W) float32 tensor, got None")
-    _check_operand(mask, (st.gv.height, st.gv.width), "mask", dev)
-    _check_operand(metrics_out, (_native.EVAL_MASK_METRICS,), "metrics_out", dev)
-    ws = torch.empty((int(L.gr_eval_mask_ws_bytes(ctypes.byref(st.gv))),), dtype=torch.uint8, device=dev)
-    _native.check(L.gr_eval_view_masked(ctypes.byref(st.gv), _native.ptr(st.saved), _native.ptr(target), _native.ptr(mask),
-                                        _native.ptr(metrics_out), _native.ptr(ws), ws.numel(), _stream(dev)),
-                  "gr_eval_view_masked")
+    _saved_view_call("gr_eval_view_masked", "gr_eval_mask_ws_bytes", st, target,
+                     (mask, (st.gv.height, st.gv.width), "mask", "an (H, W) float32 tensor"),
+                     (metrics_out, (_native.EVAL_MASK_METRICS,), "metrics_out"))
 
 
 def contrib_view_native(rs: RenderState, pv: Prepared, peak) -> None:

@@ -1,5 +1,5 @@
 """GPU: colour-corrected held-out metrics.  Kernel level: gr_cc_fit_view (k_cc_moments + k_cc_solve) and gr_eval_view_cc
-(k_eval_view_cc + k_eval_final) on a forward_native state, against the float64 numpy restatement (tests/cc_reference.py)
+(k_eval_view<true> + k_eval_final) on a forward_native state, against the float64 numpy restatement (tests/cc_reference.py)
 run on the image the existing forward composes from the same state.
   transform   within 1e-5 of the reference: a hundred times the float32 rounding of an entry near 1, four orders above
               the 1e-9 by which the order of a float64 moment sum moves an entry (include/gr_hip.h)
@@ -112,6 +112,27 @@ def test_kernels_match_the_reference(mods, cuda, W, H, n):
     S = _state(mods, cuda, W, H, n)
     assert S["st"].num_pairs > 0 or W * H == 1
     _check(mods, cuda, S, f"{W}x{H}")
+
+
+def test_more_than_256_tiles(mods, cuda):
+    """260x257: 17 x 17 = 289 tiles, partial ones on both edges: the stride-256 sums of k_cc_solve and k_eval_final take a
+    second turn."""
+    S = _state(mods, cuda, 260, 257, 2000)
+    assert S["st"].num_pairs > 0
+    _check(mods, cuda, S, "260x257")
+
+
+@pytest.mark.parametrize("W,H,n", [(50, 37, 1500), (7, 5, 200)], ids=["50x37", "7x5"])
+def test_identity_transform_is_gr_eval_view(mods, cuda, W, H, n):
+    """E = [I | 0]: the rendered colours are clamped to [0, 1], so 1 x0 + 0 x1 + 0 x2 + 0 is exactly x0 and the corrected
+    metrics are gr_eval_view's bit for bit."""
+    S = _state(mods, cuda, W, H, n)
+    want = torch.full((3,), -1.0, device=cuda)
+    mods[0].eval_view_native(S["st"], S["target"], want)
+    got = torch.full((3,), -2.0, device=cuda)
+    mods[0].eval_view_cc_native(S["st"], S["target"], torch.eye(3, 4, device=cuda).reshape(12).contiguous(), got)
+    print(f"identity {W}x{H}: {got.tolist()} against gr_eval_view {want.tolist()}")
+    assert torch.equal(got, want) and bool(torch.isfinite(want).all())
 
 
 @pytest.mark.parametrize("bg_dev", [False, True], ids=["background", "background_dev"])

@@ -93,6 +93,13 @@ def test_kernel_matches_composed_image(mods, cuda, W, H, n):
     _check(mods, cuda, S, f"{W}x{H}")
 
 
+def test_more_than_256_tiles(mods, cuda):
+    """260x257: 17 x 17 = 289 tiles, partial ones on both edges: the final kernel's stride-256 sum takes a second turn."""
+    S = _state(mods, cuda, 260, 257, 2000)
+    assert S["st"].num_pairs > 0
+    _check(mods, cuda, S, "260x257")
+
+
 @pytest.mark.parametrize("bg_dev", [False, True], ids=["background", "background_dev"])
 def test_background(mods, cuda, bg_dev):
     S = _state(mods, cuda, 50, 37, 1500, BG, bg_dev)

@@ -163,6 +163,13 @@ def test_blob_masks_match_float64(mods, cuda, W, H, n, soft):
     _check_ref(mods, cuda, S, mask, f"{W}x{H} {'soft' if soft else 'binary'}")
 
 
+def test_more_than_256_tiles(mods, cuda):
+    """260x257: 17 x 17 = 289 tiles, partial ones on both edges: the final kernel's stride-256 sums take a second turn."""
+    S = _state(mods, cuda, 260, 257, 2000)
+    assert S["st"].num_pairs > 0
+    _check_ref(mods, cuda, S, emr.blob_mask(257, 260, False).to(cuda), "260x257 binary")
+
+
 @pytest.mark.parametrize("W,H,n", CASES, ids=IDS)
 def test_mask_of_zeros(mods, cuda, W, H, n):
     S = _state(mods, cuda, W, H, n)

@@ -102,46 +102,35 @@ def kernel_lines(n, R, calls, sets, dev):
             f"{halo / us / 1e6:.2f} TB/s requested (the re-reads are served by the caches)"]
 
 
-def kernel_loop(n, R, calls, dev):
-    (m, s, c, o), st = view_state(n, R, dev)
-    target = torch.rand((R, R, 3), device=dev)
-    out = torch.zeros(3, device=dev)
-    loss = torch.zeros(1, device=dev)
-    ev = lambda: tr.eval_view_native(st, target, out)  # noqa: E731
-    bw = lambda: tr.backward_fit_ssim_gather_native(st, target, None, 0.0, None, 0.0, 1.0, 0.2, loss)  # noqa: E731
-    for i in range(calls):  # E B B E E B ...: each kernel as often behind the other (inputs in cache) as behind a backward
-        for f in ((ev, bw) if i % 2 == 0 else (bw, ev)):
-            f()
-    torch.cuda.synchronize()
-    print(f"kernel loop: {calls} x (gr_eval_view, gr_bwd_fit_ssim_gather) at {R}x{R}, {n} Gaussians")
+# --kernel-loop: the per-view calls of a variant, each f(st, target, mask, row) on one view's state, and their label.
+# plain: gr_eval_view beside the fused D-SSIM backward, alternated; the others: the calls of gr_eval_views_cc /
+# gr_eval_views_masked in order (row: the view's row of that pass, the transform at 6).
+KERNEL_LOOPS = {
+    "plain": ([lambda st, t, m, row: tr.eval_view_native(st, t, row[:3]),
+               lambda st, t, m, row: tr.backward_fit_ssim_gather_native(st, t, None, 0.0, None, 0.0, 1.0, 0.2, row[3:4])],
+              "gr_eval_view, gr_bwd_fit_ssim_gather", True),
+    "cc": ([lambda st, t, m, row: tr.eval_view_native(st, t, row[:3]),
+            lambda st, t, m, row: tr.cc_fit_view_native(st, t, row[6:]),
+            lambda st, t, m, row: tr.eval_view_cc_native(st, t, row[6:], row[3:6])],
+           "gr_eval_view, gr_cc_fit_view, gr_eval_view_cc", False),
+    "masked": ([lambda st, t, m, row: tr.eval_view_native(st, t, row[:3]),
+                lambda st, t, m, row: tr.eval_view_masked_native(st, t, m, row[3:9])],
+               "gr_eval_view, gr_eval_view_masked", False),
+}
 
 
-def cc_kernel_loop(n, R, calls, dev):
-    """--color_correct --kernel-loop: the three per-view calls of gr_eval_views_cc, for a kernel trace (k_cc_moments,
-    k_cc_solve and k_eval_view_cc beside k_eval_view)."""
-    _, st = view_state(n, R, dev)
-    target = torch.rand((R, R, 3), device=dev)
-    row = torch.zeros(18, device=dev)
-    for _ in range(calls):
-        tr.eval_view_native(st, target, row[:3])
-        tr.cc_fit_view_native(st, target, row[6:])
-        tr.eval_view_cc_native(st, target, row[6:], row[3:6])
-    torch.cuda.synchronize()
-    print(f"kernel loop: {calls} x (gr_eval_view, gr_cc_fit_view, gr_eval_view_cc) at {R}x{R}, {n} Gaussians")
-
-
-def masked_kernel_loop(n, R, calls, dev):
-    """--masked --kernel-loop: the two per-view calls of gr_eval_views_masked, for a kernel trace (k_eval_view_masked and
-    k_eval_masked_final beside k_eval_view and k_eval_final)."""
+def kernel_loop(n, R, calls, dev, per_view, label, alternate):
+    """--kernel-loop: `calls` rounds of one view's per-view calls, for a kernel trace.  alternate: every other round in
+    reverse (E B B E E B ...: each kernel as often behind the other, its inputs in cache, as behind a backward)."""
     _, st = view_state(n, R, dev)
     target = torch.rand((R, R, 3), device=dev)
     mask = (target.mean(dim=2) > 0.5).float()
-    row = torch.zeros(9, device=dev)
-    for _ in range(calls):
-        tr.eval_view_native(st, target, row[:3])
-        tr.eval_view_masked_native(st, target, mask, row[3:])
+    row = torch.zeros(18, device=dev)
+    for i in range(calls):
+        for f in (per_view[::-1] if alternate and i % 2 else per_view):
+            f(st, target, mask, row)
     torch.cuda.synchronize()
-    print(f"kernel loop: {calls} x (gr_eval_view, gr_eval_view_masked) at {R}x{R}, {n} Gaussians")
+    print(f"kernel loop: {calls} x ({label}) at {R}x{R}, {n} Gaussians")
 
 
 def option_lines(fit, args, R, name, kw, tail):
@@ -206,8 +195,7 @@ def main():
     dev = torch.device("cuda", 0)
     R = args.res
     if args.kernel_loop:
-        loop = cc_kernel_loop if args.color_correct else masked_kernel_loop if args.masked else kernel_loop
-        return loop(args.gaussians, R, 20, dev)
+        return kernel_loop(args.gaussians, R, 20, dev, *KERNEL_LOOPS["cc" if args.color_correct else "masked" if args.masked else "plain"])
     cams = fm.orbit_cameras(args.views, R, R, dev)
     g = torch.Generator(device=dev).manual_seed(3)
     targets = [torch.rand((R, R, 3), generator=g, device=dev) for _ in cams]
