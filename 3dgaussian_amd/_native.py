@@ -149,119 +149,100 @@ _lib = None
 _P = ctypes.c_void_p
 _VP = ctypes.POINTER(GrView)
 _PP = ctypes.POINTER(GrPlan)
+_I, _F, _Z = ctypes.c_int, ctypes.c_float, ctypes.c_size_t
+_PA = ctypes.POINTER(ctypes.c_void_p)  # an array of pointers
+# The operand groups of the view entries, in the order of the header's declarations (include/gr_hip.h): a row below
+# reads like its declaration.
+_VIEW = [_VP, _I, _PP]           # v, n, plan
+_PARAMS = [_P, _P, _P, _I, _P]   # means, scales, colors, color_dim, opacities
+_GRADS = [_P, _P, _P, _P]        # d_means, d_scales, d_colors, d_opacities
+_STATE = [_P, _P, _P]            # geom, bins, saved
+_UPSTREAM = [_P, _P, _P]         # g_rgb, g_alpha, g_depth
+_L1 = [_P, _P, _F]               # target_rgb, target_mask, w_sil
+_DEPTH = [_P, _F]                # target_depth, w_depth
+_WS = [_P, _Z]                   # ws, ws_bytes
+_SUMS = [_P, _P]                 # sums, sums3
+# an executor entry's head: ex, cfg, num_views, views, n (the parameters follow)
+_EXEC = [_P, ctypes.POINTER(GrFitConfig), _I, ctypes.POINTER(GrFitTarget), _I]
 _SIG = {
-    "gr_geom_bytes": (ctypes.c_size_t, [ctypes.c_int]),
-    "gr_fwd_prepare": (ctypes.c_int, [_VP, ctypes.c_int, _P, _P, _P, ctypes.c_int, _P, _P, ctypes.c_size_t, _PP, _P]),
-    "gr_fwd_prepare_async": (ctypes.c_int, [_VP, ctypes.c_int, _P, _P, _P, ctypes.c_int, _P, _P, ctypes.c_size_t, _P, _P]),
-    "gr_fwd_prepare_views_async": (ctypes.c_int, [ctypes.c_int, _VP, ctypes.c_int, _P, _P, _P, ctypes.c_int, _P,
-                                                  ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t,
-                                                  ctypes.POINTER(ctypes.c_void_p), _P]),
-    "gr_fwd_prepare_views_sized": (ctypes.c_int, [ctypes.c_int, _VP, ctypes.c_int, _P, _P, _P, ctypes.c_int, _P,
-                                                  ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t, _PP,
-                                                  ctypes.POINTER(ctypes.c_void_p), _P, _P]),
-    "gr_fit_views_batched": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(GrBatchView), ctypes.c_int, ctypes.c_float,
-                                            ctypes.c_float, ctypes.c_float, _P]),
-    "gr_bins_bytes": (ctypes.c_size_t, [_VP, ctypes.c_int, _PP]),
-    "gr_saved_floats": (ctypes.c_size_t, [_VP]),
-    "gr_fwd_scratch_bytes": (ctypes.c_size_t, [_VP, ctypes.c_int, _PP]),
-    "gr_fwd_render": (ctypes.c_int, [_VP, ctypes.c_int, _PP, _P, _P, ctypes.c_size_t, _P, ctypes.c_size_t, _P, _P, _P, _P, _P]),
-    "gr_fwd_render_saved": (ctypes.c_int, [_VP, ctypes.c_int, _PP, _P, _P, ctypes.c_size_t, _P, ctypes.c_size_t, _P, _P]),
-    "gr_fwd_compose": (ctypes.c_int, [_VP, _P, _P, _P, _P, _P]),
-    "gr_fwd_bin": (ctypes.c_int, [_VP, ctypes.c_int, _PP, _P, _P, ctypes.c_size_t, _P, ctypes.c_size_t, _P]),
-    "gr_bwd_bytes": (ctypes.c_size_t, [_VP, ctypes.c_int, _PP]),
-    "gr_bwd": (ctypes.c_int, [_VP, ctypes.c_int, _PP, _P, _P, _P, ctypes.c_int, _P, _P, _P, _P, _P, _P, _P,
-                              _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
-    "gr_bwd_indexed": (ctypes.c_int, [_VP, ctypes.c_int, _PP, _P, _P, _P, ctypes.c_int, _P, _P, _P, _P, _P, _P, _P, _P,
-                                      _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
-    "gr_bwd_camera": (ctypes.c_int, [_VP, ctypes.c_int, _PP, _P, _P, _P, ctypes.c_int, _P, _P, ctypes.c_size_t, ctypes.c_int,
-                                     _P, _P]),
-    "gr_bwd_l1": (ctypes.c_int, [_VP, ctypes.c_int, _PP, _P, _P, _P, ctypes.c_int, _P, _P, _P, _P, _P, _P,
-                                 ctypes.c_float, ctypes.c_float, _P, _P, _P, _P, _P, ctypes.c_int, _P, ctypes.c_size_t,
-                                 _P]),
-    "gr_bwd_fit": (ctypes.c_int, [_VP, ctypes.c_int, _PP, _P, _P, _P, ctypes.c_int, _P, _P, _P, _P, _P, _P,
-                                  ctypes.c_float, _P, ctypes.c_float, ctypes.c_float, _P, _P, _P, _P, _P, ctypes.c_int, _P,
-                                  ctypes.c_size_t, _P]),
-    "gr_fit_param_step": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, _P, _P, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int,
-                                         ctypes.c_float, ctypes.c_int, _P,
-                                         _P, ctypes.c_float, ctypes.c_float, ctypes.c_double, ctypes.c_double, ctypes.c_float,
-                                         _P]),
-    "gr_adam_step": (ctypes.c_int, [ctypes.c_int64, _P, _P, _P, _P, ctypes.c_float, ctypes.c_float, ctypes.c_double,
-                                    ctypes.c_double, ctypes.c_float, _P]),
-    "gr_fit_param_steps": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(GrParamStep), ctypes.c_double, ctypes.c_double,
-                                          ctypes.c_float, _P]),
-    "gr_fit_param_steps_sched": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(GrParamStep), ctypes.c_double, ctypes.c_double,
-                                                ctypes.c_float, _P, _P, _P, _P, _P]),
-    "gr_fit_activations_ws_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
-    "gr_fit_activations": (ctypes.c_int, [ctypes.c_int64, _P, _P, _P, ctypes.c_int64, _P, _P, _P, ctypes.c_float,
-                                          ctypes.c_float, _P, _P, ctypes.c_size_t, _P]),
-    "gr_fwd_render_l1": (ctypes.c_int, [_VP, ctypes.c_int, _PP, _P, _P, ctypes.c_size_t, _P, ctypes.c_size_t, _P, _P,
-                                        ctypes.c_float, ctypes.c_float, _P, _P, _P, _P, ctypes.c_size_t, _P]),
-    "gr_bwd_splat": (ctypes.c_int, [_VP, ctypes.c_int, _PP, _P, _P, _P, ctypes.c_size_t, _P]),
-    "gr_reduce_views": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(GrReduceView), ctypes.c_int, _P, _P, _P, ctypes.c_int,
-                                       _P, _P, _P, _P, _P, ctypes.c_int, _P]),
-    "gr_view_sums_floats": (ctypes.c_size_t, [ctypes.c_int]),
-    "gr_gather_view": (ctypes.c_int, [_VP, ctypes.c_int, _PP, _P, _P, _P, _P, _P]),
-    "gr_bwd_fit_gather": (ctypes.c_int, [_VP, ctypes.c_int, _PP, _P, _P, _P, _P, _P, ctypes.c_float, _P, ctypes.c_float,
-                                         ctypes.c_float, _P, _P, ctypes.c_size_t, _P, _P, _P]),
-    "gr_bwd_ssim_bytes": (ctypes.c_size_t, [_VP, ctypes.c_int, _PP]),
-    "gr_bwd_fit_ssim": (ctypes.c_int, [_VP, ctypes.c_int, _PP, _P, _P, _P, ctypes.c_int, _P, _P, _P, _P, _P, _P,
-                                       ctypes.c_float, _P, ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, _P, _P, _P,
-                                       _P, ctypes.c_int, _P, ctypes.c_size_t, _P]),
-    "gr_bwd_fit_ssim_gather": (ctypes.c_int, [_VP, ctypes.c_int, _PP, _P, _P, _P, _P, _P, ctypes.c_float, _P,
-                                              ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, _P, ctypes.c_size_t, _P,
-                                              _P, _P]),
-    "gr_fit_views_ssim": (ctypes.c_int, [_P, ctypes.POINTER(GrFitConfig), ctypes.c_int, ctypes.POINTER(GrFitTarget),
-                                         ctypes.c_int, _P, _P, _P, ctypes.c_int, _P, ctypes.c_float, ctypes.c_float,
-                                         ctypes.c_float, ctypes.c_float, _P, ctypes.POINTER(ctypes.c_void_p), _P]),
-    "gr_reduce_sums": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(GrSumsView), ctypes.c_int, _P, _P, _P, ctypes.c_int,
-                                      _P, _P, _P, _P, _P, ctypes.c_int, _P]),
-    "gr_density_stats": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(GrSumsView), ctypes.c_int, _P, _P, _P,
-                                        ctypes.c_float, _P, _P]),
-    "gr_executor_density_stats": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_void_p)]),
-    "gr_camera_grads_ws_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
-    "gr_camera_grads_sums": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(GrSumsView), ctypes.c_int, _P, _P, _P,
-                                            ctypes.c_int, _P, ctypes.POINTER(ctypes.c_void_p), _P, ctypes.c_size_t, _P]),
-    "gr_executor_camera_grads": (ctypes.c_int, [_P, _P]),
-    "gr_executor_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
+    "gr_geom_bytes": (_Z, [_I]),
+    "gr_fwd_prepare": (_I, [_VP, _I] + _PARAMS + [_P, _Z, _PP, _P]),
+    "gr_fwd_prepare_async": (_I, [_VP, _I] + _PARAMS + [_P, _Z, _P, _P]),
+    "gr_fwd_prepare_views_async": (_I, [_I, _VP, _I] + _PARAMS + [_PA, _Z, _PA, _P]),
+    "gr_fwd_prepare_views_sized": (_I, [_I, _VP, _I] + _PARAMS + [_PA, _Z, _PP, _PA, _P, _P]),
+    "gr_fit_views_batched": (_I, [_I, ctypes.POINTER(GrBatchView), _I, _F, _F, _F, _P]),
+    "gr_bins_bytes": (_Z, _VIEW),
+    "gr_saved_floats": (_Z, [_VP]),
+    "gr_fwd_scratch_bytes": (_Z, _VIEW),
+    "gr_fwd_render": (_I, _VIEW + [_P, _P, _Z, _P, _Z, _P, _P, _P, _P, _P]),
+    "gr_fwd_render_saved": (_I, _VIEW + [_P, _P, _Z, _P, _Z, _P, _P]),
+    "gr_fwd_compose": (_I, [_VP, _P, _P, _P, _P, _P]),
+    "gr_fwd_bin": (_I, _VIEW + [_P, _P, _Z, _P, _Z, _P]),
+    "gr_bwd_bytes": (_Z, _VIEW),
+    # (a comment names the arguments between the groups, as the header does)
+    "gr_bwd": (_I, _VIEW + _PARAMS + _STATE + _UPSTREAM + _GRADS + _WS + [_P]),  # stream
+    "gr_bwd_indexed": (_I, _VIEW + _PARAMS + _STATE + _UPSTREAM + [_P] + _GRADS + _WS + [_P]),  # index; stream
+    "gr_bwd_camera": (_I, _VIEW + _PARAMS + _WS + [_I, _P, _P]),  # depth, d_camera, stream
+    # g_scale, loss_out; accumulate; stream
+    "gr_bwd_l1": (_I, _VIEW + _PARAMS + _STATE + _L1 + [_F, _P] + _GRADS + [_I] + _WS + [_P]),
+    "gr_bwd_fit": (_I, _VIEW + _PARAMS + _STATE + _L1 + _DEPTH + [_F, _P] + _GRADS + [_I] + _WS + [_P]),
+    "gr_fit_param_step": (_I, [ctypes.c_int64, _I, _P, _P, _PA, _I, _F, _I, _P, _P, _F, _F, ctypes.c_double,
+                               ctypes.c_double, _F, _P]),
+    "gr_adam_step": (_I, [ctypes.c_int64, _P, _P, _P, _P, _F, _F, ctypes.c_double, ctypes.c_double, _F, _P]),
+    "gr_fit_param_steps": (_I, [_I, ctypes.POINTER(GrParamStep), ctypes.c_double, ctypes.c_double, _F, _P]),
+    "gr_fit_param_steps_sched": (_I, [_I, ctypes.POINTER(GrParamStep), ctypes.c_double, ctypes.c_double, _F, _P, _P, _P,
+                                      _P, _P]),
+    "gr_fit_activations_ws_bytes": (_Z, [ctypes.c_int64]),
+    "gr_fit_activations": (_I, [ctypes.c_int64, _P, _P, _P, ctypes.c_int64, _P, _P, _P, _F, _F, _P, _P, _Z, _P]),
+    # geom, bins + bytes, scratch + bytes; g_scale, loss_out, out_rgb, out_alpha; stream
+    "gr_fwd_render_l1": (_I, _VIEW + [_P, _P, _Z, _P, _Z] + _L1 + [_F, _P, _P, _P] + _WS + [_P]),
+    "gr_bwd_splat": (_I, _VIEW + [_P, _P, _P, _Z, _P]),
+    "gr_reduce_views": (_I, [_I, ctypes.POINTER(GrReduceView), _I] + _PARAMS + _GRADS + [_I, _P]),  # accumulate, stream
+    "gr_view_sums_floats": (_Z, [_I]),
+    "gr_gather_view": (_I, _VIEW + [_P, _P, _P, _P, _P]),
+    "gr_bwd_fit_gather": (_I, _VIEW + _STATE + _L1 + _DEPTH + [_F, _P] + _WS + _SUMS + [_P]),
+    "gr_bwd_ssim_bytes": (_Z, _VIEW),
+    # g_scale, w_dssim, loss_out
+    "gr_bwd_fit_ssim": (_I, _VIEW + _PARAMS + _STATE + _L1 + _DEPTH + [_F, _F, _P] + _GRADS + [_I] + _WS + [_P]),
+    "gr_bwd_fit_ssim_gather": (_I, _VIEW + _STATE + _L1 + _DEPTH + [_F, _F, _P] + _WS + _SUMS + [_P]),
+    "gr_fit_views_ssim": (_I, _EXEC + _PARAMS + [_F, _F, _F, _F, _P, _PA, _P]),
+    "gr_reduce_sums": (_I, [_I, ctypes.POINTER(GrSumsView), _I] + _PARAMS + _GRADS + [_I, _P]),
+    "gr_density_stats": (_I, [_I, ctypes.POINTER(GrSumsView), _I, _P, _P, _P, _F, _P, _P]),
+    "gr_executor_density_stats": (_I, [_P, _PA]),
+    "gr_camera_grads_ws_bytes": (_Z, [_I, _I]),
+    "gr_camera_grads_sums": (_I, [_I, ctypes.POINTER(GrSumsView), _I] + _PARAMS + [_PA, _P, _Z, _P]),
+    "gr_executor_camera_grads": (_I, [_P, _P]),
+    "gr_executor_create": (_I, [_I, _PA]),
     "gr_executor_destroy": (None, [_P]),
-    "gr_fit_views": (ctypes.c_int, [_P, ctypes.POINTER(GrFitConfig), ctypes.c_int, ctypes.POINTER(GrFitTarget), ctypes.c_int,
-                                    _P, _P, _P, ctypes.c_int, _P, ctypes.c_float, ctypes.c_float, ctypes.c_float, _P,
-                                    ctypes.POINTER(ctypes.c_void_p), _P]),
-    "gr_eval_ws_bytes": (ctypes.c_size_t, [_VP]),
-    "gr_eval_view": (ctypes.c_int, [_VP, _P, _P, _P, _P, ctypes.c_size_t, _P]),
-    "gr_eval_views": (ctypes.c_int, [_P, ctypes.POINTER(GrFitConfig), ctypes.c_int, ctypes.POINTER(GrFitTarget), ctypes.c_int,
-                                     _P, _P, _P, ctypes.c_int, _P, _P, _P]),
-    "gr_cc_ws_bytes": (ctypes.c_size_t, [_VP]),
-    "gr_cc_fit_view": (ctypes.c_int, [_VP, _P, _P, ctypes.c_float, _P, _P, ctypes.c_size_t, _P]),
-    "gr_eval_view_cc": (ctypes.c_int, [_VP, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
-    "gr_eval_views_cc": (ctypes.c_int, [_P, ctypes.POINTER(GrFitConfig), ctypes.c_int, ctypes.POINTER(GrFitTarget),
-                                        ctypes.c_int, _P, _P, _P, ctypes.c_int, _P, ctypes.c_float, _P, _P]),
-    "gr_eval_mask_ws_bytes": (ctypes.c_size_t, [_VP]),
-    "gr_eval_view_masked": (ctypes.c_int, [_VP, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
-    "gr_eval_views_masked": (ctypes.c_int, [_P, ctypes.POINTER(GrFitConfig), ctypes.c_int, ctypes.POINTER(GrFitTarget),
-                                            ctypes.c_int, _P, _P, _P, ctypes.c_int, _P, _P, _P]),
-    "gr_contrib_ws_bytes": (ctypes.c_size_t, [_VP, ctypes.c_int, _PP]),
-    "gr_contrib_view": (ctypes.c_int, [_VP, ctypes.c_int, _PP, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
-    "gr_contrib_views": (ctypes.c_int, [_P, ctypes.POINTER(GrFitConfig), ctypes.c_int, ctypes.POINTER(GrFitTarget),
-                                        ctypes.c_int, _P, _P, _P, ctypes.c_int, _P, _P, _P]),
-    "gr_error_ws_bytes": (ctypes.c_size_t, [_VP, ctypes.c_int, _PP]),
-    "gr_error_view": (ctypes.c_int, [_VP, ctypes.c_int, _PP, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
-    "gr_error_views": (ctypes.c_int, [_P, ctypes.POINTER(GrFitConfig), ctypes.c_int, ctypes.POINTER(GrFitTarget),
-                                      ctypes.c_int, _P, _P, _P, ctypes.c_int, _P, _P, _P]),
-    "gr_render_u8": (ctypes.c_int, [ctypes.POINTER(GrRenderParams), ctypes.c_int, _P, _P, _P, _P, _P]),
-    "gr_geom_layout": (None, [ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
-    "gr_bins_layout": (None, [_VP, ctypes.c_int, _PP, ctypes.POINTER(ctypes.c_size_t)]),
-    "gr_items_layout": (None, [_VP, ctypes.c_int, _PP, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int)]),
+    "gr_fit_views": (_I, _EXEC + _PARAMS + [_F, _F, _F, _P, _PA, _P]),
+    "gr_eval_ws_bytes": (_Z, [_VP]),
+    "gr_eval_view": (_I, [_VP, _P, _P, _P, _P, _Z, _P]),
+    "gr_eval_views": (_I, _EXEC + _PARAMS + [_P, _P]),
+    "gr_cc_ws_bytes": (_Z, [_VP]),
+    "gr_cc_fit_view": (_I, [_VP, _P, _P, _F, _P, _P, _Z, _P]),
+    "gr_eval_view_cc": (_I, [_VP, _P, _P, _P, _P, _P, _Z, _P]),
+    "gr_eval_views_cc": (_I, _EXEC + _PARAMS + [_F, _P, _P]),
+    "gr_eval_mask_ws_bytes": (_Z, [_VP]),
+    "gr_eval_view_masked": (_I, [_VP, _P, _P, _P, _P, _P, _Z, _P]),
+    "gr_eval_views_masked": (_I, _EXEC + _PARAMS + [_P, _P]),
+    "gr_contrib_ws_bytes": (_Z, _VIEW),
+    "gr_contrib_view": (_I, _VIEW + [_P, _P, _P, _P, _P, _Z, _P]),
+    "gr_contrib_views": (_I, _EXEC + _PARAMS + [_P, _P]),
+    "gr_error_ws_bytes": (_Z, _VIEW),
+    "gr_error_view": (_I, _VIEW + [_P, _P, _P, _P, _P, _P, _Z, _P]),
+    "gr_error_views": (_I, _EXEC + _PARAMS + [_P, _P]),
+    "gr_render_u8": (_I, [ctypes.POINTER(GrRenderParams), _I, _P, _P, _P, _P, _P]),
+    "gr_geom_layout": (None, [_I, ctypes.POINTER(_Z)]),
+    "gr_bins_layout": (None, _VIEW + [ctypes.POINTER(_Z)]),
+    "gr_items_layout": (None, _VIEW + [ctypes.POINTER(_Z), ctypes.POINTER(_I)]),
     "gr_profile_begin": (None, []),
-    "gr_profile_end": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)]),
-    "gr_l1_loss_ws_bytes": (ctypes.c_size_t, []),
-    "gr_l1_loss_fwd": (ctypes.c_int, [_P, _P, ctypes.c_int64, _P, _P, ctypes.c_int64, ctypes.c_float, _P, _P,
-                                      ctypes.c_size_t, _P]),
-    "gr_l1_loss_bwd": (ctypes.c_int, [_P, _P, ctypes.c_int64, _P, _P, ctypes.c_int64, ctypes.c_float, _P, _P, _P, _P]),
-    "gr_ssim_ws_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
-    "gr_ssim_fwd": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P,
-                                   ctypes.c_size_t, _P]),
-    "gr_ssim_bwd": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, ctypes.c_size_t, _P, _P]),
+    "gr_profile_end": (_I, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_I)]),
+    "gr_l1_loss_ws_bytes": (_Z, []),
+    "gr_l1_loss_fwd": (_I, [_P, _P, ctypes.c_int64, _P, _P, ctypes.c_int64, _F, _P, _P, _Z, _P]),
+    "gr_l1_loss_bwd": (_I, [_P, _P, ctypes.c_int64, _P, _P, ctypes.c_int64, _F, _P, _P, _P, _P]),
+    "gr_ssim_ws_bytes": (_Z, [_I, _I, _I, _I]),
+    "gr_ssim_fwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _Z, _P]),
+    "gr_ssim_bwd": (_I, [_P, _P, _I, _I, _I, _P, _P, _Z, _P, _P]),
     "gr_last_error": (ctypes.c_char_p, []),
     "gr_version": (ctypes.c_char_p, []),
 }

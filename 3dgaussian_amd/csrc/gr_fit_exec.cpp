@@ -172,14 +172,25 @@ struct Pass {
   }
 };
 
+// A call's operands beside its views: the activated parameters, the loss terms and where the losses and the streams'
+// gradient accumulators go (a render-only pass has neither).
+struct Params {
+  const float *means = nullptr, *scales = nullptr, *colors = nullptr;
+  int color_dim = 3;
+  const float* opacities = nullptr;
+};
+struct Operands {
+  int n = 0;
+  Params p;
+  float w_sil = 0.0f, w_depth = 0.0f, g_scale = 1.0f, w_dssim = 0.0f;  // w_dssim > 0: the D-SSIM form
+  float* losses = nullptr;
+  float* const* acc = nullptr;
+};
+
 static gr_status fit_views_on_device(gr_executor* ex, const gr_fit_config* cfg, int num_views, const gr_fit_target* views,
-                                     int n, const float* means, const float* scales, const float* colors, int color_dim,
-                                     const float* opacities, float w_sil, float w_depth, float g_scale, float w_dssim,
-                                     float* losses, float* const* acc, void* stream, Pass pass = {});
-static gr_status enqueue_views(gr_executor* ex, const gr_fit_config* cfg, int num_views, const gr_fit_target* views, int n,
-                               const float* means, const float* scales, const float* colors, int color_dim,
-                               const float* opacities, float w_sil, float w_depth, float g_scale, float w_dssim, float* losses,
-                               float* const* acc, const Sched& sc, const std::vector<hipStream_t>& st, hipStream_t prep,
+                                     const Operands& op, void* stream, Pass pass = {});
+static gr_status enqueue_views(gr_executor* ex, const gr_fit_config* cfg, int num_views, const gr_fit_target* views,
+                               const Operands& op, const Sched& sc, const std::vector<hipStream_t>& st, hipStream_t prep,
                                bool depth, int nslots, int& ngroups, Pass pass);
 
 extern "C" {
@@ -235,10 +246,8 @@ void gr_executor_destroy(gr_executor* ex) {
 }
 
 static gr_status fit_views_checked(gr_executor* ex, const gr_fit_config* cfg, int num_views, const gr_fit_target* views,
-                                   int n, const float* means, const float* scales, const float* colors, int color_dim,
-                                   const float* opacities, float w_sil, float w_depth, float g_scale, float w_dssim,
-                                   float* losses, float* const* acc, void* stream) {
-  if (!ex || !cfg || (num_views > 0 && (!views || !losses || !acc)))
+                                   const Operands& op, void* stream) {
+  if (!ex || !cfg || (num_views > 0 && (!views || !op.losses || !op.acc)))
     return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, "gr_fit_views: null argument");
   // every batch of a stream (its last one holds reduce_tail views) and every preparation group must fit the
   // fixed-size view arrays of gr_reduce_sums / gr_fwd_prepare_views_async (and the per-stream sums ring)
@@ -246,7 +255,7 @@ static gr_status fit_views_checked(gr_executor* ex, const gr_fit_config* cfg, in
       cfg->prep_first < 1 || cfg->prep_first > GR_PREPARE_MAX_VIEWS || cfg->reduce_batch < 1 ||
       cfg->reduce_batch > GR_REDUCE_MAX_VIEWS || cfg->reduce_tail < 0 || cfg->reduce_tail > cfg->reduce_batch)
     return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, "gr_fit_views: configuration out of range");
-  if (num_views == 0 || n <= 0) return GR_OK;
+  if (num_views == 0 || op.n <= 0) return GR_OK;
   if (cfg->caps && !cfg->overflow) return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, "gr_fit_views: caps without overflow");
   const bool depth = views[0].target_depth != nullptr;  // the depth-loss path (one form per call)
   for (int j = 0; j < num_views; ++j) {
@@ -258,8 +267,7 @@ static gr_status fit_views_checked(gr_executor* ex, const gr_fit_config* cfg, in
   int prev_dev = 0;
   GR_EXEC_TRY(hipGetDevice(&prev_dev));
   GR_EXEC_TRY(hipSetDevice(ex->device));
-  const gr_status st = fit_views_on_device(ex, cfg, num_views, views, n, means, scales, colors, color_dim, opacities, w_sil,
-                                           w_depth, g_scale, w_dssim, losses, acc, stream);
+  const gr_status st = fit_views_on_device(ex, cfg, num_views, views, op, stream);
   (void)hipSetDevice(prev_dev);
   return st;
 }
@@ -280,8 +288,9 @@ gr_status gr_fit_views(gr_executor* ex, const gr_fit_config* cfg, int num_views,
                        const float* means, const float* scales, const float* colors, int color_dim,
                        const float* opacities, float w_sil, float w_depth, float g_scale, float* losses,
                        float* const* acc, void* stream) {
-  return fit_views_checked(ex, cfg, num_views, views, n, means, scales, colors, color_dim, opacities, w_sil, w_depth,
-                           g_scale, 0.0f, losses, acc, stream);
+  return fit_views_checked(ex, cfg, num_views, views,
+                           {n, {means, scales, colors, color_dim, opacities}, w_sil, w_depth, g_scale, 0.0f, losses, acc},
+                           stream);
 }
 
 gr_status gr_fit_views_ssim(gr_executor* ex, const gr_fit_config* cfg, int num_views, const gr_fit_target* views, int n,
@@ -290,14 +299,15 @@ gr_status gr_fit_views_ssim(gr_executor* ex, const gr_fit_config* cfg, int num_v
                             float* losses, float* const* acc, void* stream) {
   if (!(w_dssim >= 0.0f && w_dssim <= 1.0f))
     return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, "gr_fit_views_ssim: w_dssim must be in [0, 1]");
-  return fit_views_checked(ex, cfg, num_views, views, n, means, scales, colors, color_dim, opacities, w_sil, w_depth,
-                           g_scale, w_dssim, losses, acc, stream);
+  return fit_views_checked(ex, cfg, num_views, views,
+                           {n, {means, scales, colors, color_dim, opacities}, w_sil, w_depth, g_scale, w_dssim, losses, acc},
+                           stream);
 }
 
 // A render-only pass's entry point: its checks (`name` in each message) and the schedule on the executor's device.
+// op: n and the parameters (no loss terms, losses or accumulators).
 static gr_status pass_views_checked(const char* name, Pass pass, gr_executor* ex, const gr_fit_config* cfg, int num_views,
-                                    const gr_fit_target* views, int n, const float* means, const float* scales,
-                                    const float* colors, int color_dim, const float* opacities, void* stream) {
+                                    const gr_fit_target* views, const Operands& op, void* stream) {
   const std::string who = name;
   if (!ex || !cfg || (num_views > 0 && (!views || !pass.out)))
     return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, (who + ": null argument").c_str());
@@ -306,7 +316,7 @@ static gr_status pass_views_checked(const char* name, Pass pass, gr_executor* ex
     return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, (who + ": configuration out of range").c_str());
   if (cfg->caps)
     return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, (who + ": device-side sizing (caps) is not supported").c_str());
-  if (num_views <= 0 || n <= 0) return GR_OK;
+  if (num_views <= 0 || op.n <= 0) return GR_OK;
   for (int j = 0; pass.kind != Pass::contrib && j < num_views; ++j)
     if (!views[j].target_rgb) return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, (who + ": null target").c_str());
   for (int j = 0; pass.kind == Pass::eval_masked && j < num_views; ++j)
@@ -317,8 +327,7 @@ static gr_status pass_views_checked(const char* name, Pass pass, gr_executor* ex
   int prev_dev = 0;
   GR_EXEC_TRY(hipGetDevice(&prev_dev));
   GR_EXEC_TRY(hipSetDevice(ex->device));
-  const gr_status st = fit_views_on_device(ex, &c, num_views, views, n, means, scales, colors, color_dim, opacities, 0.0f, 0.0f,
-                                           1.0f, 0.0f, nullptr, nullptr, stream, pass);
+  const gr_status st = fit_views_on_device(ex, &c, num_views, views, op, stream, pass);
   (void)hipSetDevice(prev_dev);
   return st;
 }
@@ -326,8 +335,8 @@ static gr_status pass_views_checked(const char* name, Pass pass, gr_executor* ex
 gr_status gr_eval_views(gr_executor* ex, const gr_fit_config* cfg, int num_views, const gr_fit_target* views, int n,
                         const float* means, const float* scales, const float* colors, int color_dim, const float* opacities,
                         float* metrics, void* stream) {
-  return pass_views_checked("gr_eval_views", {Pass::eval, metrics}, ex, cfg, num_views, views, n, means, scales, colors,
-                            color_dim, opacities, stream);
+  return pass_views_checked("gr_eval_views", {Pass::eval, metrics}, ex, cfg, num_views, views,
+                            {n, {means, scales, colors, color_dim, opacities}}, stream);
 }
 
 gr_status gr_eval_views_cc(gr_executor* ex, const gr_fit_config* cfg, int num_views, const gr_fit_target* views, int n,
@@ -335,44 +344,42 @@ gr_status gr_eval_views_cc(gr_executor* ex, const gr_fit_config* cfg, int num_vi
                            const float* opacities, float ridge, float* rows, void* stream) {
   if (!(ridge > 0.0f) || !(ridge <= 3.402823466e38f))  // (as gr_cc_fit_view, before anything is enqueued)
     return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, "gr_eval_views_cc: ridge must be positive and finite");
-  return pass_views_checked("gr_eval_views_cc", {Pass::eval_cc, rows, ridge}, ex, cfg, num_views, views, n, means, scales,
-                            colors, color_dim, opacities, stream);
+  return pass_views_checked("gr_eval_views_cc", {Pass::eval_cc, rows, ridge}, ex, cfg, num_views, views,
+                            {n, {means, scales, colors, color_dim, opacities}}, stream);
 }
 
 gr_status gr_eval_views_masked(gr_executor* ex, const gr_fit_config* cfg, int num_views, const gr_fit_target* views, int n,
                                const float* means, const float* scales, const float* colors, int color_dim,
                                const float* opacities, float* metrics, void* stream) {
-  return pass_views_checked("gr_eval_views_masked", {Pass::eval_masked, metrics}, ex, cfg, num_views, views, n, means, scales,
-                            colors, color_dim, opacities, stream);
+  return pass_views_checked("gr_eval_views_masked", {Pass::eval_masked, metrics}, ex, cfg, num_views, views,
+                            {n, {means, scales, colors, color_dim, opacities}}, stream);
 }
 
 gr_status gr_contrib_views(gr_executor* ex, const gr_fit_config* cfg, int num_views, const gr_fit_target* views, int n,
                            const float* means, const float* scales, const float* colors, int color_dim,
                            const float* opacities, float* peak, void* stream) {
-  return pass_views_checked("gr_contrib_views", {Pass::contrib, peak}, ex, cfg, num_views, views, n, means, scales, colors,
-                            color_dim, opacities, stream);
+  return pass_views_checked("gr_contrib_views", {Pass::contrib, peak}, ex, cfg, num_views, views,
+                            {n, {means, scales, colors, color_dim, opacities}}, stream);
 }
 
 gr_status gr_error_views(gr_executor* ex, const gr_fit_config* cfg, int num_views, const gr_fit_target* views, int n,
                          const float* means, const float* scales, const float* colors, int color_dim,
                          const float* opacities, float* err, void* stream) {
-  return pass_views_checked("gr_error_views", {Pass::error, err}, ex, cfg, num_views, views, n, means, scales, colors,
-                            color_dim, opacities, stream);
+  return pass_views_checked("gr_error_views", {Pass::error, err}, ex, cfg, num_views, views,
+                            {n, {means, scales, colors, color_dim, opacities}}, stream);
 }
 
 }  // extern "C"
 
 static gr_status fit_views_on_device(gr_executor* ex, const gr_fit_config* cfg, int num_views, const gr_fit_target* views,
-                                     int n, const float* means, const float* scales, const float* colors, int color_dim,
-                                     const float* opacities, float w_sil, float w_depth, float g_scale, float w_dssim,
-                                     float* losses, float* const* acc, void* stream, Pass pass) {
+                                     const Operands& op, void* stream, Pass pass) {
   const bool fwd_only = pass.fwd_only();
   const bool depth = !fwd_only && views[0].target_depth != nullptr;
   const Sched sc = schedule(num_views, *cfg);
   const int ns = sc.ns;
   for (int k = 0; !fwd_only && k < ns; ++k)
     for (int q = 0; q < 4; ++q)
-      if (!acc[4 * k + q]) return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, "gr_fit_views: null accumulator");
+      if (!op.acc[4 * k + q]) return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, "gr_fit_views: null accumulator");
   for (int k = 0; !fwd_only && ex->stats && k < ns; ++k)
     if (!ex->stats[k]) return gr_exec_set_error(GR_ERR_INVALID_ARGUMENT, "gr_fit_views: null density stats buffer");
   hipStream_t main = (hipStream_t)stream;
@@ -442,17 +449,16 @@ static gr_status fit_views_on_device(gr_executor* ex, const gr_fit_config* cfg, 
     if (hipEventRecord(ex->groups[ngroups], prep) != hipSuccess || hipStreamWaitEvent(main, ex->groups[ngroups], 0) != hipSuccess)
       (void)hipStreamSynchronize(prep);
   };
-  const gr_status status = enqueue_views(ex, cfg, num_views, views, n, means, scales, colors, color_dim, opacities, w_sil,
-                                         w_depth, g_scale, w_dssim, losses, acc, sc, st, prep, depth, nslots, ngroups, pass);
+  const gr_status status = enqueue_views(ex, cfg, num_views, views, op, sc, st, prep, depth, nslots, ngroups, pass);
   join();
   return status;
 }
 
-static gr_status enqueue_views(gr_executor* ex, const gr_fit_config* cfg, int num_views, const gr_fit_target* views, int n,
-                               const float* means, const float* scales, const float* colors, int color_dim,
-                               const float* opacities, float w_sil, float w_depth, float g_scale, float w_dssim, float* losses,
-                               float* const* acc, const Sched& sc, const std::vector<hipStream_t>& st, hipStream_t prep,
+static gr_status enqueue_views(gr_executor* ex, const gr_fit_config* cfg, int num_views, const gr_fit_target* views,
+                               const Operands& op, const Sched& sc, const std::vector<hipStream_t>& st, hipStream_t prep,
                                bool depth, int nslots, int& ngroups, Pass pass) {
+  const int n = op.n;
+  const Params& p = op.p;
   const bool fwd_only = pass.fwd_only();  // no backward, no reductions
   const int ns = sc.ns;
   const bool sized = cfg->caps != nullptr;  // device-side sizing: the plans are capacities, nothing to wait for
@@ -483,11 +489,11 @@ static gr_status enqueue_views(gr_executor* ex, const gr_fit_config* cfg, int nu
         group_of[g0 + q] = ngroups;
       }
       if (sized)
-        GR_EXEC_CALL(gr_fwd_prepare_views_sized(cnt, vs, n, means, scales, colors, color_dim, opacities, gs, geom_bytes,
-                                                cfg->caps + g0, ps, cfg->overflow, prep));
+        GR_EXEC_CALL(gr_fwd_prepare_views_sized(cnt, vs, n, p.means, p.scales, p.colors, p.color_dim, p.opacities, gs,
+                                                geom_bytes, cfg->caps + g0, ps, cfg->overflow, prep));
       else
-        GR_EXEC_CALL(gr_fwd_prepare_views_async(cnt, vs, n, means, scales, colors, color_dim, opacities, gs, geom_bytes, ps,
-                                                prep));
+        GR_EXEC_CALL(gr_fwd_prepare_views_async(cnt, vs, n, p.means, p.scales, p.colors, p.color_dim, p.opacities, gs,
+                                                geom_bytes, ps, prep));
       GR_EXEC_TRY(hipEventRecord(ex->groups[ngroups], prep));
       ++ngroups;
       next_prep = g0 + cnt;
@@ -517,16 +523,18 @@ static gr_status enqueue_views(gr_executor* ex, const gr_fit_config* cfg, int nu
       b[q].sums = pending[k][q].sums;
       b[q].sums3 = pending[k][q].sums3;
     }
-    GR_EXEC_CALL(gr_reduce_sums(nb, b, n, means, scales, colors, color_dim, opacities, acc[4 * k + 0], acc[4 * k + 1],
-                                acc[4 * k + 2], acc[4 * k + 3], started[k], st[k]));
+    float* const* acc = op.acc + 4 * k;
+    GR_EXEC_CALL(gr_reduce_sums(nb, b, n, p.means, p.scales, p.colors, p.color_dim, p.opacities, acc[0], acc[1], acc[2],
+                                acc[3], started[k], st[k]));
     if (ex->stats)  // the batch's density statistics beside its chain rule (gr_executor_density_stats)
-      GR_EXEC_CALL(gr_density_stats(nb, b, n, means, scales, opacities, 1.0f / g_scale, ex->stats[k], st[k]));
+      GR_EXEC_CALL(gr_density_stats(nb, b, n, p.means, p.scales, p.opacities, 1.0f / op.g_scale, ex->stats[k], st[k]));
     if (ex->cams) {  // the batch's camera gradients, view j into row j (gr_executor_camera_grads)
       float* rows[GR_REDUCE_MAX_VIEWS];
       for (int q = 0; q < nb; ++q) rows[q] = ex->cams + (size_t)GR_CAMERA_GRADS * pending[k][q].j;
       Buf& cw = ex->ws[k].cam;
       GR_EXEC_TRY(cw.fit(gr_camera_grads_ws_bytes(n, nb), st[k]));
-      GR_EXEC_CALL(gr_camera_grads_sums(nb, b, n, means, scales, colors, color_dim, opacities, rows, cw.p, cw.cap, st[k]));
+      GR_EXEC_CALL(gr_camera_grads_sums(nb, b, n, p.means, p.scales, p.colors, p.color_dim, p.opacities, rows, cw.p, cw.cap,
+                                        st[k]));
     }
     pending[k].clear();
     started[k] = 1;
@@ -547,7 +555,7 @@ static gr_status enqueue_views(gr_executor* ex, const gr_fit_config* cfg, int nu
     if (plan.num_pairs < 0 || plan.num_slots < 0) return gr_exec_set_error(GR_ERR_OVERFLOW, "pair count overflows int32");
     const gr_view& v = views[j].view;
     const size_t bins_bytes = gr_bins_bytes(&v, n, &plan), scratch_bytes = gr_fwd_scratch_bytes(&v, n, &plan);
-    const bool ssim = w_dssim > 0.0f;  // the D-SSIM form (gr_fit_views_ssim)
+    const bool ssim = op.w_dssim > 0.0f;  // the D-SSIM form (gr_fit_views_ssim)
     const size_t ws_bytes = ssim ? gr_bwd_ssim_bytes(&v, n, &plan) : gr_bwd_bytes(&v, n, &plan);
     StreamWs& W = ex->ws[k];
     GR_EXEC_TRY(W.bins.fit(bins_bytes, s));
@@ -561,40 +569,36 @@ static gr_status enqueue_views(gr_executor* ex, const gr_fit_config* cfg, int nu
       GR_EXEC_CALL(gr_fwd_render(&v, n, &plan, geom[j], bins, W.bins.cap, scratch, W.scratch.cap, nullptr, nullptr,
                                  nullptr, (float*)W.saved.p, s));
       GR_EXEC_CALL(pass.on_saved(j, views[j], n, &plan, geom[j], bins, W, s));
-    } else if (ssim) {
-      // the saved sums only (no image: the D-SSIM forward stages the colours from them); sums3 with a depth target
+    } else if (ssim || depth) {
+      // the saved-sums forms: the sums only (no image: the D-SSIM forward stages the colours from them), then the D-SSIM
+      // or the depth-loss backward up to the view's sums; sums3 with a depth target
+      const gr_fit_target& t = views[j];
       GR_EXEC_TRY(W.saved.fit(gr_saved_floats(&v) * sizeof(float), s));
+      float* saved = (float*)W.saved.p;
       GR_EXEC_CALL(gr_fwd_render(&v, n, &plan, geom[j], bins, W.bins.cap, scratch, W.scratch.cap, nullptr, nullptr,
-                                 nullptr, (float*)W.saved.p, s));
+                                 nullptr, saved, s));
       Buf& sb = W.sums[pending[k].size()];
       Buf& s3 = W.sums3[pending[k].size()];
       GR_EXEC_TRY(sb.fit(sums_bytes, s));
       if (depth) GR_EXEC_TRY(s3.fit((size_t)n * sizeof(float), s));
       float* p3 = depth ? (float*)s3.p : nullptr;
-      GR_EXEC_CALL(gr_bwd_fit_ssim_gather(&v, n, &plan, geom[j], bins, (const float*)W.saved.p, views[j].target_rgb,
-                                          views[j].target_mask, w_sil, views[j].target_depth, w_depth, g_scale, w_dssim,
-                                          losses + j, ws, W.ws.cap, (float*)sb.p, p3, s));
+      if (ssim)
+        GR_EXEC_CALL(gr_bwd_fit_ssim_gather(&v, n, &plan, geom[j], bins, saved, t.target_rgb, t.target_mask, op.w_sil,
+                                            t.target_depth, op.w_depth, op.g_scale, op.w_dssim, op.losses + j, ws, W.ws.cap,
+                                            (float*)sb.p, p3, s));
+      else
+        GR_EXEC_CALL(gr_bwd_fit_gather(&v, n, &plan, geom[j], bins, saved, t.target_rgb, t.target_mask, op.w_sil,
+                                       t.target_depth, op.w_depth, op.g_scale, op.losses + j, ws, W.ws.cap, (float*)sb.p, p3, s));
       pending[k].push_back({j, v, (float*)sb.p, p3});
-    } else if (!depth) {
+    } else {
       GR_EXEC_CALL(gr_fwd_render_l1(&v, n, &plan, geom[j], bins, W.bins.cap, scratch, W.scratch.cap, views[j].target_rgb,
-                                    views[j].target_mask, w_sil, g_scale, losses + j, nullptr, nullptr, ws, W.ws.cap, s));
+                                    views[j].target_mask, op.w_sil, op.g_scale, op.losses + j, nullptr, nullptr, ws,
+                                    W.ws.cap, s));
       GR_EXEC_CALL(gr_bwd_splat(&v, n, &plan, geom[j], bins, ws, W.ws.cap, s));
       Buf& sb = W.sums[pending[k].size()];
       GR_EXEC_TRY(sb.fit(sums_bytes, s));
       GR_EXEC_CALL(gr_gather_view(&v, n, &plan, geom[j], bins, ws, (float*)sb.p, s));
       pending[k].push_back({j, v, (float*)sb.p, nullptr});
-    } else {
-      GR_EXEC_TRY(W.saved.fit(gr_saved_floats(&v) * sizeof(float), s));
-      GR_EXEC_CALL(gr_fwd_render(&v, n, &plan, geom[j], bins, W.bins.cap, scratch, W.scratch.cap, nullptr, nullptr,
-                                 nullptr, (float*)W.saved.p, s));
-      Buf& sb = W.sums[pending[k].size()];
-      Buf& s3 = W.sums3[pending[k].size()];
-      GR_EXEC_TRY(sb.fit(sums_bytes, s));
-      GR_EXEC_TRY(s3.fit((size_t)n * sizeof(float), s));
-      GR_EXEC_CALL(gr_bwd_fit_gather(&v, n, &plan, geom[j], bins, (const float*)W.saved.p, views[j].target_rgb,
-                                     views[j].target_mask, w_sil, views[j].target_depth, w_depth, g_scale, losses + j, ws,
-                                     W.ws.cap, (float*)sb.p, (float*)s3.p, s));
-      pending[k].push_back({j, v, (float*)sb.p, (float*)s3.p});
     }
     // the geom slot may be refilled once this stream has passed its last reader
     GeomSlot& gsl = ex->geoms[slot_of[j]];

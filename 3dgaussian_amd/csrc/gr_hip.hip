@@ -6014,17 +6014,61 @@ static TZones tile_zones(const ViewCtx& c) {
   return Z;
 }
 
-// The fit loss of a view (mean |out - t| + w_sil mean |alpha - m|, with t_depth the depth term): its targets and
-// weights, the per-tile sums in the backward workspace and the element counts of the means.
-static L1Args fit_l1_args(const ViewCtx& c, const float* t_rgb, const float* t_mask, float w_sil, float g_scale,
-                          float* loss_out, const float* t_depth = nullptr, float w_depth = 0.0f) {
-  L1Args l1{t_rgb, t_mask, w_sil, g_scale, c.w.tile_loss};
-  l1.loss_out = loss_out;
+// ---- The host side's operand groups: what the entry points pass on to fwd_impl, bwd_impl and
+// the launches of the chain rule, each in the order of the ABI's argument lists.  Every member is absent by default.
+struct ParamsIn {  // the activated parameters
+  const float *means = nullptr, *scales = nullptr, *colors = nullptr;
+  int color_dim = 3;  // (an entry without parameters, the gather entries: a colour dim that check_color_dim accepts)
+  const float* opacities = nullptr;
+};
+struct GradsOut {  // the chain rule's outputs (the kernels' own GradOut is one Gaussian's rows of these)
+  float *d_means = nullptr, *d_scales = nullptr, *d_colors = nullptr, *d_opacities = nullptr;
+  int accumulate = 0;
+};
+// The fit loss of a view: mean |out - t| + w_sil mean |alpha - m|, with t_depth the depth term, its gradients scaled by
+// g_scale, the loss itself to loss_out.  t_rgb null: no fit loss (the upstream gradients are the caller's).
+struct ViewLoss {
+  const float *t_rgb = nullptr, *t_mask = nullptr;
+  float w_sil = 0.0f;
+  const float* t_depth = nullptr;
+  float w_depth = 0.0f, g_scale = 0.0f;
+  float* loss_out = nullptr;
+  // the gr_bwd_fit_ssim entries (the workspace of gr_bwd_ssim_bytes); with w_dssim > 0 the photometric term is
+  // (1 - l) L1 + l D-SSIM, its forward from the saved sums (k_ssim_fwd_saved) and k_ssim_pixel_grads in k_pixel_grads' place
+  bool ssim_entry = false;
+  float w_dssim = 0.0f;
+};
+// One backward of a view (bwd_impl): what every entry has first (the view, its render state, the workspace), then what
+// an entry names; the chain rule into `grads`, or with `sums` the per-Gaussian sums to the caller.
+struct BwdRequest {
+  const gr_view* view = nullptr;
+  int n = 0;
+  const gr_plan* plan = nullptr;
+  const void *geom = nullptr, *bins = nullptr;
+  const float* saved = nullptr;
+  void* ws = nullptr;
+  size_t ws_bytes = 0;
+  void* stream = nullptr;
+  ParamsIn params;
+  const float *g_rgb = nullptr, *g_alpha = nullptr, *g_depth = nullptr;  // the upstream gradients (without a fit loss)
+  ViewLoss loss;
+  GradsOut grads;
+  float *sums = nullptr, *sums3 = nullptr;  // gather only: the view's sums (and depth sums) to the caller, no chain rule
+  const int* sum_index = nullptr;           // gr_bwd_indexed
+};
+
+// The kernels' form of a view's fit loss: its targets and weights, the per-tile sums in the backward workspace and the
+// element counts of the means.
+static L1Args fit_l1_args(const ViewCtx& c, const ViewLoss& vl) {
+  L1Args l1{vl.t_rgb, vl.t_mask, vl.w_sil, vl.g_scale, nullptr};
+  if (!vl.t_rgb) return l1;
+  l1.tile_loss = c.w.tile_loss;
+  l1.loss_out = vl.loss_out;
   l1.n1 = (int64_t)(3 * c.HW);
-  l1.n2 = (int64_t)(t_mask ? c.HW : 0);
-  if (t_depth) {
-    l1.t_depth = t_depth;
-    l1.w_depth = w_depth;
+  l1.n2 = (int64_t)(vl.t_mask ? c.HW : 0);
+  if (vl.t_depth) {
+    l1.t_depth = vl.t_depth;
+    l1.w_depth = vl.w_depth;
     l1.dscal = c.w.dscal;
   }
   return l1;
@@ -6193,17 +6237,17 @@ static gr_status bin_impl(const ViewCtx& c, hipStream_t s) {
 }
 
 // l1 != nullptr (gr_fwd_render_l1): no_depth_grad view without depth output; the fit loss's upstream
-// fragments and tile sums go to the backward workspace `ws`, the view loss to l1_loss_out.
+// fragments and tile sums go to the backward workspace `ws`, the view loss to l1->loss_out.
 static gr_status fwd_impl(const gr_view* v, int n, const gr_plan* plan, const void* geom, void* bins, size_t bins_bytes,
                           void* scratch, size_t scratch_bytes, float* out_rgb, float* out_alpha, float* out_depth,
-                          float* saved, void* stream, const L1Args* l1, float* l1_loss_out, void* ws, size_t ws_bytes,
+                          float* saved, void* stream, const ViewLoss* l1, void* ws, size_t ws_bytes,
                           bool depth_sums = false) {
   gr_status st = check_view(v);
   if (st != GR_OK) return st;
   if (!plan) return set_error(GR_ERR_INVALID_ARGUMENT, "plan is null");
   if (plan->num_pairs < 0 || plan->num_slots < 0) return set_error(GR_ERR_OVERFLOW, "pair count overflows int32");
   if (!l1 && !saved) return set_error(GR_ERR_INVALID_ARGUMENT, "saved is required");
-  if (l1 && (!ws || ws_bytes < gr_bwd_bytes(v, n, plan) || !l1_loss_out))
+  if (l1 && (!ws || ws_bytes < gr_bwd_bytes(v, n, plan) || !l1->loss_out))
     return set_error(GR_ERR_WORKSPACE, "gr_fwd_render_l1: backward workspace too small (or null loss)");
   if (n > 0 && (!geom || !bins)) return set_error(GR_ERR_INVALID_ARGUMENT, "null workspace");
   if (bins_bytes < gr_bins_bytes(v, n, plan)) return set_error(GR_ERR_WORKSPACE, "bins workspace too small");
@@ -6223,11 +6267,8 @@ static gr_status fwd_impl(const gr_view* v, int n, const gr_plan* plan, const vo
       if (st != GR_OK) return st;
     }
   }
-  L1Args la{nullptr, nullptr, 0.f, 0.f, nullptr};
-  if (l1) {
-    la = fit_l1_args(c, l1->t_rgb, l1->t_mask, l1->w_sil, l1->g_scale, l1_loss_out);
-    la.pieces = l1->pieces;
-  }
+  L1Args la = fit_l1_args(c, l1 ? *l1 : ViewLoss{});
+  if (l1) la.pieces = v->no_depth_grad == 1 ? 2 : 3;  // (3 at f32 grade)
   uint4* UF = l1 ? c.w.UF : nullptr;
   if (!(GR_DEBUG_SKIP & 1)) {
     // every tile has a work item (an empty tile its one empty item): the splat writes every output pixel, finishes
@@ -6258,13 +6299,13 @@ gr_status gr_fwd_render(const gr_view* v, int n, const gr_plan* plan, const void
                         void* scratch, size_t scratch_bytes, float* out_rgb, float* out_alpha, float* out_depth,
                         float* saved, void* stream) {
   return fwd_impl(v, n, plan, geom, bins, bins_bytes, scratch, scratch_bytes, out_rgb, out_alpha, out_depth, saved, stream,
-                  nullptr, nullptr, nullptr, 0);
+                  nullptr, nullptr, 0);
 }
 
 gr_status gr_fwd_render_saved(const gr_view* v, int n, const gr_plan* plan, const void* geom, void* bins,
                               size_t bins_bytes, void* scratch, size_t scratch_bytes, float* saved, void* stream) {
   return fwd_impl(v, n, plan, geom, bins, bins_bytes, scratch, scratch_bytes, nullptr, nullptr, nullptr, saved, stream,
-                  nullptr, nullptr, nullptr, 0, true);
+                  nullptr, nullptr, 0, true);
 }
 
 gr_status gr_fwd_compose(const gr_view* v, const float* saved, float* out_rgb, float* out_alpha, float* out_depth,
@@ -6299,10 +6340,14 @@ gr_status gr_fwd_render_l1(const gr_view* v, int n, const gr_plan* plan, const v
   if (!v || !v->no_depth_grad)
     return set_error(GR_ERR_INVALID_ARGUMENT, "gr_fwd_render_l1: the view must have no_depth_grad = 1 or 2");
   if (!target_rgb) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_fwd_render_l1: target_rgb is null");
-  L1Args l1{target_rgb, target_mask, w_sil, g_scale, nullptr};
-  l1.pieces = v->no_depth_grad == 1 ? 2 : 3;
+  ViewLoss l1;
+  l1.t_rgb = target_rgb;
+  l1.t_mask = target_mask;
+  l1.w_sil = w_sil;
+  l1.g_scale = g_scale;
+  l1.loss_out = loss_out;
   return fwd_impl(v, n, plan, geom, bins, bins_bytes, scratch, scratch_bytes, out_rgb, out_alpha, nullptr, nullptr, stream,
-                  &l1, loss_out, ws, ws_bytes);
+                  &l1, ws, ws_bytes);
 }
 
 }  // extern "C" (bwd_impl is internal)
@@ -6334,16 +6379,14 @@ static gr_status sums_batch(const char* name, int num_views, const gr_sums_view*
 
 // The chain rule of a batch's sums (an empty batch: zero gradients, or with accumulate the buffers as they are).
 // opened: the caller has recorded the first mark of the PROF_REDUCE pair (its gather belongs to the pair).
-static gr_status launch_reduce_sums(const SBatch& B, int n, const float* means, const float* scales, const float* colors,
-                                    int color_dim, const float* opacities, float* d_means, float* d_scales,
-                                    float* d_colors, float* d_opacities, int accumulate, const int* sum_index,
+static gr_status launch_reduce_sums(const SBatch& B, int n, const ParamsIn& p, const GradsOut& g, const int* sum_index,
                                     bool opened, hipStream_t s) {
   if (!opened) prof_mark(PROF_REDUCE, s);
-  const int gpb = 64 * (4 / reduce_sums_crw(B.nv, color_dim));
+  const int gpb = 64 * (4 / reduce_sums_crw(B.nv, p.color_dim));
   const dim3 grid((n + gpb - 1) / gpb), block(256);
-  with_color_dim(color_dim, [&](auto cd) {
-    hipLaunchKernelGGL(k_reduce_sums<cd()>, grid, block, 0, s, B, n, means, scales, colors, opacities, d_means, d_scales,
-                       d_colors, d_opacities, accumulate, sum_index);
+  with_color_dim(p.color_dim, [&](auto cd) {
+    hipLaunchKernelGGL(k_reduce_sums<cd()>, grid, block, 0, s, B, n, p.means, p.scales, p.colors, p.opacities, g.d_means,
+                       g.d_scales, g.d_colors, g.d_opacities, g.accumulate, sum_index);
   });
   GR_HIP_TRY(hipGetLastError());
   prof_mark(PROF_REDUCE, s);
@@ -6352,17 +6395,18 @@ static gr_status launch_reduce_sums(const SBatch& B, int n, const float* means, 
 
 // The camera gradients of a batch's sums into d_camera[0 .. B.nv); part holds gr_camera_grads_ws_bytes(n, B.nv).
 // one_view (gr_bwd_camera): B holds one view, which takes the one-view kernel.
-static gr_status launch_camera_grads(const SBatch& B, int n, const float* means, const float* scales, const float* colors,
-                                     int color_dim, const float* opacities, float* const* d_camera, double* part,
+static gr_status launch_camera_grads(const SBatch& B, int n, const ParamsIn& p, float* const* d_camera, double* part,
                                      bool one_view, hipStream_t s) {
   CamRows rows;
   for (int k = 0; k < GR_REDUCE_MAX_VIEWS; ++k) rows.out[k] = k < B.nv ? d_camera[k] : nullptr;
   const int blocks = blocks_for(n);
-  with_color_dim(color_dim, [&](auto cd) {
+  with_color_dim(p.color_dim, [&](auto cd) {
     if (one_view)
-      hipLaunchKernelGGL(k_camera_grad<cd()>, dim3(blocks), dim3(256), 0, s, B.r[0], n, means, scales, colors, opacities, part);
+      hipLaunchKernelGGL(k_camera_grad<cd()>, dim3(blocks), dim3(256), 0, s, B.r[0], n, p.means, p.scales, p.colors,
+                         p.opacities, part);
     else
-      hipLaunchKernelGGL(k_camera_grad_views<cd()>, dim3(blocks), dim3(256), 0, s, B, n, means, scales, colors, opacities, part);
+      hipLaunchKernelGGL(k_camera_grad_views<cd()>, dim3(blocks), dim3(256), 0, s, B, n, p.means, p.scales, p.colors,
+                         p.opacities, part);
   });
   GR_HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(k_camera_final_views, dim3(CAM_GRADS, B.nv), dim3(64), 0, s, (const double*)part, blocks, rows);
@@ -6370,16 +6414,14 @@ static gr_status launch_camera_grads(const SBatch& B, int n, const float* means,
   return GR_OK;
 }
 
-static gr_status bwd_impl(const gr_view* v, int n, const gr_plan* plan, const float* means, const float* scales,
-                          const float* colors, int color_dim, const float* opacities, const void* geom, const void* bins,
-                          const float* saved, const float* g_rgb, const float* g_alpha, const float* g_depth,
-                          const float* t_rgb, const float* t_mask, float w_sil, float g_scale, float* loss_out,
-                          float* d_means, float* d_scales, float* d_colors, float* d_opacities, int accumulate, void* ws,
-                          size_t ws_bytes, void* stream, const float* t_depth = nullptr, float w_depth = 0.0f,
-                          const int* sum_index = nullptr, float* g_sums = nullptr, float* g_sums3 = nullptr,
-                          float w_dssim = -1.0f) {
-  // w_dssim >= 0: the gr_bwd_fit_ssim entries (the workspace of gr_bwd_ssim_bytes); > 0: the photometric term is
-  // (1 - l) L1 + l D-SSIM, its forward from the saved sums (k_ssim_fwd_saved) and k_ssim_pixel_grads in k_pixel_grads' place
+static gr_status bwd_impl(const BwdRequest& r) {
+  const gr_view* v = r.view;
+  const gr_plan* plan = r.plan;
+  const int n = r.n;
+  const GradsOut& g = r.grads;
+  const ViewLoss& vl = r.loss;
+  const float *saved = r.saved, *g_rgb = r.g_rgb, *g_depth = r.g_depth, *t_rgb = vl.t_rgb, *t_depth = vl.t_depth;
+  void* ws = r.ws;
   gr_status st = check_view(v);
   if (st != GR_OK) return st;
   if ((g_depth || (t_rgb && t_depth)) && v->no_depth_grad)
@@ -6390,22 +6432,22 @@ static gr_status bwd_impl(const gr_view* v, int n, const gr_plan* plan, const fl
   if (v->rows > 0)
     return set_error(GR_ERR_INVALID_ARGUMENT, "a band of tile rows (gr_view.rows): the fused fit path only (gr_bwd_splat)");
   if (!plan) return set_error(GR_ERR_INVALID_ARGUMENT, "plan is null");
-  if ((st = check_color_dim(color_dim)) != GR_OK) return st;
+  if ((st = check_color_dim(r.params.color_dim)) != GR_OK) return st;
   if (n == 0) return GR_OK;
-  const bool gather_only = g_sums != nullptr;  // gr_bwd_fit_gather: the per-Gaussian sums to the caller, no chain rule
-  if ((!g_rgb && !t_rgb) || !saved || !geom || !bins ||
-      (!gather_only && (!d_means || !d_scales || !d_colors || !d_opacities)))
+  const bool gather_only = r.sums != nullptr;
+  if ((!g_rgb && !t_rgb) || !saved || !r.geom || !r.bins ||
+      (!gather_only && (!g.d_means || !g.d_scales || !g.d_colors || !g.d_opacities)))
     return set_error(GR_ERR_INVALID_ARGUMENT, "null pointer");
-  if (t_rgb && (!loss_out || !ws)) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_bwd_l1: null loss or workspace");
+  if (t_rgb && (!vl.loss_out || !ws)) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_bwd_l1: null loss or workspace");
   const int64_t num_pairs = plan->num_pairs;
-  const bool ssim = w_dssim > 0.0f;
+  const bool ssim = vl.ssim_entry && vl.w_dssim > 0.0f;
   if (ssim && !ssim_shape_ok(v->height, v->width, 3))
     return set_error(GR_ERR_INVALID_ARGUMENT, "gr_bwd_fit_ssim: the view exceeds the D-SSIM kernels' 2^30 values");
-  const size_t ws_need = w_dssim >= 0.0f ? gr_bwd_ssim_bytes(v, n, plan) : gr_bwd_bytes(v, n, plan);
-  if ((num_pairs > 0 || t_rgb) && (!ws || ws_bytes < ws_need))
+  const size_t ws_need = vl.ssim_entry ? gr_bwd_ssim_bytes(v, n, plan) : gr_bwd_bytes(v, n, plan);
+  if ((num_pairs > 0 || t_rgb) && (!ws || r.ws_bytes < ws_need))
     return set_error(GR_ERR_WORKSPACE, "backward workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  const ViewCtx c = view_ctx(v, n, plan, geom, bins, nullptr, ws);
+  hipStream_t s = (hipStream_t)r.stream;
+  const ViewCtx c = view_ctx(v, n, plan, r.geom, r.bins, nullptr, ws);
   const ViewK& vk = c.vk;
   const int tiles = c.tiles;
   const Bins& b = c.b;
@@ -6413,15 +6455,13 @@ static gr_status bwd_impl(const gr_view* v, int n, const gr_plan* plan, const fl
   const BwdWs& w = c.w;
   uint4* UF = w.UF;
   const bool dfit = t_rgb && t_depth;  // fused depth loss (gr_bwd_fit)
-  // the view loss: written by k_pixel_grads' last tile
-  L1Args l1 = t_rgb ? fit_l1_args(c, t_rgb, t_mask, w_sil, g_scale, loss_out, t_depth, w_depth)
-                    : L1Args{t_rgb, t_mask, w_sil, g_scale, nullptr};
+  L1Args l1 = fit_l1_args(c, vl);  // the view loss: written by k_pixel_grads' last tile
   // the arrival tickets of the one-launch reductions below: the bins' (zeroed by the work-item builder, left zero
   // by every kernel that takes one)
   int* ticket = b.ticket;
   if (dfit) {
     launch_one(k_depth_tile_max, dim3(tiles), 256, 0, s, depth_tile_max_args(c, saved));
-    launch_one(k_depth_tile_sums, dim3(tiles), 256, 0, s, depth_tile_sums_args(c, saved, t_depth, w_depth, g_scale));
+    launch_one(k_depth_tile_sums, dim3(tiles), 256, 0, s, depth_tile_sums_args(c, saved, t_depth, vl.w_depth, vl.g_scale));
     GR_HIP_TRY(hipGetLastError());
   }
   const bool depth = g_depth != nullptr || dfit;  // an upstream depth gradient reaches the splat
@@ -6433,7 +6473,7 @@ static gr_status bwd_impl(const gr_view* v, int n, const gr_plan* plan, const fl
     // the D-SSIM forward's workspace (gr_ssim_ws_bytes: per-tile partial sums, then the three maps) follows gr_bwd_bytes
     float* partial = (float*)((char*)ws + gr_bwd_bytes(v, n, plan));
     float* maps = (float*)((char*)partial + ssim_partial_bytes(v->height, v->width));
-    l1.w_dssim = w_dssim;
+    l1.w_dssim = vl.w_dssim;
     hipLaunchKernelGGL(k_ssim_fwd_saved, dim3(vk.tiles_x, vk.tiles_y), dim3(256), 0, s, vk, (const float4*)saved, t_rgb,
                        partial, maps);
     hipLaunchKernelGGL(k_ssim_pixel_grads, dim3(tiles), dim3(256), 0, s, vk, (const float4*)saved, saved + 4 * HW,
@@ -6441,7 +6481,7 @@ static gr_status bwd_impl(const gr_view* v, int n, const gr_plan* plan, const fl
     GR_HIP_TRY(hipGetLastError());
   } else if (num_pairs > 0 || t_rgb) {
     launch_one(k_pixel_grads, dim3(tiles), 256, 0, s,
-               pixel_grads_args(c, saved, g_rgb, g_alpha, g_depth, pieces, l1, depth));
+               pixel_grads_args(c, saved, g_rgb, r.g_alpha, g_depth, pieces, l1, depth));
     GR_HIP_TRY(hipGetLastError());
   }
   if (num_pairs > 0) {
@@ -6456,8 +6496,8 @@ static gr_status bwd_impl(const gr_view* v, int n, const gr_plan* plan, const fl
     // 32-byte rows: the lean gather into per-Gaussian sums (with a depth gradient also the tail pairs and
     // the depth sums), then the chain rule of that one view (the two stages of gr_gather_view +
     // gr_reduce_sums; a one-pass kernel needs 117 VGPRs for the chain rule while it gathers)
-    float* sums = gather_only ? g_sums : w.sums;
-    float* sums3 = gather_only ? g_sums3 : w.sums3;
+    float* sums = gather_only ? r.sums : w.sums;
+    float* sums3 = gather_only ? r.sums3 : w.sums3;
     launch_one(depth ? k_gather_view<true> : k_gather_view<false>, dim3((n + 63) / 64), 256, 0, s,
                gather_args(c, sums, sums3, depth));
     if (gather_only) {
@@ -6468,20 +6508,18 @@ static gr_status bwd_impl(const gr_view* v, int n, const gr_plan* plan, const fl
     }
     SBatch B;
     B.add(vk, w.sums, depth ? w.sums3 : nullptr);
-    return launch_reduce_sums(B, n, means, scales, colors, color_dim, opacities, d_means, d_scales, d_colors, d_opacities,
-                              accumulate, sum_index, true, s);
+    return launch_reduce_sums(B, n, r.params, g, r.sum_index, true, s);
   }
   if (gather_only) {  // no pair: every sum is zero
-    GR_HIP_TRY(hipMemsetAsync(g_sums, 0, gr_view_sums_floats(n) * sizeof(float), s));
-    if (g_sums3) GR_HIP_TRY(hipMemsetAsync(g_sums3, 0, (size_t)n * sizeof(float), s));
+    GR_HIP_TRY(hipMemsetAsync(r.sums, 0, gr_view_sums_floats(n) * sizeof(float), s));
+    if (r.sums3) GR_HIP_TRY(hipMemsetAsync(r.sums3, 0, (size_t)n * sizeof(float), s));
     GR_HIP_TRY(hipGetLastError());
     prof_mark(PROF_REDUCE, s);
     return GR_OK;
   }
   // No pair: every sum is zero, so the chain rule of an empty batch writes the result (the gradients are zero or the
   // accumulator unchanged, whatever the row: sum_index needs no mapping here)
-  return launch_reduce_sums(SBatch{}, n, means, scales, colors, color_dim, opacities, d_means, d_scales, d_colors,
-                            d_opacities, accumulate, nullptr, true, s);
+  return launch_reduce_sums(SBatch{}, n, r.params, g, nullptr, true, s);
 }
 
 extern "C" {
@@ -6490,8 +6528,13 @@ gr_status gr_bwd(const gr_view* v, int n, const gr_plan* plan, const float* mean
                  const float* colors, int color_dim, const float* opacities, const void* geom, const void* bins,
                  const float* saved, const float* g_rgb, const float* g_alpha, const float* g_depth, float* d_means,
                  float* d_scales, float* d_colors, float* d_opacities, void* ws, size_t ws_bytes, void* stream) {
-  return bwd_impl(v, n, plan, means, scales, colors, color_dim, opacities, geom, bins, saved, g_rgb, g_alpha, g_depth,
-                  nullptr, nullptr, 0.0f, 0.0f, nullptr, d_means, d_scales, d_colors, d_opacities, 0, ws, ws_bytes, stream);
+  BwdRequest r{v, n, plan, geom, bins, saved, ws, ws_bytes, stream};
+  r.params = {means, scales, colors, color_dim, opacities};
+  r.g_rgb = g_rgb;
+  r.g_alpha = g_alpha;
+  r.g_depth = g_depth;
+  r.grads = {d_means, d_scales, d_colors, d_opacities, 0};
+  return bwd_impl(r);
 }
 
 gr_status gr_bwd_indexed(const gr_view* v, int n, const gr_plan* plan, const float* means, const float* scales,
@@ -6499,9 +6542,14 @@ gr_status gr_bwd_indexed(const gr_view* v, int n, const gr_plan* plan, const flo
                          const float* saved, const float* g_rgb, const float* g_alpha, const float* g_depth,
                          const int* index, float* d_means, float* d_scales, float* d_colors, float* d_opacities, void* ws,
                          size_t ws_bytes, void* stream) {
-  return bwd_impl(v, n, plan, means, scales, colors, color_dim, opacities, geom, bins, saved, g_rgb, g_alpha, g_depth,
-                  nullptr, nullptr, 0.0f, 0.0f, nullptr, d_means, d_scales, d_colors, d_opacities, 0, ws, ws_bytes, stream,
-                  nullptr, 0.0f, index);
+  BwdRequest r{v, n, plan, geom, bins, saved, ws, ws_bytes, stream};
+  r.params = {means, scales, colors, color_dim, opacities};
+  r.g_rgb = g_rgb;
+  r.g_alpha = g_alpha;
+  r.g_depth = g_depth;
+  r.grads = {d_means, d_scales, d_colors, d_opacities, 0};
+  r.sum_index = index;
+  return bwd_impl(r);
 }
 
 gr_status gr_bwd_fit(const gr_view* v, int n, const gr_plan* plan, const float* means, const float* scales,
@@ -6511,9 +6559,11 @@ gr_status gr_bwd_fit(const gr_view* v, int n, const gr_plan* plan, const float* 
                      float* d_scales, float* d_colors, float* d_opacities, int accumulate, void* ws, size_t ws_bytes,
                      void* stream) {
   if (!target_rgb) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_bwd_fit: target_rgb is null");
-  return bwd_impl(v, n, plan, means, scales, colors, color_dim, opacities, geom, bins, saved, nullptr, nullptr, nullptr,
-                  target_rgb, target_mask, w_sil, g_scale, loss_out, d_means, d_scales, d_colors, d_opacities,
-                  accumulate, ws, ws_bytes, stream, target_depth, w_depth);
+  BwdRequest r{v, n, plan, geom, bins, saved, ws, ws_bytes, stream};
+  r.params = {means, scales, colors, color_dim, opacities};
+  r.loss = {target_rgb, target_mask, w_sil, target_depth, w_depth, g_scale, loss_out};
+  r.grads = {d_means, d_scales, d_colors, d_opacities, accumulate};
+  return bwd_impl(r);
 }
 
 gr_status gr_bwd_fit_gather(const gr_view* v, int n, const gr_plan* plan, const void* geom, const void* bins,
@@ -6522,9 +6572,11 @@ gr_status gr_bwd_fit_gather(const gr_view* v, int n, const gr_plan* plan, const 
                             size_t ws_bytes, float* sums, float* sums3, void* stream) {
   if (!target_rgb) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_bwd_fit_gather: target_rgb is null");
   if (!sums) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_bwd_fit_gather: sums is null");
-  return bwd_impl(v, n, plan, nullptr, nullptr, nullptr, 3, nullptr, geom, bins, saved, nullptr, nullptr, nullptr,
-                  target_rgb, target_mask, w_sil, g_scale, loss_out, nullptr, nullptr, nullptr, nullptr, 0, ws, ws_bytes,
-                  stream, target_depth, w_depth, nullptr, sums, sums3);
+  BwdRequest r{v, n, plan, geom, bins, saved, ws, ws_bytes, stream};
+  r.loss = {target_rgb, target_mask, w_sil, target_depth, w_depth, g_scale, loss_out};
+  r.sums = sums;
+  r.sums3 = sums3;
+  return bwd_impl(r);
 }
 
 size_t gr_bwd_ssim_bytes(const gr_view* v, int n, const gr_plan* plan) {
@@ -6540,9 +6592,13 @@ gr_status gr_bwd_fit_ssim(const gr_view* v, int n, const gr_plan* plan, const fl
   if (!target_rgb) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_bwd_fit_ssim: target_rgb is null");
   if (!(w_dssim >= 0.0f && w_dssim <= 1.0f))
     return set_error(GR_ERR_INVALID_ARGUMENT, "gr_bwd_fit_ssim: w_dssim must be in [0, 1]");
-  return bwd_impl(v, n, plan, means, scales, colors, color_dim, opacities, geom, bins, saved, nullptr, nullptr, nullptr,
-                  target_rgb, target_mask, w_sil, g_scale, loss_out, d_means, d_scales, d_colors, d_opacities,
-                  accumulate, ws, ws_bytes, stream, target_depth, w_depth, nullptr, nullptr, nullptr, w_dssim);
+  BwdRequest r{v, n, plan, geom, bins, saved, ws, ws_bytes, stream};
+  r.params = {means, scales, colors, color_dim, opacities};
+  r.loss = {target_rgb, target_mask, w_sil, target_depth, w_depth, g_scale, loss_out};
+  r.loss.ssim_entry = true;
+  r.loss.w_dssim = w_dssim;
+  r.grads = {d_means, d_scales, d_colors, d_opacities, accumulate};
+  return bwd_impl(r);
 }
 
 gr_status gr_bwd_fit_ssim_gather(const gr_view* v, int n, const gr_plan* plan, const void* geom, const void* bins,
@@ -6553,9 +6609,13 @@ gr_status gr_bwd_fit_ssim_gather(const gr_view* v, int n, const gr_plan* plan, c
   if (!sums) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_bwd_fit_ssim_gather: sums is null");
   if (!(w_dssim >= 0.0f && w_dssim <= 1.0f))
     return set_error(GR_ERR_INVALID_ARGUMENT, "gr_bwd_fit_ssim_gather: w_dssim must be in [0, 1]");
-  return bwd_impl(v, n, plan, nullptr, nullptr, nullptr, 3, nullptr, geom, bins, saved, nullptr, nullptr, nullptr,
-                  target_rgb, target_mask, w_sil, g_scale, loss_out, nullptr, nullptr, nullptr, nullptr, 0, ws, ws_bytes,
-                  stream, target_depth, w_depth, nullptr, sums, sums3, w_dssim);
+  BwdRequest r{v, n, plan, geom, bins, saved, ws, ws_bytes, stream};
+  r.loss = {target_rgb, target_mask, w_sil, target_depth, w_depth, g_scale, loss_out};
+  r.loss.ssim_entry = true;
+  r.loss.w_dssim = w_dssim;
+  r.sums = sums;
+  r.sums3 = sums3;
+  return bwd_impl(r);
 }
 
 gr_status gr_bwd_l1(const gr_view* v, int n, const gr_plan* plan, const float* means, const float* scales,
@@ -6564,9 +6624,15 @@ gr_status gr_bwd_l1(const gr_view* v, int n, const gr_plan* plan, const float* m
                     float* loss_out, float* d_means, float* d_scales, float* d_colors, float* d_opacities,
                     int accumulate, void* ws, size_t ws_bytes, void* stream) {
   if (!target_rgb) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_bwd_l1: target_rgb is null");
-  return bwd_impl(v, n, plan, means, scales, colors, color_dim, opacities, geom, bins, saved, nullptr, nullptr, nullptr,
-                  target_rgb, target_mask, w_sil, g_scale, loss_out, d_means, d_scales, d_colors, d_opacities,
-                  accumulate, ws, ws_bytes, stream);
+  BwdRequest r{v, n, plan, geom, bins, saved, ws, ws_bytes, stream};
+  r.params = {means, scales, colors, color_dim, opacities};
+  r.loss.t_rgb = target_rgb;
+  r.loss.t_mask = target_mask;
+  r.loss.w_sil = w_sil;
+  r.loss.g_scale = g_scale;
+  r.loss.loss_out = loss_out;
+  r.grads = {d_means, d_scales, d_colors, d_opacities, accumulate};
+  return bwd_impl(r);
 }
 
 // gr_fit_views_batched: the fused fit path's per-view chain for several views, one launch per kernel (vb_add of the
@@ -6638,7 +6704,8 @@ gr_status gr_fit_views_batched(int num_views, const gr_batch_view* bv, int n, fl
     for (int j = 0; j < num_views; ++j) {
       const gr_batch_view& b = bv[j];
       const ViewCtx& c = ctx[j];
-      L1Args la = fit_l1_args(c, b.target_rgb, b.target_mask, w_sil, g_scale, b.loss);
+      // (a view of this path has no depth target)
+      L1Args la = fit_l1_args(c, {b.target_rgb, b.target_mask, w_sil, b.target_depth, w_depth, g_scale, b.loss});
       la.pieces = 2;
       const int cap = (int)c.cap;
       if (c.tc.T == T32) {
@@ -6668,11 +6735,10 @@ gr_status gr_fit_views_batched(int num_views, const gr_batch_view* bv, int n, fl
     const gr_batch_view& b = bv[j];
     const ViewCtx& c = ctx[j];
     const int cap = (int)c.cap;
-    const L1Args none{nullptr, nullptr, 0.f, 0.f, nullptr};
-    vb_add(Bf, fwd_mfma_args(c, nullptr, nullptr, nullptr, b.saved, none, nullptr), cap);
+    vb_add(Bf, fwd_mfma_args(c, nullptr, nullptr, nullptr, b.saved, fit_l1_args(c, ViewLoss{}), nullptr), cap);
     vb_add(Bm, depth_tile_max_args(c, b.saved), tiles);
     vb_add(Bd, depth_tile_sums_args(c, b.saved, b.target_depth, w_depth, g_scale), tiles);
-    const L1Args l1 = fit_l1_args(c, b.target_rgb, b.target_mask, w_sil, g_scale, b.loss, b.target_depth, w_depth);
+    const L1Args l1 = fit_l1_args(c, {b.target_rgb, b.target_mask, w_sil, b.target_depth, w_depth, g_scale, b.loss});
     vb_add(Bu, pixel_grads_args(c, b.saved, nullptr, nullptr, nullptr, 3, l1, true), tiles);
     vb_add(Bb, bwd_bf16_args(c, c.depth3()), cap);
     vb_add(Bg, gather_args(c, b.sums, b.sums3, true), (n + 63) / 64);
@@ -6796,8 +6862,8 @@ gr_status gr_reduce_sums(int num_views, const gr_sums_view* views, int n, const 
   SBatch B;
   if (gr_status st = sums_batch("gr_reduce_sums", num_views, views, false, B); st != GR_OK) return st;
   if (GR_DEBUG_SKIP & 8) return GR_OK;
-  return launch_reduce_sums(B, n, means, scales, colors, color_dim, opacities, d_means, d_scales, d_colors, d_opacities,
-                            accumulate, nullptr, false, (hipStream_t)stream);
+  return launch_reduce_sums(B, n, {means, scales, colors, color_dim, opacities},
+                            {d_means, d_scales, d_colors, d_opacities, accumulate}, nullptr, false, (hipStream_t)stream);
 }
 
 gr_status gr_density_stats(int num_views, const gr_sums_view* views, int n, const float* means, const float* scales,
@@ -6841,7 +6907,7 @@ gr_status gr_camera_grads_sums(int num_views, const gr_sums_view* views, int n, 
   if (gr_status st = sums_batch("gr_camera_grads_sums", num_views, views, false, B); st != GR_OK) return st;
   if (ws_bytes < gr_camera_grads_ws_bytes(n, num_views))
     return set_error(GR_ERR_WORKSPACE, "gr_camera_grads_sums: workspace too small");
-  return launch_camera_grads(B, n, means, scales, colors, color_dim, opacities, d_camera, (double*)ws, false, s);
+  return launch_camera_grads(B, n, {means, scales, colors, color_dim, opacities}, d_camera, (double*)ws, false, s);
 }
 
 gr_status gr_bwd_camera(const gr_view* v, int n, const gr_plan* plan, const float* means, const float* scales,
@@ -6865,7 +6931,7 @@ gr_status gr_bwd_camera(const gr_view* v, int n, const gr_plan* plan, const floa
   const BwdWs w = bwd_ws(v, n, plan, ws);  // cam_part: the one-view workspace, gr_camera_grads_ws_bytes(n, 1)
   SBatch B;
   B.add(make_viewk(v), w.sums, depth ? w.sums3 : nullptr);
-  return launch_camera_grads(B, n, means, scales, colors, color_dim, opacities, &d_camera, w.cam_part, true, s);
+  return launch_camera_grads(B, n, {means, scales, colors, color_dim, opacities}, &d_camera, w.cam_part, true, s);
 }
 
 gr_status gr_render_u8(const gr_render_params* p, int n, const float* means, const float* scales, const float* colors,

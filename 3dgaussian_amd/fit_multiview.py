@@ -733,6 +733,12 @@ class ViewShardedFitter:
             raise ValueError(f"density_stats on {device}: the statistics come from the fused fit path only, which "
                              f"this fit does not take: {why}")
 
+    def _loss_terms(self, depth: bool, ssim: bool = False) -> tuple:
+        """A step's loss terms (w_sil, w_depth, g_scale, w_dssim) as every view path passes them on: the silhouette
+        weight only with masks, the depth weight only with a depth term, the D-SSIM weight only in the D-SSIM form."""
+        w_sil = self.w_sil if (self.masks is not None and self.w_sil > 0.0) else 0.0
+        return w_sil, (self.w_depth if depth else 0.0), 1.0 / len(self.targets), (self.w_dssim if ssim else 0.0)
+
     def _inv_g_scale(self) -> float:
         """1 / g_scale of a step in float32, as gr_fit_views forms it: the schedules' statistics agree bit for bit."""
         return float(np.float32(1.0) / np.float32(1.0 / len(self.targets)))
@@ -1546,7 +1552,7 @@ class ViewShardedFitter:
             self._acc_parts = [tuple(torch.zeros_like(t) for t in (m, s, c, o))]
             return torch.zeros((), device=device)
         ns = max(1, min(NUM_STREAMS, len(views)))
-        w_sil = self.w_sil if (self.masks is not None and self.w_sil > 0.0) else 0.0
+        w_sil, w_depth, g_scale, w_dssim = self._loss_terms(depth, ssim)
         key = (tuple(views), depth, F32_GRADE, w_sil > 0.0, str(device), sized is not None, ssim)
         cache = self._native_targets
         if cache is None or cache[0] != key:
@@ -1565,7 +1571,7 @@ class ViewShardedFitter:
         L = tr._native.lib()
         head = (tr._native.executor(device.index or 0), ctypes.byref(cfg), len(views), cache[1], int(m.shape[0]),
                 tr._native.ptr(m), tr._native.ptr(s), tr._native.ptr(c), tr._color_dim(c), tr._native.ptr(o),
-                ctypes.c_float(w_sil), ctypes.c_float(self.w_depth), ctypes.c_float(1.0 / len(self.targets)))
+                ctypes.c_float(w_sil), ctypes.c_float(w_depth), ctypes.c_float(g_scale))
         tail = (tr._native.ptr(losses_v), ptrs, ctypes_stream(device))
         if self.density_stats:  # the executor enqueues gr_density_stats beside each gr_reduce_sums of this call
             sp = (ctypes.c_void_p * ns)(*[b.data_ptr() for b in self._stats_bufs(ns, device)])
@@ -1575,7 +1581,7 @@ class ViewShardedFitter:
                              "gr_executor_camera_grads")
         try:
             if ssim:
-                tr._native.check(L.gr_fit_views_ssim(*head, ctypes.c_float(self.w_dssim), *tail), "gr_fit_views_ssim")
+                tr._native.check(L.gr_fit_views_ssim(*head, ctypes.c_float(w_dssim), *tail), "gr_fit_views_ssim")
             else:
                 tr._native.check(L.gr_fit_views(*head, *tail), "gr_fit_views")
         finally:
@@ -1634,9 +1640,8 @@ class ViewShardedFitter:
         stats = self._stats_bufs(ns, device) if self.density_stats else None
         if self.refine_cameras:
             self._camera_rows(nv, device)
-        w_sil = self.w_sil if (self.masks is not None and self.w_sil > 0.0) else 0.0
-        g_scale = 1.0 / len(self.targets)
         depth = form == "depth" or (form == "ssim" and self._depth_grad())
+        w_sil, w_depth, g_scale, w_dssim = self._loss_terms(depth, form == "ssim")
         bin_stream = None
         if form == "l1" and BIN_STREAM != "":
             if self._bin is None or self._bin.device != device:
@@ -1662,14 +1667,12 @@ class ViewShardedFitter:
             pv = take(j)
             _, _, _, rs = tr.forward_native(m, s, c, o, pv.gv, pv, images=False)  # the backward reads the sums
             pv = None
-            mask = self.masks[i] if w_sil > 0.0 else None
-            if form == "ssim":
-                sums, sums3 = tr.backward_fit_ssim_gather_native(
-                    rs, self.targets[i], mask, w_sil, self.depths[i] if depth else None, self.w_depth if depth else 0.0,
-                    g_scale, self.w_dssim, losses_v[j:j + 1])
-            else:
-                sums, sums3 = tr.backward_fit_gather_native(rs, self.targets[i], mask, w_sil, self.depths[i], self.w_depth,
-                                                            g_scale, losses_v[j:j + 1])
+            # the two entries take the same operands, the D-SSIM one its weight behind g_scale
+            ssim = form == "ssim"
+            gather = tr.backward_fit_ssim_gather_native if ssim else tr.backward_fit_gather_native
+            own = (w_dssim,) if ssim else ()
+            sums, sums3 = gather(rs, self.targets[i], self.masks[i] if w_sil > 0.0 else None, w_sil,
+                                 self.depths[i] if depth else None, w_depth, g_scale, *own, losses_v[j:j + 1])
             return (rs.gv, sums, sums3) if sums3 is not None else (rs.gv, sums)
 
         gathered = GATHER or form != "l1"
@@ -2043,8 +2046,7 @@ class ViewShardedFitter:
         n = int(m.shape[0])
         views = self.my_views
         depth = self._depth_grad()
-        w_sil = self.w_sil if (self.masks is not None and self.w_sil > 0.0) else 0.0
-        g_scale = 1.0 / len(self.targets)
+        w_sil, w_depth, g_scale, _ = self._loss_terms(depth)
         bkey = (n, depth, tuple((int(cp.num_pairs), int(cp.num_core_pairs)) for cp in gs.caps), str(device))
         bw = getattr(gs, "batch_ws", None)
         if bw is None or bw[0] != bkey:
@@ -2098,7 +2100,7 @@ class ViewShardedFitter:
                 e.target_depth = self.depths[i].data_ptr() if depth else None
                 e.sums, e.sums3 = w["sums"].data_ptr(), (w["sums3"].data_ptr() if depth else None)
                 e.loss = losses_v[q:q + 1].data_ptr()
-            nat.check(L.gr_fit_views_batched(len(js), arr, n, ctypes.c_float(w_sil), ctypes.c_float(self.w_depth if depth else 0.0),
+            nat.check(L.gr_fit_views_batched(len(js), arr, n, ctypes.c_float(w_sil), ctypes.c_float(w_depth),
                                              ctypes.c_float(g_scale), stream), "gr_fit_views_batched")
         for k, sizes in enumerate(_batch_sizes(ns, len(views), tail=0)):
             mine = list(range(k, len(views), ns))

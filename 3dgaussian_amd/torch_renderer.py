@@ -512,35 +512,66 @@ def forward_native(means, scales, colors, opacities, gv: _native.GrView, prepare
     return out, alpha, depth, RenderState(gv, n, plan, geom, bins, saved)
 
 
+def _bwd_ws(L, gv: _native.GrView, n: int, plan, dev, ssim: bool = False) -> torch.Tensor:
+    """A view's backward workspace: gr_bwd_bytes, or with ``ssim`` the D-SSIM entries' gr_bwd_ssim_bytes."""
+    size = L.gr_bwd_ssim_bytes if ssim else L.gr_bwd_bytes
+    return torch.empty((_ws_round(size(ctypes.byref(gv), n, ctypes.byref(plan))),), dtype=torch.uint8, device=dev)
+
+
+def _check_targets(gv: _native.GrView, target, mask, depth_target, dev) -> None:
+    """A view loss's operands (mask and depth_target may be None), read through their raw pointers."""
+    hw = (gv.height, gv.width)
+    _check_operand(target, hw + (3,), "target", dev)
+    _check_operand(mask, hw, "mask", dev)
+    _check_operand(depth_target, hw, "depth_target", dev)
+
+
+def _view_loss(target, mask, w_sil: float, g_scale: float, loss_out, depth=None, w_dssim=None) -> list:
+    """The view-loss group of a backward entry, in the ABI's order: ``depth`` = (depth_target, w_depth) for the entries
+    with a depth term, ``w_dssim`` for the D-SSIM entries."""
+    f = ctypes.c_float
+    return ([_native.ptr(target), _native.ptr(mask), f(w_sil)]
+            + ([_native.ptr(depth[0]), f(depth[1])] if depth is not None else [])
+            + [f(g_scale)] + ([f(w_dssim)] if w_dssim is not None else []) + [_native.ptr(loss_out)])
+
+
+def _backward_call(entry: str, st: RenderState, dev, loss: list, params=None, grads=None, accumulate=None, index=None,
+                   sums=None) -> torch.Tensor:
+    """Call the backward entry ``entry`` on the current stream with its arguments in the ABI's group order (gr_hip.h):
+    view / n / plan, the parameters, the render state, ``loss`` (the upstream gradients or _view_loss), the index, the
+    gradients (and ``accumulate``), the workspace, the gathered sums, the stream; a group the entry does not have is
+    None.  Returns the workspace it allocated."""
+    L = _native.lib()
+    ws = _bwd_ws(L, st.gv, st.n, st.plan, dev, ssim="ssim" in entry)
+    args = [ctypes.byref(st.gv), st.n, ctypes.byref(st.plan)]
+    if params is not None:
+        means, scales, colors, opacities = params
+        args += [_native.ptr(means), _native.ptr(scales), _native.ptr(colors), _color_dim(colors), _native.ptr(opacities)]
+    args += [_native.ptr(st.geom), _native.ptr(st.bins), _native.ptr(st.saved)] + loss
+    if index is not None:
+        args.append(_native.ptr(index))
+    if grads is not None:
+        args += [_native.ptr(g) for g in grads]
+    if accumulate is not None:
+        args.append(1 if accumulate else 0)
+    args += [_native.ptr(ws), ws.numel()]
+    if sums is not None:
+        args += [_native.ptr(t) for t in sums]
+    _native.check(getattr(L, entry)(*args, _stream(dev)), entry)
+    return ws
+
+
 def backward_native(means, scales, colors, opacities, st: RenderState, g_out, g_alpha, g_depth, want_ws: bool = False,
                     index=None):
     """Run gr_bwd.  Returns (d_means, d_scales, d_colors, d_opacities) (+ the backward workspace with
     ``want_ws``: it holds the per-Gaussian sums camera_grad_native reads).  ``index`` (int32 device, n): the
     render was of a permuted copy; means .. opacities and the gradients are in the caller's order and index[r] is
     the rendered position of the caller's row r (gr_bwd_indexed)."""
-    L = _native.lib()
-    dev = means.device
-    cd = _color_dim(colors)
-    ws = torch.empty((_ws_round(L.gr_bwd_bytes(ctypes.byref(st.gv), st.n, ctypes.byref(st.plan))),), dtype=torch.uint8,
-                     device=dev)
-    dm = torch.empty_like(means)
-    ds = torch.empty_like(scales)
-    dc = torch.empty_like(colors)
-    do = torch.empty_like(opacities)
-    if index is None:
-        _native.check(L.gr_bwd(ctypes.byref(st.gv), st.n, ctypes.byref(st.plan), _native.ptr(means), _native.ptr(scales),
-                               _native.ptr(colors), cd, _native.ptr(opacities), _native.ptr(st.geom), _native.ptr(st.bins),
-                               _native.ptr(st.saved), _native.ptr(g_out), _native.ptr(g_alpha), _native.ptr(g_depth),
-                               _native.ptr(dm), _native.ptr(ds), _native.ptr(dc), _native.ptr(do), _native.ptr(ws),
-                               ws.numel(), _stream(dev)), "gr_bwd")
-    else:
-        _native.check(L.gr_bwd_indexed(ctypes.byref(st.gv), st.n, ctypes.byref(st.plan), _native.ptr(means),
-                                       _native.ptr(scales), _native.ptr(colors), cd, _native.ptr(opacities),
-                                       _native.ptr(st.geom), _native.ptr(st.bins), _native.ptr(st.saved), _native.ptr(g_out),
-                                       _native.ptr(g_alpha), _native.ptr(g_depth), _native.ptr(index), _native.ptr(dm),
-                                       _native.ptr(ds), _native.ptr(dc), _native.ptr(do), _native.ptr(ws), ws.numel(),
-                                       _stream(dev)), "gr_bwd_indexed")
-    return (dm, ds, dc, do, ws) if want_ws else (dm, ds, dc, do)
+    params = (means, scales, colors, opacities)
+    grads = tuple(torch.empty_like(t) for t in params)
+    ws = _backward_call("gr_bwd" if index is None else "gr_bwd_indexed", st, means.device,
+                        [_native.ptr(g_out), _native.ptr(g_alpha), _native.ptr(g_depth)], params, grads, index=index)
+    return (*grads, ws) if want_ws else grads
 
 
 def camera_grad_native(means, scales, colors, opacities, st: RenderState, ws, depth: bool) -> torch.Tensor:
@@ -579,39 +610,22 @@ def backward_l1_native(means, scales, colors, opacities, st: RenderState, target
     ``mean|out - target| + w_sil mean|alpha - mask|`` (mask may be None) scaled by ``g_scale``, written
     (accumulate=False) or added (accumulate=True) into ``grads`` = (d_means, d_scales, d_colors,
     d_opacities); the unscaled view loss goes to the 0-d / 1-element device tensor ``loss_out``."""
-    L = _native.lib()
     dev = means.device
-    ws = torch.empty((_ws_round(L.gr_bwd_bytes(ctypes.byref(st.gv), st.n, ctypes.byref(st.plan))),), dtype=torch.uint8,
-                     device=dev)
-    dm, ds, dc, do = grads
-    _native.check(L.gr_bwd_l1(ctypes.byref(st.gv), st.n, ctypes.byref(st.plan), _native.ptr(means), _native.ptr(scales),
-                              _native.ptr(colors), _color_dim(colors), _native.ptr(opacities), _native.ptr(st.geom),
-                              _native.ptr(st.bins), _native.ptr(st.saved), _native.ptr(target), _native.ptr(mask),
-                              ctypes.c_float(w_sil), ctypes.c_float(g_scale), _native.ptr(loss_out), _native.ptr(dm),
-                              _native.ptr(ds), _native.ptr(dc), _native.ptr(do), 1 if accumulate else 0,
-                              _native.ptr(ws), ws.numel(), _stream(dev)), "gr_bwd_l1")
+    _check_params(means, scales, colors, opacities)
+    _check_targets(st.gv, target, mask, None, dev)
+    _backward_call("gr_bwd_l1", st, dev, _view_loss(target, mask, w_sil, g_scale, loss_out),
+                   (means, scales, colors, opacities), grads, accumulate)
 
 
 def backward_fit_native(means, scales, colors, opacities, st: RenderState, target, mask, w_sil: float, depth_target,
                         w_depth: float, g_scale: float, loss_out, grads, accumulate: bool) -> None:
     """gr_bwd_fit on the current stream: as ``backward_l1_native`` with the fit loop's depth term
     ``w_depth mean|depth / (max(depth) + 1e-6) - depth_target|`` (the view rendered with depth_grad=True)."""
-    L = _native.lib()
     dev = means.device
     _check_params(means, scales, colors, opacities)
-    _check_operand(target, (st.gv.height, st.gv.width, 3), "target", dev)
-    _check_operand(mask, (st.gv.height, st.gv.width), "mask", dev)
-    _check_operand(depth_target, (st.gv.height, st.gv.width), "depth_target", dev)
-    ws = torch.empty((_ws_round(L.gr_bwd_bytes(ctypes.byref(st.gv), st.n, ctypes.byref(st.plan))),), dtype=torch.uint8,
-                     device=dev)
-    dm, ds, dc, do = grads
-    _native.check(L.gr_bwd_fit(ctypes.byref(st.gv), st.n, ctypes.byref(st.plan), _native.ptr(means), _native.ptr(scales),
-                               _native.ptr(colors), _color_dim(colors), _native.ptr(opacities), _native.ptr(st.geom),
-                               _native.ptr(st.bins), _native.ptr(st.saved), _native.ptr(target), _native.ptr(mask),
-                               ctypes.c_float(w_sil), _native.ptr(depth_target), ctypes.c_float(w_depth),
-                               ctypes.c_float(g_scale), _native.ptr(loss_out), _native.ptr(dm), _native.ptr(ds),
-                               _native.ptr(dc), _native.ptr(do), 1 if accumulate else 0, _native.ptr(ws), ws.numel(),
-                               _stream(dev)), "gr_bwd_fit")
+    _check_targets(st.gv, target, mask, depth_target, dev)
+    _backward_call("gr_bwd_fit", st, dev, _view_loss(target, mask, w_sil, g_scale, loss_out, (depth_target, w_depth)),
+                   (means, scales, colors, opacities), grads, accumulate)
 
 
 def _check_operand(t, shape, name: str, dev) -> None:
@@ -665,11 +679,10 @@ def forward_l1_native(means, scales, colors, opacities, gv: _native.GrView, prep
         _check_operand(out, (gv.height, gv.width, 3), "out", dev)
     if alpha is not None:
         _check_operand(alpha, (gv.height, gv.width), "alpha", dev)
-    _check_operand(target, (gv.height, gv.width, 3), "target", dev)
-    _check_operand(mask, (gv.height, gv.width), "mask", dev)
+    _check_targets(gv, target, mask, None, dev)
     plan = prepared.plan()
     bins, scratch, rv = _bin_ahead(L, gv, n, plan, prepared, bin_stream, dev)
-    ws = torch.empty((_ws_round(L.gr_bwd_bytes(ctypes.byref(gv), n, ctypes.byref(plan))),), dtype=torch.uint8, device=dev)
+    ws = _bwd_ws(L, gv, n, plan, dev)
     _native.check(L.gr_fwd_render_l1(ctypes.byref(rv), n, ctypes.byref(plan), _native.ptr(prepared.geom),
                                      _native.ptr(bins), bins.numel(), _native.ptr(scratch), scratch.numel(),
                                      _native.ptr(target), _native.ptr(mask), ctypes.c_float(w_sil), ctypes.c_float(g_scale),
@@ -733,26 +746,18 @@ def backward_fit_gather_native(st: RenderState, target, mask, w_sil: float, dept
     """gr_bwd_fit_gather on the current stream: the depth-loss backward of a view rendered with depth_grad=True up to
     its per-Gaussian sums; returns (sums (n, 8), depth sums (n,)) for reduce_sums_native (the view's geom, bins and
     saved sums are free after it)."""
-    L = _native.lib()
+    return _backward_gather("gr_bwd_fit_gather", st, target, mask, depth_target,
+                            _view_loss(target, mask, w_sil, g_scale, loss_out, (depth_target, w_depth)), True)
+
+
+def _backward_gather(entry: str, st: RenderState, target, mask, depth_target, loss: list, want_sums3: bool):
+    """A gather entry: the view's backward up to (sums (n, 8), depth sums (n,) or None), which it allocates."""
     dev = st.saved.device
-    _check_operand(target, (st.gv.height, st.gv.width, 3), "target", dev)
-    _check_operand(mask, (st.gv.height, st.gv.width), "mask", dev)
-    _check_operand(depth_target, (st.gv.height, st.gv.width), "depth_target", dev)
-    ws = torch.empty((_ws_round(L.gr_bwd_bytes(ctypes.byref(st.gv), st.n, ctypes.byref(st.plan))),), dtype=torch.uint8,
-                     device=dev)
+    _check_targets(st.gv, target, mask, depth_target, dev)
     sums = torch.empty((st.n, 8), dtype=torch.float32, device=dev)
-    sums3 = torch.empty((st.n,), dtype=torch.float32, device=dev)
-    _native.check(L.gr_bwd_fit_gather(ctypes.byref(st.gv), st.n, ctypes.byref(st.plan), _native.ptr(st.geom),
-                                      _native.ptr(st.bins), _native.ptr(st.saved), _native.ptr(target), _native.ptr(mask),
-                                      ctypes.c_float(w_sil), _native.ptr(depth_target), ctypes.c_float(w_depth),
-                                      ctypes.c_float(g_scale), _native.ptr(loss_out), _native.ptr(ws), ws.numel(),
-                                      _native.ptr(sums), _native.ptr(sums3), _stream(dev)), "gr_bwd_fit_gather")
+    sums3 = torch.empty((st.n,), dtype=torch.float32, device=dev) if want_sums3 else None
+    _backward_call(entry, st, dev, loss, sums=(sums, sums3))
     return sums, sums3
-
-
-def _ssim_ws(L, st: RenderState, dev) -> torch.Tensor:
-    return torch.empty((_ws_round(L.gr_bwd_ssim_bytes(ctypes.byref(st.gv), st.n, ctypes.byref(st.plan))),),
-                       dtype=torch.uint8, device=dev)
 
 
 def backward_fit_ssim_native(means, scales, colors, opacities, st: RenderState, target, mask, w_sil: float, depth_target,
@@ -761,21 +766,12 @@ def backward_fit_ssim_native(means, scales, colors, opacities, st: RenderState, 
     + l dssim(out, target) + w_sil mean|alpha - mask| (+ the depth term)``, l = ``w_dssim`` in [0, 1]: the D-SSIM
     forward from the saved sums and its backward fused with the upstream pass, no image and no gradient image
     (``mask`` / ``depth_target`` may be None; a depth target needs the view rendered with depth_grad=True)."""
-    L = _native.lib()
     dev = means.device
     _check_params(means, scales, colors, opacities)
-    _check_operand(target, (st.gv.height, st.gv.width, 3), "target", dev)
-    _check_operand(mask, (st.gv.height, st.gv.width), "mask", dev)
-    _check_operand(depth_target, (st.gv.height, st.gv.width), "depth_target", dev)
-    ws = _ssim_ws(L, st, dev)
-    dm, ds, dc, do = grads
-    _native.check(L.gr_bwd_fit_ssim(ctypes.byref(st.gv), st.n, ctypes.byref(st.plan), _native.ptr(means), _native.ptr(scales),
-                                    _native.ptr(colors), _color_dim(colors), _native.ptr(opacities), _native.ptr(st.geom),
-                                    _native.ptr(st.bins), _native.ptr(st.saved), _native.ptr(target), _native.ptr(mask),
-                                    ctypes.c_float(w_sil), _native.ptr(depth_target), ctypes.c_float(w_depth),
-                                    ctypes.c_float(g_scale), ctypes.c_float(w_dssim), _native.ptr(loss_out),
-                                    _native.ptr(dm), _native.ptr(ds), _native.ptr(dc), _native.ptr(do),
-                                    1 if accumulate else 0, _native.ptr(ws), ws.numel(), _stream(dev)), "gr_bwd_fit_ssim")
+    _check_targets(st.gv, target, mask, depth_target, dev)
+    _backward_call("gr_bwd_fit_ssim", st, dev,
+                   _view_loss(target, mask, w_sil, g_scale, loss_out, (depth_target, w_depth), w_dssim),
+                   (means, scales, colors, opacities), grads, accumulate)
 
 
 def backward_fit_ssim_gather_native(st: RenderState, target, mask, w_sil: float, depth_target, w_depth: float,
@@ -783,21 +779,9 @@ def backward_fit_ssim_gather_native(st: RenderState, target, mask, w_sil: float,
     """gr_bwd_fit_ssim_gather on the current stream: ``backward_fit_ssim_native`` up to the view's per-Gaussian sums;
     returns (sums (n, 8), depth sums (n,) or None without a depth target) for reduce_sums_native (the view's geom,
     bins and saved sums are free after it)."""
-    L = _native.lib()
-    dev = st.saved.device
-    _check_operand(target, (st.gv.height, st.gv.width, 3), "target", dev)
-    _check_operand(mask, (st.gv.height, st.gv.width), "mask", dev)
-    _check_operand(depth_target, (st.gv.height, st.gv.width), "depth_target", dev)
-    ws = _ssim_ws(L, st, dev)
-    sums = torch.empty((st.n, 8), dtype=torch.float32, device=dev)
-    sums3 = torch.empty((st.n,), dtype=torch.float32, device=dev) if depth_target is not None else None
-    _native.check(L.gr_bwd_fit_ssim_gather(ctypes.byref(st.gv), st.n, ctypes.byref(st.plan), _native.ptr(st.geom),
-                                           _native.ptr(st.bins), _native.ptr(st.saved), _native.ptr(target),
-                                           _native.ptr(mask), ctypes.c_float(w_sil), _native.ptr(depth_target),
-                                           ctypes.c_float(w_depth), ctypes.c_float(g_scale), ctypes.c_float(w_dssim),
-                                           _native.ptr(loss_out), _native.ptr(ws), ws.numel(), _native.ptr(sums),
-                                           _native.ptr(sums3), _stream(dev)), "gr_bwd_fit_ssim_gather")
-    return sums, sums3
+    return _backward_gather("gr_bwd_fit_ssim_gather", st, target, mask, depth_target,
+                            _view_loss(target, mask, w_sil, g_scale, loss_out, (depth_target, w_depth), w_dssim),
+                            depth_target is not None)
 
 
 def _sums_views(batch, n: int, dev):
