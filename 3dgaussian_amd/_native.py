@@ -114,8 +114,9 @@ class GrFitConfig(ctypes.Structure):
                 ("caps", ctypes.POINTER(GrPlan)), ("observed", ctypes.c_void_p), ("overflow", ctypes.c_void_p)]
 
 
-FIT_MAX_ACC = 8      # GR_FIT_MAX_ACC
+FIT_MAX_ACC = 8      # GR_FIT_MAX_ACC: the stream accumulators one parameter step sums
 FIT_MAX_PARAMS = 8   # GR_FIT_MAX_PARAMS
+ACT_IDENTITY, ACT_SOFTPLUS, ACT_SIGMOID = 0, 1, 2  # GR_ACT_*: the activation whose backward a parameter step applies
 
 
 class GrParamStep(ctypes.Structure):

@@ -5293,74 +5293,42 @@ __global__ __launch_bounds__(256) void k_ssim_pixel_grads(ViewK v, const float4*
                          l1.w_dssim, l1.loss_out, reinterpret_cast<double (*)[256]>(&tm[0][0]));
 }
 
-// The fit loop's parameter update (fit_multiview_stub.py:268-275 activations, :307-308 regulariser,
-// :311 Adam) for one parameter tensor, fused into one pass over its elements (gr_fit_param_step):
+// The fit loop's parameter update (fit_multiview_stub.py:268-275 activations, :307-308 regulariser, :311 Adam), fused
+// into one pass over a parameter tensor's elements.  Its arithmetic is stated once, in the two routines below:
 //   g_raw = act'(raw) * (((acc0 + acc1) + ...) + reg)     d loss / d raw parameter (torch's backward of
 //                                                         softplus(x) + 1e-3 / sigmoid / identity)
-//   then, with Adam, torch.optim.Adam's foreach update in its own operation order:
+//   then, with Adam, torch.optim.Adam's update in its own operation order:
 //   m = m + (1 - b1)(g - m); v = v b2 + ((1 - b2) g) g; p = p + step_size m / (sqrt(v) / bc2_sqrt + eps).
-// act: 0 identity, 1 softplus (threshold 20, as torch), 2 sigmoid.
-struct AccList {
-  const float* p[GR_FIT_MAX_ACC];
-  int n;
-};
-__global__ __launch_bounds__(256) void k_fit_param_step(int64_t count, int act, float* __restrict__ p,
-                                                        float* __restrict__ grad, AccList acc, float reg, int adam, float* __restrict__ m, float* __restrict__ v,
-                                                        float neg_step, float bc2_sqrt, float b1, float b2, float b2_c,
-                                                        float eps) {
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < count; e += (int64_t)gridDim.x * 256) {
-    float gact = acc.n > 0 ? acc.p[0][e] : 0.0f;
-    for (int a = 1; a < acc.n; ++a) gact = gact + acc.p[a][e];  // in stream order
-    gact = gact + reg;
-    const float x = p[e];
-    float g;
-    if (act == 1) {  // softplus backward: g z / (z + 1), z = exp(x) (x <= 20), else g
-      const float z = expf(x);
-      g = x > 20.0f ? gact : gact * z / (z + 1.0f);
-    } else if (act == 2) {  // sigmoid backward: g (1 - y) y
-      const float y = 1.0f / (1.0f + expf(-x));
-      g = gact * (1.0f - y) * y;
-    } else {
-      g = gact;
-    }
-    if (grad) grad[e] = g;
-    if (adam) {  // b1 here is 1 - beta1 and b2 is (beta2, 1 - beta2) rounded from double on the host, as torch's scalars
-      const float mm = fmaf(b1, g - m[e], m[e]);
-      const float vv = fmaf(b2_c, g * g, v[e] * b2);
-      m[e] = mm;
-      v[e] = vv;
-      p[e] = fmaf(neg_step, mm / (sqrtf(vv) / bc2_sqrt + eps), x);
-    }
-  }
-}
-
-// k_fit_param_step over several parameter tensors (gr_fit_param_steps): block b belongs to the tensor whose block
-// range [first[t], first[t + 1]) holds it and grid-strides over that tensor alone.
-struct ParamSteps {
-  gr_param_step s[GR_FIT_MAX_PARAMS];
-  int first[GR_FIT_MAX_PARAMS + 1];
-  int vec4[GR_FIT_MAX_PARAMS];  // 1: count % 4 == 0 and every array 16-byte aligned (float4 loads and stores)
-  int num;
-};
-// One element of k_fit_param_steps: the activation's backward on the summed gradient, then Adam (torch's
-// single-tensor update order).  Returns the gradient; m, v and x are updated in place.
-__device__ __forceinline__ float fit_param_elem(int act, float gact, float& x, float& m, float& v, float neg_step,
-                                                float bc2s, float b1, float b2, float b2_c, float eps) {
-  float g;
-  if (act == 1) {  // softplus backward: g z / (z + 1), z = exp(x) (x <= 20), else g
+// The activation's backward on gact, the summed upstream gradient plus the regulariser's (softplus: threshold 20, as torch).
+__device__ __forceinline__ float act_backward(int act, float gact, float x) {
+  if (act == GR_ACT_SOFTPLUS) {  // g z / (z + 1), z = exp(x) (x <= 20), else g
     const float z = expf(x);
-    g = x > 20.0f ? gact : gact * z / (z + 1.0f);
-  } else if (act == 2) {  // sigmoid backward: g (1 - y) y
-    const float y = 1.0f / (1.0f + expf(-x));
-    g = gact * (1.0f - y) * y;
-  } else {
-    g = gact;
+    return x > 20.0f ? gact : gact * z / (z + 1.0f);
   }
+  if (act == GR_ACT_SIGMOID) {  // g (1 - y) y
+    const float y = 1.0f / (1.0f + expf(-x));
+    return gact * (1.0f - y) * y;
+  }
+  return gact;
+}
+// One element of Adam, x, m and v updated in place.  b1 is 1 - beta1 and (b2, b2_c) are (beta2, 1 - beta2), rounded from
+// double on the host as torch's Python-float scalars are.
+__device__ __forceinline__ void adam_elem(float g, float& x, float& m, float& v, float neg_step, float bc2s, float b1,
+                                          float b2, float b2_c, float eps) {
   m = fmaf(b1, g - m, m);
   v = fmaf(b2_c, g * g, v * b2);
   x = fmaf(neg_step, m / (sqrtf(v) / bc2s + eps), x);
-  return g;
 }
+
+// The parameter tensors of one k_fit_param_steps launch: block b belongs to the tensor whose block range
+// [first[t], first[t + 1]) holds it and grid-strides over that tensor alone.
+struct ParamSteps {
+  gr_param_step s[GR_FIT_MAX_PARAMS];
+  int first[GR_FIT_MAX_PARAMS + 1] = {0};
+  int vec4[GR_FIT_MAX_PARAMS];  // 1: count % 4 == 0 and every array 16-byte aligned (float4 loads and stores)
+  int adam[GR_FIT_MAX_PARAMS];  // 0: the gradient alone (exp_avg / exp_avg_sq are not read and may be null)
+  int num = 0;
+};
 // sched (gr_fit_param_steps_sched): the step's (neg_step_size, bias_correction2_sqrt) are sched[2 *step_dev + 0/1], and a
 // step whose views overflowed their capacities (*ovf) updates nothing.
 __global__ __launch_bounds__(256) void k_fit_param_steps(ParamSteps P, float b1, float b2, float b2_c, float eps,
@@ -5370,6 +5338,7 @@ __global__ __launch_bounds__(256) void k_fit_param_steps(ParamSteps P, float b1,
   int t = 0;
   while (t + 1 < P.num && (int)blockIdx.x >= P.first[t + 1]) ++t;
   const gr_param_step& q = P.s[t];
+  const bool adam = P.adam[t] != 0;  // (uniform per block)
   const int ts = sched ? *step_dev : 0;
   const float neg_step = sched ? sched[2 * ts] : q.neg_step_size, bc2s = sched ? sched[2 * ts + 1] : q.bias_correction2_sqrt;
   const int nb = P.first[t + 1] - P.first[t];
@@ -5387,12 +5356,18 @@ __global__ __launch_bounds__(256) void k_fit_param_steps(ParamSteps P, float b1,
         ga.z = ga.z + u.z;
         ga.w = ga.w + u.w;
       }
-      float4 x = ((float4*)p)[e], mm = ((float4*)m)[e], vv = ((float4*)v)[e], g;
-      g.x = fit_param_elem(q.act, ga.x + q.reg, x.x, mm.x, vv.x, neg_step, bc2s, b1, b2, b2_c, eps);
-      g.y = fit_param_elem(q.act, ga.y + q.reg, x.y, mm.y, vv.y, neg_step, bc2s, b1, b2, b2_c, eps);
-      g.z = fit_param_elem(q.act, ga.z + q.reg, x.z, mm.z, vv.z, neg_step, bc2s, b1, b2, b2_c, eps);
-      g.w = fit_param_elem(q.act, ga.w + q.reg, x.w, mm.w, vv.w, neg_step, bc2s, b1, b2, b2_c, eps);
+      float4 x = ((const float4*)p)[e], mm, vv, g;
+      if (adam) mm = ((const float4*)m)[e], vv = ((const float4*)v)[e];
+      g.x = act_backward(q.act, ga.x + q.reg, x.x);
+      g.y = act_backward(q.act, ga.y + q.reg, x.y);
+      g.z = act_backward(q.act, ga.z + q.reg, x.z);
+      g.w = act_backward(q.act, ga.w + q.reg, x.w);
       if (q.grad) ((float4*)q.grad)[e] = g;
+      if (!adam) continue;
+      adam_elem(g.x, x.x, mm.x, vv.x, neg_step, bc2s, b1, b2, b2_c, eps);
+      adam_elem(g.y, x.y, mm.y, vv.y, neg_step, bc2s, b1, b2, b2_c, eps);
+      adam_elem(g.z, x.z, mm.z, vv.z, neg_step, bc2s, b1, b2, b2_c, eps);
+      adam_elem(g.w, x.w, mm.w, vv.w, neg_step, bc2s, b1, b2, b2_c, eps);
       ((float4*)m)[e] = mm;
       ((float4*)v)[e] = vv;
       ((float4*)p)[e] = x;
@@ -5402,9 +5377,12 @@ __global__ __launch_bounds__(256) void k_fit_param_steps(ParamSteps P, float b1,
   for (int64_t e = e0; e < q.count; e += stride) {
     float gact = q.num_accs > 0 ? q.accs[0][e] : 0.0f;
     for (int a = 1; a < q.num_accs; ++a) gact = gact + q.accs[a][e];  // in stream order
-    float x = p[e], mm = m[e], vv = v[e];
-    const float g = fit_param_elem(q.act, gact + q.reg, x, mm, vv, neg_step, bc2s, b1, b2, b2_c, eps);
+    float x = p[e], mm, vv;
+    if (adam) mm = m[e], vv = v[e];
+    const float g = act_backward(q.act, gact + q.reg, x);
     if (q.grad) q.grad[e] = g;
+    if (!adam) continue;
+    adam_elem(g, x, mm, vv, neg_step, bc2s, b1, b2, b2_c, eps);
     m[e] = mm;
     v[e] = vv;
     p[e] = x;
@@ -5489,17 +5467,17 @@ __global__ __launch_bounds__(256) void k_fit_activations(int64_t n, const float*
   }
 }
 
-// Adam alone on an assembled (e.g. all-reduced) gradient.
+// Adam alone on an assembled (e.g. all-reduced) gradient.  (A kernel of its own: through k_fit_param_steps' accumulator
+// sum the gradient would pick up a + 0.0f, which changes the sign of a negative zero.)
 __global__ __launch_bounds__(256) void k_adam_step(int64_t count, float* __restrict__ p, const float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v, float neg_step,
                                                    float bc2_sqrt, float b1, float b2, float b2_c, float eps) {
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < count; e += (int64_t)gridDim.x * 256) {
-    const float ge = g[e];
-    const float mm = fmaf(b1, ge - m[e], m[e]);
-    const float vv = fmaf(b2_c, ge * ge, v[e] * b2);
+    float x = p[e], mm = m[e], vv = v[e];
+    adam_elem(g[e], x, mm, vv, neg_step, bc2_sqrt, b1, b2, b2_c, eps);
     m[e] = mm;
     v[e] = vv;
-    p[e] = fmaf(neg_step, mm / (sqrtf(vv) / bc2_sqrt + eps), p[e]);
+    p[e] = x;
   }
 }
 
@@ -7085,6 +7063,28 @@ gr_status gr_l1_loss_fwd(const float* a, const float* b, int64_t n1, const float
   return GR_OK;
 }
 
+// One checked, non-empty tensor of a k_fit_param_steps launch: its float4 eligibility and its share of the grid.
+static void param_steps_add(ParamSteps& P, const gr_param_step& q, int adam) {
+  auto al = [](const void* a) { return a == nullptr || ((uintptr_t)a & 15u) == 0; };
+  bool v4 = q.count % 4 == 0 && al(q.param) && al(q.grad) && al(q.exp_avg) && al(q.exp_avg_sq);
+  for (int a = 0; a < q.num_accs; ++a) v4 = v4 && al(q.accs[a]);
+  P.s[P.num] = q;
+  P.vec4[P.num] = v4 ? 1 : 0;
+  P.adam[P.num] = adam ? 1 : 0;
+  // one element (or float4) per thread up to 16384 blocks per tensor: the loads of one pass are all in flight
+  P.first[P.num + 1] = P.first[P.num] + (int)std::min<int64_t>(((v4 ? q.count / 4 : q.count) + 255) / 256, 16384);
+  ++P.num;
+}
+
+// torch.optim.Adam passes 1 - beta1 (lerp weight) and 1 - beta2 (addcmul value) as Python floats (double).
+static gr_status param_steps_launch(const ParamSteps& P, double beta1, double beta2, float eps, const float* sched,
+                                    const int* step_dev, const int* overflow, void* stream) {
+  hipLaunchKernelGGL(k_fit_param_steps, dim3(P.first[P.num]), dim3(256), 0, (hipStream_t)stream, P, (float)(1.0 - beta1),
+                     (float)beta2, (float)(1.0 - beta2), eps, sched, step_dev, overflow);
+  GR_HIP_TRY(hipGetLastError());
+  return GR_OK;
+}
+
 gr_status gr_fit_param_step(int64_t count, int act, float* param, float* grad, const float* const* accs, int num_accs,
                             float reg, int adam, float* exp_avg, float* exp_avg_sq, float neg_step_size,
                             float bias_correction2_sqrt, double beta1, double beta2, float eps, void* stream) {
@@ -7092,19 +7092,16 @@ gr_status gr_fit_param_step(int64_t count, int act, float* param, float* grad, c
       num_accs < 0 || num_accs > GR_FIT_MAX_ACC || (num_accs > 0 && !accs))
     return set_error(GR_ERR_INVALID_ARGUMENT, "gr_fit_param_step: bad arguments");
   if (count == 0) return GR_OK;
-  AccList acc;
-  acc.n = num_accs;
+  gr_param_step q = {count, act, num_accs, param, grad, {}, exp_avg, exp_avg_sq, reg, neg_step_size, bias_correction2_sqrt};
   for (int a = 0; a < num_accs; ++a) {
     if (!accs[a]) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_fit_param_step: null accumulator");
-    acc.p[a] = accs[a];
+    q.accs[a] = accs[a];
   }
-  const int blocks = (int)std::min<int64_t>((count + 255) / 256, 4096);
-  // torch.optim.Adam passes 1 - beta1 (lerp weight) and 1 - beta2 (addcmul value) as Python floats (double)
-  const float w1 = (float)(1.0 - beta1), w2 = (float)(1.0 - beta2);
   if (GR_DEBUG_SKIP & 16) return GR_OK;
-  hipLaunchKernelGGL(k_fit_param_step, dim3(blocks), dim3(256), 0, (hipStream_t)stream, count, act, param, grad, acc, reg, adam, exp_avg, exp_avg_sq, neg_step_size, bias_correction2_sqrt, w1, (float)beta2, w2, eps);
-  GR_HIP_TRY(hipGetLastError());
-  return GR_OK;
+  ParamSteps P;
+  // the batched launch's shape: of the shapes tried for one tensor alone the quickest (profiles/param_step_refactor.txt)
+  param_steps_add(P, q, adam);
+  return param_steps_launch(P, beta1, beta2, eps, nullptr, nullptr, nullptr, stream);
 }
 
 static gr_status param_steps_impl(int num, const gr_param_step* steps, double beta1, double beta2, float eps,
@@ -7112,8 +7109,6 @@ static gr_status param_steps_impl(int num, const gr_param_step* steps, double be
   if (num < 0 || num > GR_FIT_MAX_PARAMS || (num > 0 && !steps))
     return set_error(GR_ERR_INVALID_ARGUMENT, "gr_fit_param_steps: bad arguments");
   ParamSteps P;
-  P.num = 0;
-  P.first[0] = 0;
   for (int t = 0; t < num; ++t) {
     const gr_param_step& q = steps[t];
     if (q.count < 0 || q.act < 0 || q.act > 2 || !q.param || !q.exp_avg || !q.exp_avg_sq || q.num_accs < 0 ||
@@ -7121,22 +7116,13 @@ static gr_status param_steps_impl(int num, const gr_param_step* steps, double be
       return set_error(GR_ERR_INVALID_ARGUMENT, "gr_fit_param_steps: bad parameter entry");
     for (int a = 0; a < q.num_accs; ++a)
       if (!q.accs[a]) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_fit_param_steps: null accumulator");
-    if (q.count == 0) continue;
-    auto al = [](const void* a) { return a == nullptr || ((uintptr_t)a & 15u) == 0; };
-    bool v4 = q.count % 4 == 0 && al(q.param) && al(q.grad) && al(q.exp_avg) && al(q.exp_avg_sq);
-    for (int a = 0; a < q.num_accs; ++a) v4 = v4 && al(q.accs[a]);
-    P.s[P.num] = q;
-    P.vec4[P.num] = v4 ? 1 : 0;
-    // one element (or float4) per thread up to 16384 blocks per tensor: the loads of one pass are all in flight
-    P.first[P.num + 1] = P.first[P.num] + (int)std::min<int64_t>(((v4 ? q.count / 4 : q.count) + 255) / 256, 16384);
-    ++P.num;
+    if (q.count > 0) param_steps_add(P, q, 1);
   }
   if (P.num == 0 && !sched) return GR_OK;
   if (GR_DEBUG_SKIP & 16) return GR_OK;
   if (P.num > 0) {
-    hipLaunchKernelGGL(k_fit_param_steps, dim3(P.first[P.num]), dim3(256), 0, (hipStream_t)stream, P, (float)(1.0 - beta1),
-                       (float)beta2, (float)(1.0 - beta2), eps, sched, (const int*)step_dev, (const int*)overflow);
-    GR_HIP_TRY(hipGetLastError());
+    const gr_status st = param_steps_launch(P, beta1, beta2, eps, sched, step_dev, overflow, stream);
+    if (st != GR_OK) return st;
   }
   if (sched) {
     int* mapped = nullptr;

@@ -76,7 +76,6 @@ REDUCE_TAIL = max(0, min(REDUCE_BATCH, int(os.environ.get("GR_REDUCE_TAIL", "2")
 FUSED_STEP = os.environ.get("GR_FUSED_STEP", "1") != "0"
 # fused path: views prepared ahead of the one being rendered (on the preparation stream)
 PREP_AHEAD = max(1, int(os.environ.get("GR_PREP_AHEAD", "6")))
-L_MAX_ACC = 8  # GR_FIT_MAX_ACC: stream accumulators gr_fit_param_step sums
 # views prepared together (gr_fwd_prepare_views_async: the parameters read once for the group)
 PREP_GROUP = max(1, min(4, int(os.environ.get("GR_PREP_GROUP", "4"))))
 PREP_FIRST = max(1, min(PREP_GROUP, int(os.environ.get("GR_PREP_FIRST", "1"))))
@@ -1704,15 +1703,17 @@ class ViewShardedFitter:
     def _fused_param_step(self, scales, opacities, loss, sized=None) -> torch.Tensor:
         """fit_multiview_stub.py:307-311 after the views: d loss / d raw parameters through the activations
         (softplus + 1e-3, sigmoid, identity) and the regulariser (rank 0), then torch.optim.Adam's update with
-        its own state tensors, one gr_fit_param_step pass per parameter (world size 1), or gradient assembly
-        into the flat all-reduce buffer, the all-reduce, then gr_adam_step per parameter."""
-        L = tr._native.lib()
+        its own state tensors: every parameter in one launch (world size 1; gr_fit_param_steps), or gradient assembly
+        into the flat all-reduce buffer (gr_fit_param_step), the all-reduce, then gr_adam_step per parameter."""
+        nat = tr._native
+        L = nat.lib()
         g = self.opt.param_groups[0]
         lr, (b1, b2), eps = float(g["lr"]), g["betas"], float(g["eps"])
         parts = self._acc_parts
         self._acc_parts = None
         slot = {"means": 0, "scales_raw": 1, "colors_raw": 2, "sh_raw": 2, "opacities_raw": 3}
-        act = {"means": 0, "scales_raw": 1, "colors_raw": 2, "sh_raw": 0, "opacities_raw": 2}
+        act = {"means": nat.ACT_IDENTITY, "scales_raw": nat.ACT_SOFTPLUS, "colors_raw": nat.ACT_SIGMOID,
+               "sh_raw": nat.ACT_IDENTITY, "opacities_raw": nat.ACT_SIGMOID}
         # mean()'s backward: the float32 weight divided by the float32 element count, as autograd computes it
         reg = {"scales_raw": float(np.float32(self.reg_scale) / np.float32(max(1, scales.numel()))),
                "opacities_raw": float(np.float32(self.reg_opacity) / np.float32(max(1, opacities.numel())))}
@@ -1723,9 +1724,11 @@ class ViewShardedFitter:
         if self.world > 1:
             flat = torch.empty(sum(p.numel() for p in plist) + 1, dtype=torch.float32, device=plist[0].device)
         off = 0
-        steps = []
-        assembly = []
-        for k, p in zip(names, plist):
+        most = nat.FIT_MAX_ACC
+        # every tensor's operands, stated once: each route below hands these entries to its entry point
+        entries = (nat.GrParamStep * len(plist))()
+        held = []  # the summed arrays (folded ones included), alive until their launch is issued
+        for e, k, p in zip(entries, names, plist):
             st = self.opt.state[p]
             if not st:  # torch.optim.Adam's lazy state, same tensors and layout
                 st["step"] = torch.tensor(0.0, dtype=torch.float32)
@@ -1734,16 +1737,17 @@ class ViewShardedFitter:
             if sized is None:  # (a captured step: the graph driver advances the host counts per replay)
                 st["step"] += 1
             t = float(st["step"])
-            neg_step = -(lr / (1.0 - b1 ** t))
-            bc2s = (1.0 - b2 ** t) ** 0.5
-            steps.append((neg_step, bc2s))
+            e.neg_step_size, e.bias_correction2_sqrt = -(lr / (1.0 - b1 ** t)), (1.0 - b2 ** t) ** 0.5
             a = [pp[slot[k]] for pp in parts]
-            if len(a) > L_MAX_ACC:  # more streams than the kernel sums: fold the rest in stream order first
-                t = a[L_MAX_ACC - 1]
-                for x in a[L_MAX_ACC:]:
+            if len(a) > most:  # more streams than the kernel sums: fold the rest in stream order first
+                t = a[most - 1]
+                for x in a[most:]:
                     t = t + x
-                a = a[:L_MAX_ACC - 1] + [t]
-            accs = (ctypes.c_void_p * max(1, len(a)))(*[x.data_ptr() for x in a])
+                a = a[:most - 1] + [t]
+            held.append(a)
+            e.num_accs = len(a)
+            for j, x in enumerate(a):
+                e.accs[j] = x.data_ptr()
             if flat is not None:
                 grad = flat[off:off + p.numel()].view_as(p)
                 off += p.numel()
@@ -1757,43 +1761,30 @@ class ViewShardedFitter:
             # p.grad is this kept tensor, overwritten in place every step (an alias, not a fresh tensor): a caller that
             # keeps a reference to p.grad across steps (logging, clipping history, EMA) must copy it
             p.grad = grad
-            r = reg.get(k, 0.0) if self.rank == 0 else 0.0
+            e.count, e.act = p.numel(), act[k]
+            e.param, e.grad = p.data.data_ptr(), grad.data_ptr()
+            e.exp_avg, e.exp_avg_sq = st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()
+            e.reg = reg.get(k, 0.0) if self.rank == 0 else 0.0
+        betas_eps = (ctypes.c_double(b1), ctypes.c_double(b2), ctypes.c_float(eps))
 
-            def step_call(p=p, grad=grad, accs=accs, a=a, r=r, k=k, st=st, neg_step=neg_step, bc2s=bc2s):
-                tr._native.check(L.gr_fit_param_step(p.numel(), act[k], tr._native.ptr(p.data), tr._native.ptr(grad),
-                                                     accs, len(a), ctypes.c_float(r), 0 if flat is not None else 1,
-                                                     tr._native.ptr(st["exp_avg"]), tr._native.ptr(st["exp_avg_sq"]),
-                                                     ctypes.c_float(neg_step), ctypes.c_float(bc2s), ctypes.c_double(b1),
-                                                     ctypes.c_double(b2), ctypes.c_float(eps), stream), "gr_fit_param_step")
-            assembly.append(step_call)
+        def gradient(e, adam):  # one tensor's gradient, with adam its update too (gr_fit_param_step)
+            nat.check(L.gr_fit_param_step(e.count, e.act, e.param, e.grad, e.accs, e.num_accs, ctypes.c_float(e.reg),
+                                                 adam, e.exp_avg, e.exp_avg_sq, ctypes.c_float(e.neg_step_size),
+                                                 ctypes.c_float(e.bias_correction2_sqrt), *betas_eps, stream),
+                             "gr_fit_param_step")
+
         if flat is None:
-            if len(plist) <= tr._native.FIT_MAX_PARAMS and all(len(pp) <= tr._native.FIT_MAX_ACC for pp in parts):
-                # world size 1: every parameter's gradient and Adam update in one launch (gr_fit_param_steps)
-                arr = (tr._native.GrParamStep * len(plist))()
-                for q, (k, p) in enumerate(zip(names, plist)):
-                    st, (neg_step, bc2s) = self.opt.state[p], steps[q]
-                    a = [pp[slot[k]] for pp in parts]
-                    e = arr[q]
-                    e.count, e.act, e.num_accs = p.numel(), act[k], len(a)
-                    e.param, e.grad = p.data.data_ptr(), p.grad.data_ptr()
-                    for j, x in enumerate(a):
-                        e.accs[j] = x.data_ptr()
-                    e.exp_avg, e.exp_avg_sq = st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()
-                    e.reg = reg.get(k, 0.0) if self.rank == 0 else 0.0
-                    e.neg_step_size, e.bias_correction2_sqrt = neg_step, bc2s
-                if sized is None:
-                    tr._native.check(L.gr_fit_param_steps(len(plist), arr, ctypes.c_double(b1), ctypes.c_double(b2),
-                                                          ctypes.c_float(eps), stream), "gr_fit_param_steps")
-                else:  # the step's scalars from the device table, skipped on overflow (gr_fit_param_steps_sched)
-                    tr._native.check(L.gr_fit_param_steps_sched(
-                        len(plist), arr, ctypes.c_double(b1), ctypes.c_double(b2), ctypes.c_float(eps),
-                        tr._native.ptr(sized.sched), tr._native.ptr(sized.step_dev), tr._native.ptr(sized.ovf),
-                        ctypes.c_void_p(sized.flags.data_ptr()), stream), "gr_fit_param_steps_sched")
-            elif sized is not None:
-                raise RuntimeError("graph step: more parameters or stream accumulators than one gr_fit_param_steps launch")
-            else:
-                for call in assembly:
-                    call()
+            if len(plist) > nat.FIT_MAX_PARAMS:  # more tensors than one launch takes: one launch each
+                if sized is not None:
+                    raise RuntimeError("graph step: more parameters than one gr_fit_param_steps launch")
+                for e in entries:
+                    gradient(e, 1)
+            elif sized is None:  # world size 1: every parameter's gradient and Adam update in one launch
+                nat.check(L.gr_fit_param_steps(len(plist), entries, *betas_eps, stream), "gr_fit_param_steps")
+            else:  # the step's scalars from the device table, skipped on overflow (gr_fit_param_steps_sched)
+                nat.check(L.gr_fit_param_steps_sched(
+                    len(plist), entries, *betas_eps, nat.ptr(sized.sched), nat.ptr(sized.step_dev),
+                    nat.ptr(sized.ovf), ctypes.c_void_p(sized.flags.data_ptr()), stream), "gr_fit_param_steps_sched")
             return loss.detach()
         bounds, o0 = [], 0
         for p in plist:
@@ -1802,17 +1793,14 @@ class ViewShardedFitter:
         bounds[-1] = (bounds[-1][0], off + 1)  # the loss rides in the last bucket
 
         def assemble(b):
-            assembly[b]()
+            gradient(entries[b], 0)
             if b == len(plist) - 1:
                 flat[off:off + 1].copy_(loss.detach().reshape(1))
 
         def finish(b):
-            p, (neg_step, bc2s) = plist[b], steps[b]
-            st = self.opt.state[p]
-            tr._native.check(L.gr_adam_step(p.numel(), tr._native.ptr(p.data), tr._native.ptr(p.grad),
-                                            tr._native.ptr(st["exp_avg"]), tr._native.ptr(st["exp_avg_sq"]),
-                                            ctypes.c_float(neg_step), ctypes.c_float(bc2s), ctypes.c_double(b1),
-                                            ctypes.c_double(b2), ctypes.c_float(eps), stream), "gr_adam_step")
+            e = entries[b]
+            nat.check(L.gr_adam_step(e.count, e.param, e.grad, e.exp_avg, e.exp_avg_sq, ctypes.c_float(e.neg_step_size),
+                                            ctypes.c_float(e.bias_correction2_sqrt), *betas_eps, stream), "gr_adam_step")
 
         bucketed_all_reduce([flat[a:b] for a, b in bounds], assemble, finish, self.group)
         return flat[off]

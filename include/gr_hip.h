@@ -705,13 +705,17 @@ gr_status gr_ssim_bwd(const float* x, const float* y, int height, int width, int
 /* Fit-loop parameter update, the caller's side of the render op (fit_multiview_stub.py:268-275   */
 /* activations, :307-308 regulariser, :311 torch.optim.Adam), one pass per parameter tensor:    */
 /*   grad = act'(param) * (((accs[0] + accs[1]) + ...) + reg)  (up to GR_FIT_MAX_ACC device arrays  */
-/*          of count floats, summed in order; act 0 identity,                                     */
-/*          1 softplus(x) + 1e-3, 2 sigmoid: torch's backward formulas);                          */
+/*          of count floats, summed in order; act GR_ACT_IDENTITY, GR_ACT_SOFTPLUS                 */
+/*          (softplus(x) + 1e-3) or GR_ACT_SIGMOID: torch's backward formulas);                   */
 /*   adam != 0: exp_avg / exp_avg_sq / param updated as Adam's foreach step with                 */
 /*   neg_step_size = -lr / (1 - beta1^t), bias_correction2_sqrt = sqrt(1 - beta2^t); the betas are */
-/*   doubles so 1 - beta rounds to float as torch's Python-float scalars do.                     */
+/*   doubles so 1 - beta rounds to float as torch's Python-float scalars do.  adam == 0: only    */
+/*   grad is written (required then); exp_avg and exp_avg_sq are not read and may be NULL.       */
 /* gr_adam_step: the Adam update alone on an assembled gradient (after an all-reduce).           */
 /* ------------------------------------------------------------------------------------------ */
+#define GR_ACT_IDENTITY 0
+#define GR_ACT_SOFTPLUS 1
+#define GR_ACT_SIGMOID 2
 #define GR_FIT_MAX_ACC 8
 gr_status gr_fit_param_step(int64_t count, int act, float* param, float* grad, const float* const* accs,
                             int num_accs, float reg, int adam, float* exp_avg, float* exp_avg_sq,

@@ -1,6 +1,6 @@
 """One steady-state fit step's kernel timeline from a rocprofv3 --kernel-trace CSV run: every kernel's
 start / end (us from the step's first kernel), its queue, and the idle gaps of the whole GPU; the step is
-the span between two consecutive parameter-update launches (k_adam_step, or k_fit_param_step at world size 1) in the middle of the run.
+the span between two consecutive parameter-update launches (k_adam_step, or k_fit_param_steps at world size 1) in the middle of the run.
     python tools/step_timeline.py <dir> [step index from the end, default 3]"""
 import csv
 import glob
