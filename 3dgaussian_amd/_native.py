@@ -206,6 +206,9 @@ _SIG = {
     # g_scale, w_dssim, loss_out
     "gr_bwd_fit_ssim": (_I, _VIEW + _PARAMS + _STATE + _L1 + _DEPTH + [_F, _F, _P] + _GRADS + [_I] + _WS + [_P]),
     "gr_bwd_fit_ssim_gather": (_I, _VIEW + _STATE + _L1 + _DEPTH + [_F, _F, _P] + _WS + _SUMS + [_P]),
+    "gr_bwd_exposure_bytes": (_Z, _VIEW),
+    # g_scale, exposure, d_exposure, loss_out
+    "gr_bwd_fit_exposure_gather": (_I, _VIEW + _STATE + _L1 + _DEPTH + [_F, _P, _P, _P] + _WS + _SUMS + [_P]),
     "gr_fit_views_ssim": (_I, _EXEC + _PARAMS + [_F, _F, _F, _F, _P, _PA, _P]),
     "gr_reduce_sums": (_I, [_I, ctypes.POINTER(GrSumsView), _I] + _PARAMS + _GRADS + [_I, _P]),
     "gr_density_stats": (_I, [_I, ctypes.POINTER(GrSumsView), _I, _P, _P, _P, _F, _P, _P]),

@@ -20,6 +20,8 @@
 //   k_pixel_grads    per pixel upstream vector U = (dC, dW, dD), pre-split into MFMA fragments.
 //   k_ssim_pixel_grads  k_pixel_grads of a fit with a D-SSIM term: the D-SSIM backward's convolutions in the same
 //                    tile, its gradient added to the L1 term's per pixel (gr_bwd_fit_ssim; no gradient image).
+//   k_pixel_grads_expo  k_pixel_grads of a fit with per-view exposure: the L1 term on E (x, 1), E read from the device;
+//                    12 sums per tile, d loss / d E by the last tile to arrive (gr_bwd_fit_exposure_gather).
 //   k_raster_bwd_bf16   per work item: the two K = 16 contractions (over x, over y) of U with the
 //                    Gaussians' exponentials; 8- or 9-float partial rows at the pairs' sorted positions.
 //   k_gather_view    per Gaussian: its rows (through pos_of) summed in a fixed order (deterministic, no
@@ -2180,11 +2182,21 @@ __device__ __forceinline__ float sign0(float t) { return t > 0.0f ? 1.0f : (t < 
 // U of pixel p from its sums s = (W, C_r, C_g, C_b) and D; l_rgb / l_sil get the pixel's L1 terms.
 // SSIM (k_ssim_pixel_grads): the photometric gradient is sign(out - t) (1 - l) g / (3 HW) + g_ssim[k], l = l1.w_dssim,
 // g_ssim the pixel's three D-SSIM gradients (already scaled by l g).
-template <bool SSIM = false>
+// EXPO (k_pixel_grads_expo): the photometric term is taken on the exposed colour
+// y_k = E[k][0] x_0 + E[k][1] x_1 + E[k][2] x_2 + E[k][3] of x_j = clamp01(out_j) (y is not clamped), so colour j
+// receives sum_k E[k][j] sign(y_k - t_k) g / (3 HW) through x_j's clamp mask; xp keeps the signs and x for dE.
+// With E = [I | 0] every product below is exact (1 a = a, 0 a = 0 for the finite a here) and every sum adds zeros, so
+// the values are those of the plain form whether or not the compiler contracts a product and a sum into an fma.
+struct ExpoPixel {
+  float E[12];                    // the view's 3 x 4 exposure, row-major
+  float sg[3] = {0.f, 0.f, 0.f};  // sign0(y_k - t_k); zero outside the image
+  float x[3] = {0.f, 0.f, 0.f};   // clamp01(out_j)
+};
+template <bool SSIM = false, bool EXPO = false>
 __device__ __forceinline__ void pixel_upstream(const ViewK& v, int p, float4 s, float Dp, const float* __restrict__ g_rgb,
                                                const float* __restrict__ g_alpha, const float* __restrict__ g_depth,
                                                const L1Args& l1, float (&u)[5], float& l_rgb, float& l_sil,
-                                               const float* g_ssim = nullptr) {
+                                               const float* g_ssim = nullptr, ExpoPixel* xp = nullptr) {
   const float den = 1.0f + s.x, dden = s.x + 1e-6f;
   // one correctly rounded reciprocal of the finalize's denominator instead of ten divisions (each ~10 VALU): the
   // quotients below are products with it, within 1 ulp of the divisions (round 6, the L1 epilogue of the fit forwards)
@@ -2192,23 +2204,49 @@ __device__ __forceinline__ void pixel_upstream(const ViewK& v, int p, float4 s, 
   float gW = 0.f;
   const float C[3] = {s.y, s.z, s.w};
   const float HWf = (float)v.W * (float)v.H;
+  if constexpr (EXPO) {
+    static_assert(!SSIM, "the exposure form has no D-SSIM term");
+    const float* E = xp->E;
+    float r[3], gy[3];
 #pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float r = (view_bg(v, k) + C[k]) * inv;
-    float gk;
-    if (l1.t_rgb) {
-      const float t = clamp01(r) - l1.t_rgb[3 * p + k];
-      l_rgb += fabsf(t);
-      if constexpr (SSIM)
-        gk = sign0(t) * (((1.0f - l1.w_dssim) * l1.g_scale) / (3.0f * HWf)) + g_ssim[k];
-      else
-        gk = sign0(t) * (l1.g_scale / (3.0f * HWf));
-    } else {
-      gk = g_rgb[3 * p + k];
+    for (int j = 0; j < 3; ++j) {
+      r[j] = (view_bg(v, j) + C[j]) * inv;
+      xp->x[j] = clamp01(r[j]);
     }
-    const float go = (r >= 0.0f && r <= 1.0f) ? gk : 0.0f;
-    u[k] = go * inv;
-    gW -= (go * r) * inv;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const float y = ((E[4 * k] * xp->x[0] + E[4 * k + 1] * xp->x[1]) + E[4 * k + 2] * xp->x[2]) + E[4 * k + 3];
+      const float t = y - l1.t_rgb[3 * p + k];
+      l_rgb += fabsf(t);
+      xp->sg[k] = sign0(t);
+      gy[k] = sign0(t) * (l1.g_scale / (3.0f * HWf));
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const float gj = (E[j] * gy[0] + E[4 + j] * gy[1]) + E[8 + j] * gy[2];
+      const float go = (r[j] >= 0.0f && r[j] <= 1.0f) ? gj : 0.0f;
+      u[j] = go * inv;
+      gW -= (go * r[j]) * inv;
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const float r = (view_bg(v, k) + C[k]) * inv;
+      float gk;
+      if (l1.t_rgb) {
+        const float t = clamp01(r) - l1.t_rgb[3 * p + k];
+        l_rgb += fabsf(t);
+        if constexpr (SSIM)
+          gk = sign0(t) * (((1.0f - l1.w_dssim) * l1.g_scale) / (3.0f * HWf)) + g_ssim[k];
+        else
+          gk = sign0(t) * (l1.g_scale / (3.0f * HWf));
+      } else {
+        gk = g_rgb[3 * p + k];
+      }
+      const float go = (r >= 0.0f && r <= 1.0f) ? gk : 0.0f;
+      u[k] = go * inv;
+      gW -= (go * r) * inv;
+    }
   }
   const float al = s.x * inv;
   float ga = 0.0f;
@@ -2450,22 +2488,94 @@ __device__ __forceinline__ void tile_fragments(const float (*sU)[TP], uint4* __r
   }
 }
 
+// The exposure form's operands (k_pixel_grads_expo only; gr_bwd_fit_exposure_gather).
+struct ExpoArgs {
+  const float* E = nullptr;   // the view's exposure: 12 floats on the device, row-major 3 x 4
+  float* tile_sums = nullptr; // [tiles][12]: per tile S[k][j] = sum_p sign0(y_k - t_k) x_j (j < 3), S[k][3] = sum_p sign0(y_k - t_k)
+  float* d_E = nullptr;       // 12 floats, written by the last tile to arrive: (g_scale / (3 HW)) sum_tiles S
+};
+// The tile's 12 exposure sums (block of 256 threads, one pixel each), as tile_loss_sums: waves, then the 4 wave sums
+// in a fixed order, write-through for the launch's last tile.
+__device__ __forceinline__ void tile_expo_sums(int tile, int tid, const ExpoPixel& xp, float* tile_sums) {
+  float S[12];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) S[4 * k + j] = xp.sg[k] * xp.x[j];
+    S[4 * k + 3] = xp.sg[k];
+  }
+#pragma unroll
+  for (int c = 0; c < 12; ++c) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) S[c] += __shfl_xor(S[c], o);
+  }
+  __shared__ float sE[12][4];
+  if ((tid & 63) == 0) {
+#pragma unroll
+    for (int c = 0; c < 12; ++c) sE[c][tid >> 6] = S[c];
+  }
+  __syncthreads();
+  if (tid < 12) st_through(&tile_sums[12 * tile + tid], ((sE[tid][0] + sE[tid][1]) + sE[tid][2]) + sE[tid][3]);
+}
+// d_E from the tiles' write-through sums (one block of 256 threads; the last tile of k_pixel_grads_expo): each of the
+// 12 columns summed over the tiles in double in tile_loss_total's fixed order, three columns per pass over its
+// double[3][256] scratch, then the loss's constant once.
+__device__ __forceinline__ void tile_expo_total(const float* __restrict__ tile_sums, int tiles, float scale,
+                                                float* __restrict__ d_E, double (*r)[256]) {
+  const int t = threadIdx.x;
+  for (int c0 = 0; c0 < 12; c0 += 3) {
+    double s[3] = {0.0, 0.0, 0.0};
+    for (int i = t; i < tiles; i += 256) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) s[c] += (double)ld_through(tile_sums + 12 * i + c0 + c);
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) r[c][t] = s[c];
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+      if (t < w) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) r[c][t] += r[c][t + w];
+      }
+      __syncthreads();
+    }
+    if (t < 3) d_E[c0 + t] = (float)(r[t][0] * (double)scale);
+    __syncthreads();  // the next pass (and tile_loss_total) overwrite r
+  }
+}
+
 // With the fit loss (l1.t_rgb) the last tile to finish (arrive_last_tile) also writes the view loss.
+// EXPO (k_pixel_grads_expo): the fit loss on the exposed colour (pixel_upstream<false, true>; l1.t_rgb, l1.tile_loss and
+// l1.loss_out are set); the last tile also writes d_E.
+template <bool EXPO = false>
 __device__ __forceinline__ void k_pixel_grads_body(ViewK v, const float4* __restrict__ saved4,
                                                      const float* __restrict__ savedD, const float* __restrict__ g_rgb,
                                                      const float* __restrict__ g_alpha, const float* __restrict__ g_depth,
                                                      uint4* __restrict__ UF, int pieces, L1Args l1, bool depth,
-                                                     int* __restrict__ ticket, const BI blockIdx, const BI gridDim) {
+                                                     int* __restrict__ ticket, const BI blockIdx, const BI gridDim,
+                                                     ExpoArgs ex = ExpoArgs{}) {
   const int tile = blockIdx.x, tid = threadIdx.x;
   const int tx = tile % v.tiles_x, ty = tile / v.tiles_x;
   const int x = tx * T + (tid & (T - 1)), y = ty * T + (tid >> 4);
   float u[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
   float l_rgb = 0.f, l_sil = 0.f;
-  if (x < v.W && y < v.H) {
-    const int p = y * v.W + x;
-    pixel_upstream(v, p, saved4[p], savedD[p], g_rgb, g_alpha, g_depth, l1, u, l_rgb, l_sil);
+  if constexpr (EXPO) {
+    ExpoPixel xp;
+#pragma unroll
+    for (int i = 0; i < 12; ++i) xp.E[i] = ex.E[i];  // uniform: one read per block, no host copy of E
+    if (x < v.W && y < v.H) {
+      const int p = y * v.W + x;
+      pixel_upstream<false, true>(v, p, saved4[p], savedD[p], nullptr, nullptr, nullptr, l1, u, l_rgb, l_sil, nullptr, &xp);
+    }
+    tile_loss_sums(tile, tid, l_rgb, l_sil, l1.tile_loss);
+    tile_expo_sums(tile, tid, xp, ex.tile_sums);
+  } else {
+    if (x < v.W && y < v.H) {
+      const int p = y * v.W + x;
+      pixel_upstream(v, p, saved4[p], savedD[p], g_rgb, g_alpha, g_depth, l1, u, l_rgb, l_sil);
+    }
+    if (l1.tile_loss) tile_loss_sums(tile, tid, l_rgb, l_sil, l1.tile_loss);
   }
-  if (l1.tile_loss) tile_loss_sums(tile, tid, l_rgb, l_sil, l1.tile_loss);
   // six rows, not five: the last tile reuses the buffer as tile_loss_total's double[3][256] (6 KiB)
   __shared__ __attribute__((aligned(16))) float sU[6][TP];
   static_assert(sizeof(sU) >= 3 * 256 * sizeof(double), "tile_loss_total scratch");
@@ -2476,9 +2586,13 @@ __device__ __forceinline__ void k_pixel_grads_body(ViewK v, const float4* __rest
   if (l1.tile_loss && l1.loss_out) {  // (tile_loss_sums' stores are write-through)
     __shared__ int last;
     const int tiles = v.tiles_x * v.tiles_y;
-    if (arrive_last_tile(ticket, tiles, tile, &last))
+    if (arrive_last_tile(ticket, tiles, tile, &last)) {
+      if constexpr (EXPO)
+        tile_expo_total(ex.tile_sums, tiles, l1.g_scale / (3.0f * ((float)v.W * (float)v.H)), ex.d_E,
+                        reinterpret_cast<double (*)[256]>(&sU[0][0]));
       tile_loss_total<true>(l1.tile_loss, tiles, l1.n1, l1.n2, l1.w_sil, l1.t_depth ? l1.n1 / 3 : 0, l1.w_depth,
                             l1.loss_out, reinterpret_cast<double (*)[256]>(&sU[0][0]));
+    }
   }
 }
 struct k_pixel_grads_args {
@@ -2503,6 +2617,18 @@ __global__ __launch_bounds__(256) void k_pixel_grads(k_pixel_grads_args a) {
 __global__ __launch_bounds__(256) void k_pixel_grads_views(VBatch<k_pixel_grads_args> B) {
   const VBlock b = vbatch_block(B);
   k_pixel_grads_run(B.a[b.view], b);
+}
+// k_pixel_grads of a fit with per-view exposure (gr_bwd_fit_exposure_gather): the fit loss on the exposed colour, the
+// view loss and d_E by the last tile to arrive.  One view per launch (no batched form).
+struct k_pixel_grads_expo_args {
+  k_pixel_grads_args a;  // g_rgb / g_alpha / g_depth unused (the fit loss)
+  ExpoArgs ex;
+};
+__global__ __launch_bounds__(256) void k_pixel_grads_expo(k_pixel_grads_expo_args e) {
+  const k_pixel_grads_args& a = e.a;
+  const VBlock b = own_block();
+  k_pixel_grads_body<true>(a.v, a.saved4, a.savedD, nullptr, nullptr, nullptr, a.UF, a.pieces, a.l1, a.depth, a.ticket, b.block,
+                           b.grid, e.ex);
 }
 
 
@@ -6015,6 +6141,11 @@ struct ViewLoss {
   // (1 - l) L1 + l D-SSIM, its forward from the saved sums (k_ssim_fwd_saved) and k_ssim_pixel_grads in k_pixel_grads' place
   bool ssim_entry = false;
   float w_dssim = 0.0f;
+  // gr_bwd_fit_exposure_gather (the workspace of gr_bwd_exposure_bytes): the photometric term on the exposed colour
+  // (k_pixel_grads_expo in k_pixel_grads' place), `exposure` the view's 12 floats on the device, d_exposure written
+  bool expo_entry = false;
+  const float* exposure = nullptr;
+  float* d_exposure = nullptr;
 };
 // One backward of a view (bwd_impl): what every entry has first (the view, its render state, the workspace), then what
 // an entry names; the chain rule into `grads`, or with `sums` the per-Gaussian sums to the caller.
@@ -6421,7 +6552,9 @@ static gr_status bwd_impl(const BwdRequest& r) {
   const bool ssim = vl.ssim_entry && vl.w_dssim > 0.0f;
   if (ssim && !ssim_shape_ok(v->height, v->width, 3))
     return set_error(GR_ERR_INVALID_ARGUMENT, "gr_bwd_fit_ssim: the view exceeds the D-SSIM kernels' 2^30 values");
-  const size_t ws_need = vl.ssim_entry ? gr_bwd_ssim_bytes(v, n, plan) : gr_bwd_bytes(v, n, plan);
+  const size_t ws_need = vl.ssim_entry   ? gr_bwd_ssim_bytes(v, n, plan)
+                         : vl.expo_entry ? gr_bwd_exposure_bytes(v, n, plan)
+                                         : gr_bwd_bytes(v, n, plan);
   if ((num_pairs > 0 || t_rgb) && (!ws || r.ws_bytes < ws_need))
     return set_error(GR_ERR_WORKSPACE, "backward workspace too small");
   hipStream_t s = (hipStream_t)r.stream;
@@ -6456,6 +6589,14 @@ static gr_status bwd_impl(const BwdRequest& r) {
                        partial, maps);
     hipLaunchKernelGGL(k_ssim_pixel_grads, dim3(tiles), dim3(256), 0, s, vk, (const float4*)saved, saved + 4 * HW,
                        (const float*)maps, (const float*)partial, UF, pieces, l1, depth, ticket);
+    GR_HIP_TRY(hipGetLastError());
+  } else if (vl.expo_entry) {
+    // the per-tile exposure sums ([tiles][12]) follow gr_bwd_bytes; without a pair the launch still writes the view
+    // loss and d_exposure (from the background)
+    float* tile_sums = (float*)((char*)ws + gr_bwd_bytes(v, n, plan));
+    launch_one(k_pixel_grads_expo, dim3(tiles), 256, 0, s,
+               k_pixel_grads_expo_args{pixel_grads_args(c, saved, nullptr, nullptr, nullptr, pieces, l1, depth),
+                                       ExpoArgs{vl.exposure, tile_sums, vl.d_exposure}});
     GR_HIP_TRY(hipGetLastError());
   } else if (num_pairs > 0 || t_rgb) {
     launch_one(k_pixel_grads, dim3(tiles), 256, 0, s,
@@ -6591,6 +6732,29 @@ gr_status gr_bwd_fit_ssim_gather(const gr_view* v, int n, const gr_plan* plan, c
   r.loss = {target_rgb, target_mask, w_sil, target_depth, w_depth, g_scale, loss_out};
   r.loss.ssim_entry = true;
   r.loss.w_dssim = w_dssim;
+  r.sums = sums;
+  r.sums3 = sums3;
+  return bwd_impl(r);
+}
+
+size_t gr_bwd_exposure_bytes(const gr_view* v, int n, const gr_plan* plan) {
+  return gr_bwd_bytes(v, n, plan) + align_up((size_t)tiles_of(v) * 12 * sizeof(float));
+}
+
+gr_status gr_bwd_fit_exposure_gather(const gr_view* v, int n, const gr_plan* plan, const void* geom, const void* bins,
+                                     const float* saved, const float* target_rgb, const float* target_mask, float w_sil,
+                                     const float* target_depth, float w_depth, float g_scale, const float* exposure,
+                                     float* d_exposure, float* loss_out, void* ws, size_t ws_bytes, float* sums,
+                                     float* sums3, void* stream) {
+  if (!target_rgb) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_bwd_fit_exposure_gather: target_rgb is null");
+  if (!sums) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_bwd_fit_exposure_gather: sums is null");
+  if (!exposure) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_bwd_fit_exposure_gather: exposure is null");
+  if (!d_exposure) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_bwd_fit_exposure_gather: d_exposure is null");
+  BwdRequest r{v, n, plan, geom, bins, saved, ws, ws_bytes, stream};
+  r.loss = {target_rgb, target_mask, w_sil, target_depth, w_depth, g_scale, loss_out};
+  r.loss.expo_entry = true;
+  r.loss.exposure = exposure;
+  r.loss.d_exposure = d_exposure;
   r.sums = sums;
   r.sums3 = sums3;
   return bwd_impl(r);

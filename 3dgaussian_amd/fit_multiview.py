@@ -560,7 +560,7 @@ class ViewShardedFitter:
                  render_fn: RenderFn = hip_render, group=None, reorder: bool = True, dssim_weight: float = 0.0,
                  dssim_fused: bool = False, density_stats: bool = False, refine_cameras: bool = False,
                  camera_lr: float = 1e-3, camera_fixed: tuple = (0,), exposure: bool = False, exposure_lr: float = 1e-3,
-                 exposure_fixed: tuple = (0,)):
+                 exposure_fixed: tuple = (0,), exposure_fused: bool = False):
         # dssim_weight l > 0: a view's photometric term is (1 - l) mean|pred - tgt| + l dssim(pred, tgt)
         # (losses.dssim_loss) on the per-view autograd path; 0 (default): the L1 fit, every path as it was
         # dssim_fused (with l > 0, the HIP render op): the fused path's D-SSIM form (_views_scheduled or the native
@@ -574,8 +574,10 @@ class ViewShardedFitter:
         # exposure: per-view exposure compensation, a 3 x 4 colour transform E per training view (from [I | 0]) fitted
         # with the scene by an Adam of its own at exposure_lr: the photometric term (L1 and D-SSIM alike) compares
         # E (pred, 1) with the target (the views of exposure_fixed keep theirs, which pins the overall brightness
-        # gauge), through autograd in view_loss.  Host tensors only: the HIP device has no exposure form yet, and a fit
-        # on it raises rather than leave the fused path; evaluate() renders without it
+        # gauge), through autograd in view_loss on host tensors.  On the HIP device exposure alone raises rather than
+        # leave the fused path; exposure_fused opts into the fused path's exposure form (_views_scheduled's "exposure":
+        # gr_bwd_fit_exposure_gather per view reads E from the device and writes d loss / d E, the Python schedule with
+        # the fused parameter step only, no D-SSIM term); on host tensors it changes nothing.  evaluate() renders without E
         # reorder: keep the Gaussians in spatial (Morton) order, re-established after every
         # densify/prune (spatial_order); off only to compare with an unpermuted run
         # perm: self.params[k][i] = canonical[k][perm[i]], the canonical order being the stub's (the
@@ -659,13 +661,23 @@ class ViewShardedFitter:
             self._cam_rows = None  # the fused paths' per-step (len(my_views), 35) camera-gradient rows
             self._cam_params = {}  # the autograd path's pose leaves of this step
         self.exposure = bool(exposure)
+        self.exposure_fused = bool(exposure_fused)
+        if self.exposure_fused and not self.exposure:
+            raise ValueError("exposure_fused without exposure: it selects the HIP device's form of exposure=True")
+        self._expo_dev = False  # the fused path's exposure form runs (exposure_fused on the HIP device)
         if self.exposure:
             if self.dssim_fused:
                 raise ValueError("exposure with dssim_fused: the fused D-SSIM form stages the colours inside its SSIM "
                                  "kernels and has no exposure (use dssim_fused=False)")
+            if self.exposure_fused and self.w_dssim > 0.0:
+                raise ValueError("exposure_fused with dssim_weight > 0: the fused exposure form has no D-SSIM term "
+                                 "(gr_bwd_fit_exposure_gather is the L1 form's)")
             if dev.type == "cuda":
-                raise ValueError("exposure on the HIP device: the fused fit path has no exposure form yet (fit on host "
-                                 "tensors, --device cpu)")
+                if not self.exposure_fused:
+                    raise ValueError("exposure on the HIP device: the fused fit path takes exposure only in its own form "
+                                     "(pass exposure_fused=True / --exposure_fused), or fit on host tensors, --device cpu")
+                self._exposure_check(dev)
+                self._expo_dev = True
             V = len(cams)
             self.exposure_lr = float(exposure_lr)
             self.exposure_fixed = tuple(sorted({int(i) for i in exposure_fixed}))
@@ -679,6 +691,7 @@ class ViewShardedFitter:
                 self._expo_free[i] = 0.0
             self._expo_opt = torch.optim.Adam([self._expo], lr=self.exposure_lr)
             self._expo_leaves = {}  # the exposure leaves of this step
+            self._expo_rows = None  # the fused form's (V, 12) d loss / d E rows of this step (_views_scheduled)
 
     def canonical_params(self) -> dict:
         """The parameters in the stub's order (undoes the trainer's Morton permutation)."""
@@ -731,6 +744,22 @@ class ViewShardedFitter:
         if why is not None:
             raise ValueError(f"density_stats on {device}: the statistics come from the fused fit path only, which "
                              f"this fit does not take: {why}")
+
+    def _exposure_check(self, device) -> None:
+        """exposure_fused on the HIP device needs the fused path (_direct): a fit that would take the per-view autograd
+        path there raises with the reason, as nothing falls back quietly."""
+        why = None
+        if self.render_fn is not hip_render:
+            why = "a custom render_fn"
+        elif not self._images_ok:
+            why = "targets, masks or depths that are not exactly (height, width) float32 images"
+        elif not all(p.dtype == torch.float32 for p in self.params.values()):
+            why = "parameters that are not float32"
+        elif not (FUSED_LOSS and DIRECT_BACKWARD):
+            why = "the fused path switched off (GR_FUSED_LOSS / GR_DIRECT)"
+        if why is not None:
+            raise ValueError(f"exposure_fused on {device}: the exposure form is the fused fit path's, which this fit "
+                             f"does not take: {why}")
 
     def _loss_terms(self, depth: bool, ssim: bool = False) -> tuple:
         """A step's loss terms (w_sil, w_depth, g_scale, w_dssim) as every view path passes them on: the silhouette
@@ -930,6 +959,15 @@ class ViewShardedFitter:
             dist.all_reduce(g, group=self.group)
         self._exposure_update(g)
 
+    def _exposure_step_fused(self) -> None:
+        """_exposure_step_autograd for the fused path's exposure form: the step's (V, 12) rows as the views' kernels
+        wrote them (this rank's; zero elsewhere), on the main stream after it has waited for the render streams.  No host
+        read: the rows, the all-reduce and the update stay on the device."""
+        g, self._expo_rows = self._expo_rows, None
+        if self.world > 1:
+            dist.all_reduce(g, group=self.group)
+        self._exposure_update(g)
+
     def _exposure_update(self, g: torch.Tensor) -> None:
         """Adam on the exposures from the all-reduced (V, 12) gradient (every rank the same arithmetic on the same
         numbers), the rows of exposure_fixed zeroed: a gradient that is always zero leaves its row where it is."""
@@ -1067,7 +1105,7 @@ class ViewShardedFitter:
         return self.dssim_fused and self.w_dssim > 0.0
 
     def _bands_ok(self) -> bool:
-        if self._ssim_form():
+        if self._ssim_form() or self._expo_dev:  # (the exposure form: whole views through the gather entry)
             return False
         V, W = len(self.targets), self.world
         r = V % W if W > 1 else 0
@@ -1407,7 +1445,10 @@ class ViewShardedFitter:
             self._camera_grads_batch(m, s, c, o, batch, js, k)
 
     def _form(self) -> str:
-        """The fused step's form: "ssim" (the D-SSIM form, with or without a depth term), "depth" or "l1"."""
+        """The fused step's form: "exposure" (exposure_fused, with or without a depth term), "ssim" (the D-SSIM form,
+        with or without a depth term), "depth" or "l1"."""
+        if self._expo_dev:
+            return "exposure"
         return "ssim" if self._ssim_form() else "depth" if self._depth_grad() else "l1"
 
     def _direct(self, device) -> bool:
@@ -1441,6 +1482,8 @@ class ViewShardedFitter:
             out = self._fused_param_step(scales, opacities, loss)
             if self.refine_cameras:  # the next step renders with this update
                 self._camera_step_fused(device)
+            if self._expo_dev:
+                self._exposure_step_fused()
             return out
         means, scales, colors, opacities = activations(self.params)
         if self._direct(device) and means.shape[0] > 0:
@@ -1464,6 +1507,8 @@ class ViewShardedFitter:
             out = self._finish_step(loss)
             if self.refine_cameras:
                 self._camera_step_fused(device)
+            if self._expo_dev:
+                self._exposure_step_fused()
             return out
         # HIP renderer: the next view's preparation is enqueued before this view renders, so the
         # host reads each view's pair count while the device is still busy (no idle gap per view);
@@ -1598,7 +1643,7 @@ class ViewShardedFitter:
         the preparation stream (_reg_after_exec; the L1 form's tail_fn: neither before the first view nor between the
         last reduction and the parameter update); the depth and D-SSIM forms of the Python schedule take it as it is."""
         reg_fn = (lambda: reg_t) if reg_t is not None else None
-        if native:
+        if native and not self._expo_dev:  # (the exposure form has no executor entry: the Python schedule)
             total = self._views_native(means, scales, colors, opacities, self._depth_grad(), sized=sized, ssim=self._ssim_form())
             return total, self._reg_after_exec(reg_fn, means.device)
         form = self._form()
@@ -1620,7 +1665,10 @@ class ViewShardedFitter:
                  W and D, the depth-gradient footprint) keeping its saved sums, then gr_bwd_fit_gather (L1 + silhouette
                  + depth loss gradients and the render backward up to the per-Gaussian sums);
           ssim   the D-SSIM form (dssim_fused): gr_bwd_fit_ssim_gather in its place, whose photometric term is
-                 (1 - l) L1 + l D-SSIM; with a depth term the depth form's views, without one _ssim_view's.
+                 (1 - l) L1 + l D-SSIM; with a depth term the depth form's views, without one _ssim_view's;
+          exposure  the exposure form (exposure_fused): gr_bwd_fit_exposure_gather in its place, whose photometric term
+                 is taken on E_i (clamp01(out), 1), E_i read from the device tensor, and which writes row i of
+                 self._expo_rows (d loss / d E); the D-SSIM form's views.
         Every reduction batch of a stream adds its views' gradient w.r.t. the activated parameters into that stream's
         accumulator set (_reduce_batch, in view order: deterministic); the sets leave in self._acc_parts, to be summed
         in stream order by the caller (gr_fit_param_step or torch adds).  Returns (the sum of the view losses (device,
@@ -1639,7 +1687,11 @@ class ViewShardedFitter:
         stats = self._stats_bufs(ns, device) if self.density_stats else None
         if self.refine_cameras:
             self._camera_rows(nv, device)
-        depth = form == "depth" or (form == "ssim" and self._depth_grad())
+        expo = form == "exposure"
+        if expo:  # every view's d loss / d E row (gr_bwd_fit_exposure_gather writes its own; other ranks' stay zero)
+            self._expo_rows = torch.zeros((len(self.targets), 12), dtype=torch.float32, device=device)
+        sums16 = ("ssim", "exposure")  # the forms whose views without a depth term are _ssim_view's (16-pixel tiles)
+        depth = form == "depth" or (form in sums16 and self._depth_grad())
         w_sil, w_depth, g_scale, w_dssim = self._loss_terms(depth, form == "ssim")
         bin_stream = None
         if form == "l1" and BIN_STREAM != "":
@@ -1666,17 +1718,19 @@ class ViewShardedFitter:
             pv = take(j)
             _, _, _, rs = tr.forward_native(m, s, c, o, pv.gv, pv, images=False)  # the backward reads the sums
             pv = None
-            # the two entries take the same operands, the D-SSIM one its weight behind g_scale
+            # the entries take the same operands, the D-SSIM one its weight behind g_scale, the exposure one the view's
+            # E (a row view of the device tensor: no host read) and its row of d loss / d E
             ssim = form == "ssim"
-            gather = tr.backward_fit_ssim_gather_native if ssim else tr.backward_fit_gather_native
-            own = (w_dssim,) if ssim else ()
+            gather = (tr.backward_fit_exposure_gather_native if expo
+                      else tr.backward_fit_ssim_gather_native if ssim else tr.backward_fit_gather_native)
+            own = (self._expo[i], self._expo_rows[i]) if expo else (w_dssim,) if ssim else ()
             sums, sums3 = gather(rs, self.targets[i], self.masks[i] if w_sil > 0.0 else None, w_sil,
                                  self.depths[i] if depth else None, w_depth, g_scale, *own, losses_v[j:j + 1])
             return (rs.gv, sums, sums3) if sums3 is not None else (rs.gv, sums)
 
         gathered = GATHER or form != "l1"
         tail = self._view_loop(
-            device, nv, self._preparer(m, s, c, o, lambda q: self._step_view(views[q], device, depth, form == "ssim"), nv, sized),
+            device, nv, self._preparer(m, s, c, o, lambda q: self._step_view(views[q], device, depth, form in sums16), nv, sized),
             body_l1 if form == "l1" else body_sums,
             lambda k, batch, js, accumulate: self._reduce_batch(m, s, c, o, batch, js, k, acc, stats, accumulate, gathered),
             tail_fn)
@@ -1837,6 +1891,8 @@ class ViewShardedFitter:
         form: the batched and graph steps have none."""
         if self._ssim_form() or self.density_stats:  # (a replayed step that overflowed is redone: its statistics
             return False                             # would count twice, so a fit that collects them steps eagerly)
+        if self.exposure:  # (the exposure form has no batched / captured schedule)
+            return False
         if self.refine_cameras:  # (captured launches carry the view matrices as kernel arguments)
             return False
         mode = self._graph_mode()
@@ -2636,16 +2692,23 @@ def main(argv=None) -> None:
     ap.add_argument("--exposure", action="store_true",
                     help="fit a 3x4 exposure / white-balance transform per training view with the Gaussians (from "
                          "identity; the photometric term compares the transformed render with the target) and write "
-                         "exposures.npz; host tensors only (--device cpu); held-out metrics (--holdout_every) are taken "
-                         "without exposure: held-out views have none, and the metric is of the image rendered from the "
-                         "saved Gaussians; --eval_color_correct is the way to judge held-out views of such photo sets")
+                         "exposures.npz; host tensors (--device cpu), or the HIP device with --exposure_fused; held-out "
+                         "metrics (--holdout_every) are taken without exposure: held-out views have none, and the metric is "
+                         "of the image rendered from the saved Gaussians; --eval_color_correct is the way to judge "
+                         "held-out views of such photo sets")
     ap.add_argument("--exposure_lr", type=float, default=1e-3,
                     help="with --exposure: Adam's learning rate of the exposure matrices")
     ap.add_argument("--exposure_fix", default="0",
                     help="with --exposure: comma list of training-view indices whose exposure stays at identity (they pin "
                          "the overall brightness), or 'none'")
+    ap.add_argument("--exposure_fused", action="store_true",
+                    help="with --exposure on the HIP device: the fused path's exposure form (the exposure matrices read "
+                         "and their gradients written by the render backward's upstream pass; the Python schedule, no "
+                         "D-SSIM term) instead of an error; changes nothing with --device cpu")
     ap.add_argument("--device", default="", help="cpu: host tensors (cpu_renderer, gloo); default: the HIP device")
     args = ap.parse_args(argv)
+    if args.exposure_fused and not args.exposure:
+        ap.error("--exposure_fused requires --exposure")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -2722,7 +2785,8 @@ def main(argv=None) -> None:
     if args.exposure:
         fix = args.exposure_fix.strip().lower()
         fixed = () if fix in ("none", "") else tuple(int(x) for x in fix.split(","))
-        refine.update(exposure=True, exposure_lr=args.exposure_lr, exposure_fixed=fixed)
+        refine.update(exposure=True, exposure_lr=args.exposure_lr, exposure_fixed=fixed,
+                      exposure_fused=args.exposure_fused)
     params = build_params(args.num_gaussians, device, args.use_sh, args.sh_degree)
     fitter = ViewShardedFitter(params, cams, targets, args.width, args.height, lr=args.lr, masks=masks, depths=depths,
                                silhouette_weight=args.silhouette_weight, depth_weight=args.depth_weight,

@@ -512,9 +512,10 @@ def forward_native(means, scales, colors, opacities, gv: _native.GrView, prepare
     return out, alpha, depth, RenderState(gv, n, plan, geom, bins, saved)
 
 
-def _bwd_ws(L, gv: _native.GrView, n: int, plan, dev, ssim: bool = False) -> torch.Tensor:
-    """A view's backward workspace: gr_bwd_bytes, or with ``ssim`` the D-SSIM entries' gr_bwd_ssim_bytes."""
-    size = L.gr_bwd_ssim_bytes if ssim else L.gr_bwd_bytes
+def _bwd_ws(L, gv: _native.GrView, n: int, plan, dev, ssim: bool = False, exposure: bool = False) -> torch.Tensor:
+    """A view's backward workspace: gr_bwd_bytes, or with ``ssim`` the D-SSIM entries' gr_bwd_ssim_bytes, with
+    ``exposure`` the exposure entry's gr_bwd_exposure_bytes."""
+    size = L.gr_bwd_ssim_bytes if ssim else (L.gr_bwd_exposure_bytes if exposure else L.gr_bwd_bytes)
     return torch.empty((_ws_round(size(ctypes.byref(gv), n, ctypes.byref(plan))),), dtype=torch.uint8, device=dev)
 
 
@@ -526,13 +527,15 @@ def _check_targets(gv: _native.GrView, target, mask, depth_target, dev) -> None:
     _check_operand(depth_target, hw, "depth_target", dev)
 
 
-def _view_loss(target, mask, w_sil: float, g_scale: float, loss_out, depth=None, w_dssim=None) -> list:
+def _view_loss(target, mask, w_sil: float, g_scale: float, loss_out, depth=None, w_dssim=None, exposure=None) -> list:
     """The view-loss group of a backward entry, in the ABI's order: ``depth`` = (depth_target, w_depth) for the entries
-    with a depth term, ``w_dssim`` for the D-SSIM entries."""
+    with a depth term, ``w_dssim`` for the D-SSIM entries, ``exposure`` = (exposure, d_exposure) for the exposure entry."""
     f = ctypes.c_float
     return ([_native.ptr(target), _native.ptr(mask), f(w_sil)]
             + ([_native.ptr(depth[0]), f(depth[1])] if depth is not None else [])
-            + [f(g_scale)] + ([f(w_dssim)] if w_dssim is not None else []) + [_native.ptr(loss_out)])
+            + [f(g_scale)] + ([f(w_dssim)] if w_dssim is not None else [])
+            + ([_native.ptr(exposure[0]), _native.ptr(exposure[1])] if exposure is not None else [])
+            + [_native.ptr(loss_out)])
 
 
 def _backward_call(entry: str, st: RenderState, dev, loss: list, params=None, grads=None, accumulate=None, index=None,
@@ -542,7 +545,7 @@ def _backward_call(entry: str, st: RenderState, dev, loss: list, params=None, gr
     gradients (and ``accumulate``), the workspace, the gathered sums, the stream; a group the entry does not have is
     None.  Returns the workspace it allocated."""
     L = _native.lib()
-    ws = _bwd_ws(L, st.gv, st.n, st.plan, dev, ssim="ssim" in entry)
+    ws = _bwd_ws(L, st.gv, st.n, st.plan, dev, ssim="ssim" in entry, exposure="exposure" in entry)
     args = [ctypes.byref(st.gv), st.n, ctypes.byref(st.plan)]
     if params is not None:
         means, scales, colors, opacities = params
@@ -782,6 +785,30 @@ def backward_fit_ssim_gather_native(st: RenderState, target, mask, w_sil: float,
     return _backward_gather("gr_bwd_fit_ssim_gather", st, target, mask, depth_target,
                             _view_loss(target, mask, w_sil, g_scale, loss_out, (depth_target, w_depth), w_dssim),
                             depth_target is not None)
+
+
+def backward_fit_exposure_gather_native(st: RenderState, target, mask, w_sil: float, depth_target, w_depth: float,
+                                        g_scale: float, exposure, d_exposure, loss_out):
+    """gr_bwd_fit_exposure_gather on the current stream: ``backward_fit_gather_native`` with the photometric term on the
+    exposed colour ``y = E[:, :3] clamp01(out) + E[:, 3]``, E = ``exposure`` (12 float32 on the view's device, row-major
+    3 x 4, read by the kernel: no host copy); ``d_exposure`` (12 float32, overwritten) gets the gradient of ``g_scale`` x
+    the view loss with respect to E.  Returns (sums (n, 8), depth sums (n,) or None without a depth target) for
+    reduce_sums_native."""
+    dev = st.saved.device
+    _check_exposure(exposure, "exposure", dev)
+    _check_exposure(d_exposure, "d_exposure", dev)
+    return _backward_gather("gr_bwd_fit_exposure_gather", st, target, mask, depth_target,
+                            _view_loss(target, mask, w_sil, g_scale, loss_out, (depth_target, w_depth),
+                                       exposure=(exposure, d_exposure)),
+                            depth_target is not None)
+
+
+def _check_exposure(t, name: str, dev) -> None:
+    """A view's exposure operand: 12 contiguous float32 on ``dev`` ((12,) or (3, 4): a row of the fitter's (V, 12))."""
+    if not isinstance(t, torch.Tensor) or t.numel() != 12:
+        raise ValueError(f"{name}: expected a contiguous float32 tensor of 12 elements on {dev}, got "
+                         f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)}")
+    _check_operand(t, tuple(t.shape), name, dev)
 
 
 def _sums_views(batch, n: int, dev):

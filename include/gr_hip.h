@@ -406,6 +406,34 @@ gr_status gr_bwd_fit_ssim_gather(const gr_view* v, int n, const gr_plan* plan, c
                                  const float* target_depth, float w_depth, float g_scale, float w_dssim,
                                  float* loss_out, void* ws, size_t ws_bytes, float* sums, float* sums3, void* stream);
 
+/* gr_bwd_fit_gather for a view with its own exposure (an extension: the reference fit loop compares the render with
+ * the photo as it is, fit_multiview_stub.py:292-299; photo sets differ in exposure and white balance per view).  The
+ * photometric term is taken on the exposed colour,
+ *   x_j = clamp(out_j, 0, 1),  y_k = E[k][0] x_0 + E[k][1] x_1 + E[k][2] x_2 + E[k][3]   (y not clamped)
+ *   loss = mean|y - target_rgb| + w_sil mean|alpha - target_mask| + w_depth mean|depth / (max(depth) + 1e-6) - target_depth|
+ * with E = `exposure`, 12 device floats (row-major 3 x 4) read by the kernel: no host read, no synchronisation.  One
+ * kernel per 16 x 16 tile in k_pixel_grads' place writes the splat's upstream operands (colour j receives
+ * sum_k E[k][j] sign(y_k - t_k) g_scale / (3 HW) through x_j's clamp mask), the tile's loss sums and the tile's 12
+ * sums of sign(y_k - t_k) x_j | 1; the last tile to arrive totals both over the tiles in double in a fixed order and
+ * writes the view loss and
+ *   d_exposure[k][j] = g_scale / (3 HW) sum_p sign(y_k - t_k) (x_j | 1)          (12 device floats, overwritten)
+ * the gradient of g_scale x loss with respect to E.  Then the splat and the gather as gr_bwd_fit_gather.
+ *   - E = [I | 0]: sums, sums3 and the loss are gr_bwd_fit_gather's bit for bit
+ *   - the view: 16-pixel tiles, whole (tile = 32 and rows > 0 are rejected as by gr_bwd), rendered by gr_fwd_render
+ *     with no_depth_grad = 1 or 2 without a depth target, 0 with one
+ *   - ws: gr_bwd_exposure_bytes (gr_bwd_bytes plus the per-tile exposure sums); shorter: GR_ERR_WORKSPACE
+ *   - a null target_rgb, sums, exposure or d_exposure: GR_ERR_INVALID_ARGUMENT; nothing is launched on a refusal
+ *   - a view without pairs still gets its loss and d_exposure (the background's) and zero sums
+ *   - stream-ordered, no allocation, no atomics on the sums: deterministic; the bins' arrival ticket is left zero;
+ *     n == 0: no-op
+ *   - no D-SSIM term, no chain-rule (non-gather) entry, no gr_fit_views form */
+size_t gr_bwd_exposure_bytes(const gr_view* v, int n, const gr_plan* plan);
+gr_status gr_bwd_fit_exposure_gather(const gr_view* v, int n, const gr_plan* plan, const void* geom, const void* bins,
+                                     const float* saved, const float* target_rgb, const float* target_mask,
+                                     float w_sil, const float* target_depth, float w_depth, float g_scale,
+                                     const float* exposure, float* d_exposure, float* loss_out, void* ws,
+                                     size_t ws_bytes, float* sums, float* sums3, void* stream);
+
 /* The fit step's views in one call: the per-view schedule of 3dgaussian_amd/fit_multiview.py
  * (fit_multiview_stub.py:277-310 across several HIP streams) as native host code
  * (3dgaussian_amd/csrc/gr_fit_exec.cpp).  Per view: its preparation ahead on the executor's preparation
