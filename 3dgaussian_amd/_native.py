@@ -209,6 +209,8 @@ _SIG = {
     "gr_bwd_exposure_bytes": (_Z, _VIEW),
     # g_scale, exposure, d_exposure, loss_out
     "gr_bwd_fit_exposure_gather": (_I, _VIEW + _STATE + _L1 + _DEPTH + [_F, _P, _P, _P] + _WS + _SUMS + [_P]),
+    # g_scale, target_weight, loss_out
+    "gr_bwd_fit_weighted_gather": (_I, _VIEW + _STATE + _L1 + _DEPTH + [_F, _P, _P] + _WS + _SUMS + [_P]),
     "gr_fit_views_ssim": (_I, _EXEC + _PARAMS + [_F, _F, _F, _F, _P, _PA, _P]),
     "gr_reduce_sums": (_I, [_I, ctypes.POINTER(GrSumsView), _I] + _PARAMS + _GRADS + [_I, _P]),
     "gr_density_stats": (_I, [_I, ctypes.POINTER(GrSumsView), _I, _P, _P, _P, _F, _P, _P]),

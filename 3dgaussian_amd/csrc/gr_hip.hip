@@ -22,6 +22,9 @@
 //                    tile, its gradient added to the L1 term's per pixel (gr_bwd_fit_ssim; no gradient image).
 //   k_pixel_grads_expo  k_pixel_grads of a fit with per-view exposure: the L1 term on E (x, 1), E read from the device;
 //                    12 sums per tile, d loss / d E by the last tile to arrive (gr_bwd_fit_exposure_gather).
+//   k_pixel_grads_wgt   k_pixel_grads of a fit with per-pixel loss weights: every L1 term and its gradient times the
+//                    pixel's weight, read from a plane of its own (gr_bwd_fit_weighted_gather); k_depth_tile_sums_wgt
+//                    the depth loss's weighted tile sums beside it.
 //   k_raster_bwd_bf16   per work item: the two K = 16 contractions (over x, over y) of U with the
 //                    Gaussians' exponentials; 8- or 9-float partial rows at the pairs' sorted positions.
 //   k_gather_view    per Gaussian: its rows (through pos_of) summed in a fixed order (deterministic, no
@@ -2187,16 +2190,20 @@ __device__ __forceinline__ float sign0(float t) { return t > 0.0f ? 1.0f : (t < 
 // receives sum_k E[k][j] sign(y_k - t_k) g / (3 HW) through x_j's clamp mask; xp keeps the signs and x for dE.
 // With E = [I | 0] every product below is exact (1 a = a, 0 a = 0 for the finite a here) and every sum adds zeros, so
 // the values are those of the plain form whether or not the compiler contracts a product and a sum into an fma.
+// WGT (k_pixel_grads_wgt): the pixel's loss weight w >= 0 multiplies its three L1 terms and, last,
+// their gradient constants; the arg-max share dscal[1] already carries the weighted sum (k_depth_tile_sums_wgt).  With
+// w = 1 every product is exact (1 a = a), so the values are the plain form's, contracted into an fma or not.
 struct ExpoPixel {
   float E[12];                    // the view's 3 x 4 exposure, row-major
   float sg[3] = {0.f, 0.f, 0.f};  // sign0(y_k - t_k); zero outside the image
   float x[3] = {0.f, 0.f, 0.f};   // clamp01(out_j)
 };
-template <bool SSIM = false, bool EXPO = false>
+template <bool SSIM = false, bool EXPO = false, bool WGT = false>
 __device__ __forceinline__ void pixel_upstream(const ViewK& v, int p, float4 s, float Dp, const float* __restrict__ g_rgb,
                                                const float* __restrict__ g_alpha, const float* __restrict__ g_depth,
                                                const L1Args& l1, float (&u)[5], float& l_rgb, float& l_sil,
-                                               const float* g_ssim = nullptr, ExpoPixel* xp = nullptr) {
+                                               const float* g_ssim = nullptr, ExpoPixel* xp = nullptr, float w = 1.0f) {
+  static_assert(!(WGT && (SSIM || EXPO)), "the weighted form is the L1 form's: no D-SSIM term, no exposure");
   const float den = 1.0f + s.x, dden = s.x + 1e-6f;
   // one correctly rounded reciprocal of the finalize's denominator instead of ten divisions (each ~10 VALU): the
   // quotients below are products with it, within 1 ulp of the divisions (round 6, the L1 epilogue of the fit forwards)
@@ -2235,9 +2242,14 @@ __device__ __forceinline__ void pixel_upstream(const ViewK& v, int p, float4 s, 
       float gk;
       if (l1.t_rgb) {
         const float t = clamp01(r) - l1.t_rgb[3 * p + k];
-        l_rgb += fabsf(t);
+        if constexpr (WGT)
+          l_rgb += w * fabsf(t);
+        else
+          l_rgb += fabsf(t);
         if constexpr (SSIM)
           gk = sign0(t) * (((1.0f - l1.w_dssim) * l1.g_scale) / (3.0f * HWf)) + g_ssim[k];
+        else if constexpr (WGT)
+          gk = (sign0(t) * (l1.g_scale / (3.0f * HWf))) * w;
         else
           gk = sign0(t) * (l1.g_scale / (3.0f * HWf));
       } else {
@@ -2255,6 +2267,10 @@ __device__ __forceinline__ void pixel_upstream(const ViewK& v, int p, float4 s, 
     const float t = clamp01(al) - l1.t_mask[p];
     l_sil = fabsf(t);
     ga = sign0(t) * ((l1.w_sil * l1.g_scale) / HWf);
+    if constexpr (WGT) {
+      l_sil *= w;
+      ga *= w;
+    }
     has_a = true;
   } else if (g_alpha) {
     ga = g_alpha[p];
@@ -2268,7 +2284,10 @@ __device__ __forceinline__ void pixel_upstream(const ViewK& v, int p, float4 s, 
       if (dfit) {  // d (w_depth mean|d / (M + 1e-6) - t|) / d depth, plus the max's share on arg-max pixels
         const float M = l1.dscal[0], dm = M + 1e-6f;
         const float t = d / dm - l1.t_depth[p];
-        gd = (sign0(t) * ((l1.w_depth * l1.g_scale) / HWf)) / dm;
+        if constexpr (WGT)
+          gd = ((sign0(t) * ((l1.w_depth * l1.g_scale) / HWf)) * w) / dm;
+        else
+          gd = (sign0(t) * ((l1.w_depth * l1.g_scale) / HWf)) / dm;
         if (d == M) gd += l1.dscal[1];
       } else {
         gd = g_depth[p];
@@ -2338,12 +2357,15 @@ __global__ __launch_bounds__(256) void k_depth_tile_max_views(VBatch<k_depth_til
 __device__ void depth_final(const float* __restrict__ tile_loss, const float* __restrict__ tile_aux, int tiles, int64_t HW,
                             float w_depth, float g_scale, float* __restrict__ dscal, double (*r)[256]);
 // Per tile the depth loss's sums; the last tile to finish (arrive_last_tile) turns them into the max's
-// gradient per arg-max pixel (depth_final).
+// gradient per arg-max pixel (depth_final).  WGT (k_depth_tile_sums_wgt): the loss term and the max's chain term times
+// the pixel's weight wgt[p]; the arg-max count is not weighted.
+template <bool WGT = false>
 __device__ __forceinline__ void k_depth_tile_sums_body(ViewK v, const float4* __restrict__ saved4,
                                                          const float* __restrict__ savedD, const float* __restrict__ t_depth,
                                                          float* __restrict__ dscal, float* __restrict__ tile_loss,
                                                          float* __restrict__ tile_aux, int64_t HW, float w_depth,
-                                                         float g_scale, int* __restrict__ ticket, const BI blockIdx, const BI gridDim) {
+                                                         float g_scale, int* __restrict__ ticket, const BI blockIdx, const BI gridDim,
+                                                         const float* __restrict__ wgt = nullptr) {
   const int tile = blockIdx.x, tid = threadIdx.x;
   const int tx = tile % v.tiles_x, ty = tile / v.tiles_x;
   const int x = tx * T + (tid & (T - 1)), y = ty * T + (tid >> 4);
@@ -2354,6 +2376,11 @@ __device__ __forceinline__ void k_depth_tile_sums_body(ViewK v, const float4* __
     const float t = d / dm - t_depth[p];
     l = fabsf(t);
     sd = sign0(t) * ((d / dm) / dm);
+    if constexpr (WGT) {
+      const float w = wgt[p];
+      l *= w;
+      sd *= w;
+    }
     cnt = d == M ? 1.0f : 0.0f;
   }
 #pragma unroll
@@ -2402,6 +2429,17 @@ __global__ __launch_bounds__(256) void k_depth_tile_sums(k_depth_tile_sums_args 
 __global__ __launch_bounds__(256) void k_depth_tile_sums_views(VBatch<k_depth_tile_sums_args> B) {
   const VBlock b = vbatch_block(B);
   k_depth_tile_sums_run(B.a[b.view], b);
+}
+// k_depth_tile_sums of a fit with per-pixel loss weights (gr_bwd_fit_weighted_gather).  One view per launch.
+struct k_depth_tile_sums_wgt_args {
+  k_depth_tile_sums_args a;
+  const float* wgt;  // (H,W) loss weights
+};
+__global__ __launch_bounds__(256) void k_depth_tile_sums_wgt(k_depth_tile_sums_wgt_args e) {
+  const k_depth_tile_sums_args& a = e.a;
+  const VBlock b = own_block();
+  k_depth_tile_sums_body<true>(a.v, a.saved4, a.savedD, a.t_depth, a.dscal, a.tile_loss, a.tile_aux, a.HW, a.w_depth, a.g_scale,
+                               a.ticket, b.block, b.grid, e.wgt);
 }
 
 
@@ -2547,13 +2585,16 @@ __device__ __forceinline__ void tile_expo_total(const float* __restrict__ tile_s
 // With the fit loss (l1.t_rgb) the last tile to finish (arrive_last_tile) also writes the view loss.
 // EXPO (k_pixel_grads_expo): the fit loss on the exposed colour (pixel_upstream<false, true>; l1.t_rgb, l1.tile_loss and
 // l1.loss_out are set); the last tile also writes d_E.
-template <bool EXPO = false>
+// WGT (k_pixel_grads_wgt): the fit loss with the pixel's weight wgt[p] (pixel_upstream<false, false, true>); the sums,
+// the fragments and the last tile's view loss as in the plain form.
+template <bool EXPO = false, bool WGT = false>
 __device__ __forceinline__ void k_pixel_grads_body(ViewK v, const float4* __restrict__ saved4,
                                                      const float* __restrict__ savedD, const float* __restrict__ g_rgb,
                                                      const float* __restrict__ g_alpha, const float* __restrict__ g_depth,
                                                      uint4* __restrict__ UF, int pieces, L1Args l1, bool depth,
                                                      int* __restrict__ ticket, const BI blockIdx, const BI gridDim,
-                                                     ExpoArgs ex = ExpoArgs{}) {
+                                                     ExpoArgs ex = ExpoArgs{}, const float* __restrict__ wgt = nullptr) {
+  static_assert(!(EXPO && WGT), "the weighted form has no exposure");
   const int tile = blockIdx.x, tid = threadIdx.x;
   const int tx = tile % v.tiles_x, ty = tile / v.tiles_x;
   const int x = tx * T + (tid & (T - 1)), y = ty * T + (tid >> 4);
@@ -2569,6 +2610,13 @@ __device__ __forceinline__ void k_pixel_grads_body(ViewK v, const float4* __rest
     }
     tile_loss_sums(tile, tid, l_rgb, l_sil, l1.tile_loss);
     tile_expo_sums(tile, tid, xp, ex.tile_sums);
+  } else if constexpr (WGT) {
+    if (x < v.W && y < v.H) {
+      const int p = y * v.W + x;
+      pixel_upstream<false, false, true>(v, p, saved4[p], savedD[p], nullptr, nullptr, nullptr, l1, u, l_rgb, l_sil, nullptr,
+                                         nullptr, wgt[p]);
+    }
+    tile_loss_sums(tile, tid, l_rgb, l_sil, l1.tile_loss);
   } else {
     if (x < v.W && y < v.H) {
       const int p = y * v.W + x;
@@ -2629,6 +2677,18 @@ __global__ __launch_bounds__(256) void k_pixel_grads_expo(k_pixel_grads_expo_arg
   const VBlock b = own_block();
   k_pixel_grads_body<true>(a.v, a.saved4, a.savedD, nullptr, nullptr, nullptr, a.UF, a.pieces, a.l1, a.depth, a.ticket, b.block,
                            b.grid, e.ex);
+}
+// k_pixel_grads of a fit with per-pixel loss weights (gr_bwd_fit_weighted_gather): the fit loss's terms and gradients
+// times the pixel's weight, the view loss by the last tile to arrive.  One view per launch (no batched form).
+struct k_pixel_grads_wgt_args {
+  k_pixel_grads_args a;  // g_rgb / g_alpha / g_depth unused (the fit loss)
+  const float* wgt;      // (H,W) loss weights
+};
+__global__ __launch_bounds__(256) void k_pixel_grads_wgt(k_pixel_grads_wgt_args e) {
+  const k_pixel_grads_args& a = e.a;
+  const VBlock b = own_block();
+  k_pixel_grads_body<false, true>(a.v, a.saved4, a.savedD, nullptr, nullptr, nullptr, a.UF, a.pieces, a.l1, a.depth, a.ticket,
+                                  b.block, b.grid, ExpoArgs{}, e.wgt);
 }
 
 
@@ -6146,6 +6206,10 @@ struct ViewLoss {
   bool expo_entry = false;
   const float* exposure = nullptr;
   float* d_exposure = nullptr;
+  // gr_bwd_fit_weighted_gather (the workspace of gr_bwd_bytes): every L1 term times the pixel's loss weight t_weight[p]
+  // (k_pixel_grads_wgt in k_pixel_grads' place, k_depth_tile_sums_wgt in k_depth_tile_sums')
+  bool wgt_entry = false;
+  const float* t_weight = nullptr;  // (H,W), finite and >= 0
 };
 // One backward of a view (bwd_impl): what every entry has first (the view, its render state, the workspace), then what
 // an entry names; the chain rule into `grads`, or with `sums` the per-Gaussian sums to the caller.
@@ -6572,7 +6636,11 @@ static gr_status bwd_impl(const BwdRequest& r) {
   int* ticket = b.ticket;
   if (dfit) {
     launch_one(k_depth_tile_max, dim3(tiles), 256, 0, s, depth_tile_max_args(c, saved));
-    launch_one(k_depth_tile_sums, dim3(tiles), 256, 0, s, depth_tile_sums_args(c, saved, t_depth, vl.w_depth, vl.g_scale));
+    if (vl.wgt_entry)
+      launch_one(k_depth_tile_sums_wgt, dim3(tiles), 256, 0, s,
+                 k_depth_tile_sums_wgt_args{depth_tile_sums_args(c, saved, t_depth, vl.w_depth, vl.g_scale), vl.t_weight});
+    else
+      launch_one(k_depth_tile_sums, dim3(tiles), 256, 0, s, depth_tile_sums_args(c, saved, t_depth, vl.w_depth, vl.g_scale));
     GR_HIP_TRY(hipGetLastError());
   }
   const bool depth = g_depth != nullptr || dfit;  // an upstream depth gradient reaches the splat
@@ -6597,6 +6665,11 @@ static gr_status bwd_impl(const BwdRequest& r) {
     launch_one(k_pixel_grads_expo, dim3(tiles), 256, 0, s,
                k_pixel_grads_expo_args{pixel_grads_args(c, saved, nullptr, nullptr, nullptr, pieces, l1, depth),
                                        ExpoArgs{vl.exposure, tile_sums, vl.d_exposure}});
+    GR_HIP_TRY(hipGetLastError());
+  } else if (vl.wgt_entry) {
+    // without a pair the launch still writes the view loss (the weighted distance of the background)
+    launch_one(k_pixel_grads_wgt, dim3(tiles), 256, 0, s,
+               k_pixel_grads_wgt_args{pixel_grads_args(c, saved, nullptr, nullptr, nullptr, pieces, l1, depth), vl.t_weight});
     GR_HIP_TRY(hipGetLastError());
   } else if (num_pairs > 0 || t_rgb) {
     launch_one(k_pixel_grads, dim3(tiles), 256, 0, s,
@@ -6755,6 +6828,23 @@ gr_status gr_bwd_fit_exposure_gather(const gr_view* v, int n, const gr_plan* pla
   r.loss.expo_entry = true;
   r.loss.exposure = exposure;
   r.loss.d_exposure = d_exposure;
+  r.sums = sums;
+  r.sums3 = sums3;
+  return bwd_impl(r);
+}
+
+gr_status gr_bwd_fit_weighted_gather(const gr_view* v, int n, const gr_plan* plan, const void* geom, const void* bins,
+                                     const float* saved, const float* target_rgb, const float* target_mask, float w_sil,
+                                     const float* target_depth, float w_depth, float g_scale, const float* target_weight,
+                                     float* loss_out, void* ws, size_t ws_bytes, float* sums, float* sums3,
+                                     void* stream) {
+  if (!target_rgb) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_bwd_fit_weighted_gather: target_rgb is null");
+  if (!sums) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_bwd_fit_weighted_gather: sums is null");
+  if (!target_weight) return set_error(GR_ERR_INVALID_ARGUMENT, "gr_bwd_fit_weighted_gather: target_weight is null");
+  BwdRequest r{v, n, plan, geom, bins, saved, ws, ws_bytes, stream};
+  r.loss = {target_rgb, target_mask, w_sil, target_depth, w_depth, g_scale, loss_out};
+  r.loss.wgt_entry = true;
+  r.loss.t_weight = target_weight;
   r.sums = sums;
   r.sums3 = sums3;
   return bwd_impl(r);

@@ -430,6 +430,31 @@ def _fit_images(name: str, imgs: Optional[list], shape: tuple, device) -> tuple:
     return [torch.as_tensor(t).to(device=device, dtype=torch.float32).contiguous() for t in imgs], True
 
 
+def _fit_weights(weights: Optional[list], count: int, shape: tuple, device) -> tuple:
+    """The per-pixel loss weights of a fit (ViewShardedFitter(weights=...)), checked once: one map per training view,
+    exactly ``shape`` = (H, W), a real floating-point dtype, finite and >= 0 after conversion to float32.  Returns
+    (maps, ok) as _fit_images does (float32, contiguous, on ``device``)."""
+    if weights is None:
+        return None, True
+    weights = list(weights)
+    if len(weights) != count:
+        raise ValueError(f"weights: expected one map per training view ({count}), got {len(weights)}")
+    maps = []
+    for i, w in enumerate(weights):
+        w = torch.as_tensor(w)
+        if tuple(w.shape) != tuple(shape):
+            raise ValueError(f"weights[{i}]: expected shape {tuple(shape)} (height, width), got {tuple(w.shape)}")
+        if not w.is_floating_point():
+            raise ValueError(f"weights[{i}]: expected a floating-point dtype (converted to float32), got {w.dtype}")
+        w = w.detach().to(dtype=torch.float32)
+        if not bool(torch.isfinite(w).all()):
+            raise ValueError(f"weights[{i}]: every weight must be finite (a NaN or an infinity after conversion to float32)")
+        if bool((w < 0).any()):
+            raise ValueError(f"weights[{i}]: every weight must be >= 0, got a minimum of {float(w.min()):g}")
+        maps.append(w)
+    return _fit_images("weights", maps, tuple(shape), device)
+
+
 def _batch_sizes(ns: int, nviews: int, tail: Optional[int] = None) -> list:
     """Per stream (views j = k, k + ns, ...): its views' reduction batches, near-equal and at most REDUCE_BATCH, in
     the order they fill; a short last batch of REDUCE_TAIL views (the reductions left when the renders end run alone).
@@ -560,7 +585,7 @@ class ViewShardedFitter:
                  render_fn: RenderFn = hip_render, group=None, reorder: bool = True, dssim_weight: float = 0.0,
                  dssim_fused: bool = False, density_stats: bool = False, refine_cameras: bool = False,
                  camera_lr: float = 1e-3, camera_fixed: tuple = (0,), exposure: bool = False, exposure_lr: float = 1e-3,
-                 exposure_fixed: tuple = (0,), exposure_fused: bool = False):
+                 exposure_fixed: tuple = (0,), exposure_fused: bool = False, weights: Optional[list] = None):
         # dssim_weight l > 0: a view's photometric term is (1 - l) mean|pred - tgt| + l dssim(pred, tgt)
         # (losses.dssim_loss) on the per-view autograd path; 0 (default): the L1 fit, every path as it was
         # dssim_fused (with l > 0, the HIP render op): the fused path's D-SSIM form (_views_scheduled or the native
@@ -578,6 +603,13 @@ class ViewShardedFitter:
         # leave the fused path; exposure_fused opts into the fused path's exposure form (_views_scheduled's "exposure":
         # gr_bwd_fit_exposure_gather per view reads E from the device and writes d loss / d E, the Python schedule with
         # the fused parameter step only, no D-SSIM term); on host tensors it changes nothing.  evaluate() renders without E
+        # weights: per-pixel loss weights, one (H, W) map per training view, finite and >= 0: every L1 term of pixel p
+        # (photometric, silhouette, depth) counts weights[i][p] times, the means keep their denominators 3 HW / HW (ones
+        # are the fit without weights bit for bit, 0 a pixel the fit does not see); the depth maximum and its arg-max
+        # count stay unweighted.  On host tensors element-wise in view_loss (with or without exposure); on the HIP device
+        # the fused path's weighted form (_views_scheduled's "weighted": gr_bwd_fit_weighted_gather per view, the Python
+        # schedule with the fused parameter step).  No D-SSIM term; evaluate(), contribution_state() and error_state()
+        # do not see the weights
         # reorder: keep the Gaussians in spatial (Morton) order, re-established after every
         # densify/prune (spatial_order); off only to compare with an unpermuted run
         # perm: self.params[k][i] = canonical[k][perm[i]], the canonical order being the stub's (the
@@ -599,8 +631,10 @@ class ViewShardedFitter:
         targets, ok_t = _fit_images("targets", targets, (height, width, 3), dev)
         masks, ok_m = _fit_images("masks", masks, (height, width), dev)
         depths, ok_d = _fit_images("depths", depths, (height, width), dev)
-        self._images_ok = ok_t and ok_m and ok_d  # the fused path's exact-shape precondition
+        weights, ok_w = _fit_weights(weights, len(targets), (height, width), dev)
+        self._images_ok = ok_t and ok_m and ok_d and ok_w  # the fused path's exact-shape precondition
         self.cams, self.targets, self.masks, self.depths = cams, targets, masks, depths
+        self.weights = weights
         self.width, self.height, self.lr = width, height, lr
         self.w_sil, self.w_depth = silhouette_weight, depth_weight
         if not 0.0 <= dssim_weight <= 1.0:
@@ -692,6 +726,17 @@ class ViewShardedFitter:
             self._expo_opt = torch.optim.Adam([self._expo], lr=self.exposure_lr)
             self._expo_leaves = {}  # the exposure leaves of this step
             self._expo_rows = None  # the fused form's (V, 12) d loss / d E rows of this step (_views_scheduled)
+        self._wgt_dev = False  # the fused path's weighted form runs (weights on the HIP device)
+        if self.weights is not None:
+            if self.w_dssim > 0.0:
+                raise ValueError("weights with dssim_weight > 0: the weighted D-SSIM map is not built (the weights are the "
+                                 "L1 terms')")
+            if dev.type == "cuda":
+                if self.exposure_fused:
+                    raise ValueError("weights with exposure_fused: the fused exposure form has no loss weights "
+                                     "(gr_bwd_fit_weighted_gather is the L1 form's); fit on host tensors, --device cpu")
+                self._weights_check(dev)
+                self._wgt_dev = True
 
     def canonical_params(self) -> dict:
         """The parameters in the stub's order (undoes the trainer's Morton permutation)."""
@@ -760,6 +805,22 @@ class ViewShardedFitter:
         if why is not None:
             raise ValueError(f"exposure_fused on {device}: the exposure form is the fused fit path's, which this fit "
                              f"does not take: {why}")
+
+    def _weights_check(self, device) -> None:
+        """weights on the HIP device need the fused path (_direct): a fit that would take the per-view autograd path
+        there raises with the reason, as nothing falls back quietly."""
+        why = None
+        if self.render_fn is not hip_render:
+            why = "a custom render_fn"
+        elif not self._images_ok:
+            why = "targets, masks or depths that are not exactly (height, width) float32 images"
+        elif not all(p.dtype == torch.float32 for p in self.params.values()):
+            why = "parameters that are not float32"
+        elif not (FUSED_LOSS and DIRECT_BACKWARD):
+            why = "the fused path switched off (GR_FUSED_LOSS / GR_DIRECT)"
+        if why is not None:
+            raise ValueError(f"weights on {device}: the weighted form is the fused fit path's, which this fit does not "
+                             f"take: {why}")
 
     def _loss_terms(self, depth: bool, ssim: bool = False) -> tuple:
         """A step's loss terms (w_sil, w_depth, g_scale, w_dssim) as every view path passes them on: the silhouette
@@ -1105,8 +1166,8 @@ class ViewShardedFitter:
         return self.dssim_fused and self.w_dssim > 0.0
 
     def _bands_ok(self) -> bool:
-        if self._ssim_form() or self._expo_dev:  # (the exposure form: whole views through the gather entry)
-            return False
+        if self._ssim_form() or self._expo_dev or self._wgt_dev:  # (the exposure and weighted forms: whole views
+            return False                                            # through their gather entries)
         V, W = len(self.targets), self.world
         r = V % W if W > 1 else 0
         if not (BAND_SPLIT and r and not self._depth_grad()):
@@ -1256,7 +1317,13 @@ class ViewShardedFitter:
             E = self._exposure_leaf(i).to(pred.device)
             y = pred[..., 0:1] * E[:, 0] + pred[..., 1:2] * E[:, 1] + pred[..., 2:3] * E[:, 2] + E[:, 3]
             pred = torch.empty_like(pred).copy_(y)
-        if self.w_dssim > 0.0:
+        wgt = None if self.weights is None else self.weights[i]
+        if wgt is not None:
+            # every L1 term of pixel p times its weight, the means over all 3 HW / HW elements (ones: the same bits)
+            loss = torch.mean(wgt[..., None] * torch.abs(pred - self.targets[i]))
+            if use_sil:
+                loss = loss + self.w_sil * torch.mean(wgt * torch.abs(alpha - self.masks[i]))
+        elif self.w_dssim > 0.0:
             # (1 - l) L1 + l D-SSIM for the photometric term; the silhouette term as below
             lam = self.w_dssim
             if self.render_fn is hip_render and pred.device.type == "cuda" and FUSED_LOSS:
@@ -1277,7 +1344,10 @@ class ViewShardedFitter:
                 loss = loss + self.w_sil * torch.mean(torch.abs(alpha - self.masks[i]))
         if self.depths is not None and self.w_depth > 0.0:
             d_pred = depth / (depth.max() + 1e-6)
-            loss = loss + self.w_depth * torch.mean(torch.abs(d_pred - self.depths[i]))
+            if wgt is not None:  # (the maximum over all pixels, unweighted: autograd gives its weighted chain term)
+                loss = loss + self.w_depth * torch.mean(wgt * torch.abs(d_pred - self.depths[i]))
+            else:
+                loss = loss + self.w_depth * torch.mean(torch.abs(d_pred - self.depths[i]))
         return loss
 
     # ---- the fused path's streams, kept buffers and its one per-view schedule ------------------------------------
@@ -1445,10 +1515,12 @@ class ViewShardedFitter:
             self._camera_grads_batch(m, s, c, o, batch, js, k)
 
     def _form(self) -> str:
-        """The fused step's form: "exposure" (exposure_fused, with or without a depth term), "ssim" (the D-SSIM form,
-        with or without a depth term), "depth" or "l1"."""
+        """The fused step's form: "exposure" (exposure_fused, with or without a depth term), "weighted" (weights, with
+        or without a depth term), "ssim" (the D-SSIM form, with or without a depth term), "depth" or "l1"."""
         if self._expo_dev:
             return "exposure"
+        if self._wgt_dev:
+            return "weighted"
         return "ssim" if self._ssim_form() else "depth" if self._depth_grad() else "l1"
 
     def _direct(self, device) -> bool:
@@ -1643,7 +1715,8 @@ class ViewShardedFitter:
         the preparation stream (_reg_after_exec; the L1 form's tail_fn: neither before the first view nor between the
         last reduction and the parameter update); the depth and D-SSIM forms of the Python schedule take it as it is."""
         reg_fn = (lambda: reg_t) if reg_t is not None else None
-        if native and not self._expo_dev:  # (the exposure form has no executor entry: the Python schedule)
+        if native and not (self._expo_dev or self._wgt_dev):  # (the exposure and weighted forms have no executor entry:
+            #                                                      the Python schedule)
             total = self._views_native(means, scales, colors, opacities, self._depth_grad(), sized=sized, ssim=self._ssim_form())
             return total, self._reg_after_exec(reg_fn, means.device)
         form = self._form()
@@ -1669,6 +1742,8 @@ class ViewShardedFitter:
           exposure  the exposure form (exposure_fused): gr_bwd_fit_exposure_gather in its place, whose photometric term
                  is taken on E_i (clamp01(out), 1), E_i read from the device tensor, and which writes row i of
                  self._expo_rows (d loss / d E); the D-SSIM form's views.
+          weighted  the weighted form (weights): gr_bwd_fit_weighted_gather in its place, every L1 term times the view's
+                 loss weights; the D-SSIM form's views.
         Every reduction batch of a stream adds its views' gradient w.r.t. the activated parameters into that stream's
         accumulator set (_reduce_batch, in view order: deterministic); the sets leave in self._acc_parts, to be summed
         in stream order by the caller (gr_fit_param_step or torch adds).  Returns (the sum of the view losses (device,
@@ -1690,7 +1765,8 @@ class ViewShardedFitter:
         expo = form == "exposure"
         if expo:  # every view's d loss / d E row (gr_bwd_fit_exposure_gather writes its own; other ranks' stay zero)
             self._expo_rows = torch.zeros((len(self.targets), 12), dtype=torch.float32, device=device)
-        sums16 = ("ssim", "exposure")  # the forms whose views without a depth term are _ssim_view's (16-pixel tiles)
+        wgt = form == "weighted"
+        sums16 = ("ssim", "exposure", "weighted")  # the forms whose views without a depth term are _ssim_view's (16-pixel tiles)
         depth = form == "depth" or (form in sums16 and self._depth_grad())
         w_sil, w_depth, g_scale, w_dssim = self._loss_terms(depth, form == "ssim")
         bin_stream = None
@@ -1719,11 +1795,13 @@ class ViewShardedFitter:
             _, _, _, rs = tr.forward_native(m, s, c, o, pv.gv, pv, images=False)  # the backward reads the sums
             pv = None
             # the entries take the same operands, the D-SSIM one its weight behind g_scale, the exposure one the view's
-            # E (a row view of the device tensor: no host read) and its row of d loss / d E
+            # E (a row view of the device tensor: no host read) and its row of d loss / d E, the weighted one the view's
+            # loss weights
             ssim = form == "ssim"
             gather = (tr.backward_fit_exposure_gather_native if expo
+                      else tr.backward_fit_weighted_gather_native if wgt
                       else tr.backward_fit_ssim_gather_native if ssim else tr.backward_fit_gather_native)
-            own = (self._expo[i], self._expo_rows[i]) if expo else (w_dssim,) if ssim else ()
+            own = (self._expo[i], self._expo_rows[i]) if expo else (self.weights[i],) if wgt else (w_dssim,) if ssim else ()
             sums, sums3 = gather(rs, self.targets[i], self.masks[i] if w_sil > 0.0 else None, w_sil,
                                  self.depths[i] if depth else None, w_depth, g_scale, *own, losses_v[j:j + 1])
             return (rs.gv, sums, sums3) if sums3 is not None else (rs.gv, sums)
@@ -1891,8 +1969,8 @@ class ViewShardedFitter:
         form: the batched and graph steps have none."""
         if self._ssim_form() or self.density_stats:  # (a replayed step that overflowed is redone: its statistics
             return False                             # would count twice, so a fit that collects them steps eagerly)
-        if self.exposure:  # (the exposure form has no batched / captured schedule)
-            return False
+        if self.exposure or self.weights is not None:  # (the exposure and weighted forms have no batched / captured
+            return False                               # schedule)
         if self.refine_cameras:  # (captured launches carry the view matrices as kernel arguments)
             return False
         mode = self._graph_mode()
@@ -2592,6 +2670,17 @@ def _load_image(path: Path, width: int, height: int, gray: bool = False) -> np.n
     return np.asarray(img, dtype=np.float32) / 255.0
 
 
+def _load_weights(wdir: Path, stem: str, width: int, height: int) -> torch.Tensor:
+    """--weights_dir's map of one training view: <stem>.npy as it is (the fitter checks shape, dtype and values), else
+    <stem>.png through _load_image (grey, 0..255 -> 0..1, resized like the targets)."""
+    npy, png = wdir / f"{stem}.npy", wdir / f"{stem}.png"
+    if npy.exists():
+        return torch.from_numpy(np.load(npy))
+    if png.exists():
+        return torch.from_numpy(_load_image(png, width, height, gray=True))
+    raise FileNotFoundError(f"--weights_dir: no weight map for training view '{stem}' ({npy.name} or {png.name}) in {wdir}")
+
+
 def orbit_cameras(num_views: int, width: int, height: int, device) -> list:
     """fit_multiview_stub.py:70-90."""
     proj = tr.perspective(60.0, width / height, 0.01, 100.0, device=device)
@@ -2613,6 +2702,11 @@ def main(argv=None) -> None:
     ap.add_argument("--camera_npz", default="")
     ap.add_argument("--masks_dir", default="")
     ap.add_argument("--depth_dir", default="")
+    ap.add_argument("--weights_dir", default="",
+                    help="per-pixel loss weights of the training views: per target <stem>.npy (float32 (height, width), "
+                         "any finite values >= 0), else <stem>.png (grey, 0..255 -> 0..1); every L1 term of a pixel counts "
+                         "that many times (0: a pixel the fit does not see: a passer-by, sky, a lens flare); a training "
+                         "view without a file is an error, held-out views need none; no D-SSIM term (--dssim_weight 0)")
     ap.add_argument("--iters", type=int, default=300)
     ap.add_argument("--lr", type=float, default=0.02)
     ap.add_argument("--width", type=int, default=128)
@@ -2771,6 +2865,9 @@ def main(argv=None) -> None:
         eval_masks = [masks[i] for i in hold] if args.eval_masked else None
         pick = lambda xs: None if xs is None else [xs[i] for i in train]  # noqa: E731
         targets, masks, depths, cams = pick(targets), pick(masks), pick(depths), pick(cams)
+    if args.weights_dir:  # the training views' loss weights (held-out views have none: evaluation is unweighted)
+        refine_weights = [_load_weights(Path(args.weights_dir), paths[i].stem, args.width, args.height).to(device)
+                          for i in train]
     do_eval = args.holdout_every > 0 or args.eval_interval > 0
     eval_log = [] if do_eval else None
 
@@ -2787,6 +2884,8 @@ def main(argv=None) -> None:
         fixed = () if fix in ("none", "") else tuple(int(x) for x in fix.split(","))
         refine.update(exposure=True, exposure_lr=args.exposure_lr, exposure_fixed=fixed,
                       exposure_fused=args.exposure_fused)
+    if args.weights_dir:
+        refine.update(weights=refine_weights)
     params = build_params(args.num_gaussians, device, args.use_sh, args.sh_degree)
     fitter = ViewShardedFitter(params, cams, targets, args.width, args.height, lr=args.lr, masks=masks, depths=depths,
                                silhouette_weight=args.silhouette_weight, depth_weight=args.depth_weight,

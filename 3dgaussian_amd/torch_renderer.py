@@ -519,22 +519,26 @@ def _bwd_ws(L, gv: _native.GrView, n: int, plan, dev, ssim: bool = False, exposu
     return torch.empty((_ws_round(size(ctypes.byref(gv), n, ctypes.byref(plan))),), dtype=torch.uint8, device=dev)
 
 
-def _check_targets(gv: _native.GrView, target, mask, depth_target, dev) -> None:
-    """A view loss's operands (mask and depth_target may be None), read through their raw pointers."""
+def _check_targets(gv: _native.GrView, target, mask, depth_target, dev, weight=None) -> None:
+    """A view loss's operands (mask, depth_target and weight may be None), read through their raw pointers."""
     hw = (gv.height, gv.width)
     _check_operand(target, hw + (3,), "target", dev)
     _check_operand(mask, hw, "mask", dev)
     _check_operand(depth_target, hw, "depth_target", dev)
+    _check_operand(weight, hw, "weight", dev)
 
 
-def _view_loss(target, mask, w_sil: float, g_scale: float, loss_out, depth=None, w_dssim=None, exposure=None) -> list:
+def _view_loss(target, mask, w_sil: float, g_scale: float, loss_out, depth=None, w_dssim=None, exposure=None,
+               weight=None) -> list:
     """The view-loss group of a backward entry, in the ABI's order: ``depth`` = (depth_target, w_depth) for the entries
-    with a depth term, ``w_dssim`` for the D-SSIM entries, ``exposure`` = (exposure, d_exposure) for the exposure entry."""
+    with a depth term, ``w_dssim`` for the D-SSIM entries, ``exposure`` = (exposure, d_exposure) for the exposure entry,
+    ``weight`` the per-pixel loss weights for the weighted entry."""
     f = ctypes.c_float
     return ([_native.ptr(target), _native.ptr(mask), f(w_sil)]
             + ([_native.ptr(depth[0]), f(depth[1])] if depth is not None else [])
             + [f(g_scale)] + ([f(w_dssim)] if w_dssim is not None else [])
             + ([_native.ptr(exposure[0]), _native.ptr(exposure[1])] if exposure is not None else [])
+            + ([_native.ptr(weight)] if weight is not None else [])
             + [_native.ptr(loss_out)])
 
 
@@ -753,10 +757,10 @@ def backward_fit_gather_native(st: RenderState, target, mask, w_sil: float, dept
                             _view_loss(target, mask, w_sil, g_scale, loss_out, (depth_target, w_depth)), True)
 
 
-def _backward_gather(entry: str, st: RenderState, target, mask, depth_target, loss: list, want_sums3: bool):
+def _backward_gather(entry: str, st: RenderState, target, mask, depth_target, loss: list, want_sums3: bool, weight=None):
     """A gather entry: the view's backward up to (sums (n, 8), depth sums (n,) or None), which it allocates."""
     dev = st.saved.device
-    _check_targets(st.gv, target, mask, depth_target, dev)
+    _check_targets(st.gv, target, mask, depth_target, dev, weight)
     sums = torch.empty((st.n, 8), dtype=torch.float32, device=dev)
     sums3 = torch.empty((st.n,), dtype=torch.float32, device=dev) if want_sums3 else None
     _backward_call(entry, st, dev, loss, sums=(sums, sums3))
@@ -801,6 +805,20 @@ def backward_fit_exposure_gather_native(st: RenderState, target, mask, w_sil: fl
                             _view_loss(target, mask, w_sil, g_scale, loss_out, (depth_target, w_depth),
                                        exposure=(exposure, d_exposure)),
                             depth_target is not None)
+
+
+def backward_fit_weighted_gather_native(st: RenderState, target, mask, w_sil: float, depth_target, w_depth: float,
+                                        g_scale: float, weight, loss_out):
+    """gr_bwd_fit_weighted_gather on the current stream: ``backward_fit_gather_native`` with every L1 term (photometric,
+    silhouette, depth) of pixel p times ``weight[p]``, (H, W) float32 on the view's device, finite and >= 0 (the caller
+    checks the values: the kernel reads them as they are); the means keep their denominators 3 HW / HW.  Returns (sums
+    (n, 8), depth sums (n,) or None without a depth target) for reduce_sums_native."""
+    if weight is None:
+        raise ValueError("weight: expected a contiguous float32 tensor, got None (backward_fit_gather_native is the "
+                         "unweighted entry)")
+    return _backward_gather("gr_bwd_fit_weighted_gather", st, target, mask, depth_target,
+                            _view_loss(target, mask, w_sil, g_scale, loss_out, (depth_target, w_depth), weight=weight),
+                            depth_target is not None, weight)
 
 
 def _check_exposure(t, name: str, dev) -> None:
