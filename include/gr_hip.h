@@ -83,7 +83,8 @@ typedef struct gr_view {
                        /* gradient needs (d depth/d w cancels on thin pixels); a backward that  */
                        /* gets no depth gradient runs the two-piece splat (nothing cancels).  1: the caller   */
                        /* will not pass a depth gradient to gr_bwd for this view; W and D are   */
-                       /* then accumulated within 2^-16 relative (as the colours), and gr_bwd   */
+                       /* then accumulated to ~2^-16 relative (as the colours: two bf16 pieces  */
+                       /* per operand, each term within 1.25 x 2^-16, unbiased), and gr_bwd    */
                        /* rejects a non-NULL g_depth (GR_ERR_INVALID_ARGUMENT).  2: no depth    */
                        /* gradient (as 1) but every splat at the default mode's f32 grade       */
                        /* (three-piece splits): the fit path's precision reference              */
