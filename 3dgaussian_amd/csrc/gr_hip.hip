@@ -5483,8 +5483,11 @@ __global__ __launch_bounds__(256) void k_ssim_pixel_grads(ViewK v, const float4*
 // into one pass over a parameter tensor's elements.  Its arithmetic is stated once, in the two routines below:
 //   g_raw = act'(raw) * (((acc0 + acc1) + ...) + reg)     d loss / d raw parameter (torch's backward of
 //                                                         softplus(x) + 1e-3 / sigmoid / identity)
-//   then, with Adam, torch.optim.Adam's update in its own operation order:
-//   m = m + (1 - b1)(g - m); v = v b2 + ((1 - b2) g) g; p = p + step_size m / (sqrt(v) / bc2_sqrt + eps).
+//   then, with Adam, torch.optim.Adam's update, each line one fused multiply-add (adam_elem):
+//   m = m + (1 - b1)(g - m); v = v b2 + (1 - b2)(g g); p = p + step_size (m / (sqrt(v) / bc2_sqrt + eps)).
+//   (torch's addcmul associates ((1 - b2) g) g; both orders have the same roundings and lie within the same
+//   element-wise bars of the float64 update, tests/param_step_reference.py, as does torch's CPU step.  Domain:
+//   |g| <= 1e18, beyond which g g leaves float32's range; eps > 0.)
 // The activation's backward on gact, the summed upstream gradient plus the regulariser's (softplus: threshold 20, as torch).
 __device__ __forceinline__ float act_backward(int act, float gact, float x) {
   if (act == GR_ACT_SOFTPLUS) {  // g z / (z + 1), z = exp(x) (x <= 20), else g
